@@ -9,6 +9,12 @@ A "step" = one complete sample() of a batch of `--batch` slices per GPU (DA-CLIP
 50 UNet forwards + DDIM updates).  Slices are independent, so GPUs shard the slice range with
 no data-path collective (weak scaling); one RCCL all-gather reassembles the output volume at
 the end of the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the
+benchmark measures, outside the timed region: the untimed replay under the rocm-smi clock / power sampler,
+the H2D-inclusive repeat, the per-kernel roofline, the other precisions and samplers (fp16, fp32s, fp32,
+fp8 25-step, ancestral, batch-1 latency) and the CPU baseline (each can still be switched off with its
+--no-* option).  `--dump-outputs DIR` writes what the last timed step returned (see dump_outputs).
 """
 import argparse
 import json
@@ -519,6 +525,25 @@ def clocks_under_load(lib, launches, seconds=1.5):
     return out
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_CAP_BYTES):
+    """Write {name: tensor} as out_dir/<name>.npy in float32.  Each array gets an equal share of `cap`; one over its share
+    is cut to a fixed sample of its slices along dim 0 (seeded, sorted indices: the same ones from run to run for the
+    same arguments)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = cap // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            per = a.nbytes // a.shape[0]
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, share // per), replace=False))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def self_launch(a):
     """`python bench.py --gpus N` from a bare shell: start the N ranks as a CHILD torch.distributed.run (this
     process never touches a GPU), relay its output and exit with its code."""
@@ -541,6 +566,11 @@ def main():
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=16, help="slices per GPU per step (run as two concurrent half-batches)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy (float32, "
+                    "<= 64 MB in all): `denoised` = sample()[-1] (the volume), `noisy_input` = sample()[0]")
+    ap.add_argument("--full", action="store_true", help="also run the measurements beyond the headline figure (clock / power "
+                    "sampler, H2D-inclusive repeat, roofline, other precisions and samplers, CPU baseline); the --no-* "
+                    "options below switch parts of it off")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-clock-replay", action="store_true", help="skip the 1.5 s halo-conv replay behind "
@@ -556,6 +586,8 @@ def main():
                          "workload -- ~30 s per step of 16 slices; a separate variant, never the headline")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the fp8 (configs[4]) and ancestral (configs[3]) legs")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.sampler == "ancestral":
         a.ddim_steps = 1000
 
@@ -586,8 +618,8 @@ def main():
     seeds = torch.arange(lo, hi, dtype=torch.int64) + 1000      # ancestral: step noise keyed by the GLOBAL slice index
 
     def step():
-        out = dif.sample([x], batch_size=B, noise=noise, slice_seeds=seeds)[-1]
-        return parallel.gather_volume(out, world)
+        outs = dif.sample([x], batch_size=B, noise=noise, slice_seeds=seeds)
+        return outs, parallel.gather_volume(outs[-1], world)
 
     for _ in range(a.warmup):
         step()
@@ -596,15 +628,19 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        vol = step()
+        outs, vol = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        noisy = parallel.gather_volume(outs[0], world)          # (a collective: every rank takes part, rank 0 writes)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, {"denoised": vol, "noisy_input": noisy})
     # shader clock / socket power of this workload on this box: sampled over an identical UNTIMED replay of the timed region
     # (rocm-smi forked every 0.4 s from a host thread: host contention and SMU queries stay out of the headline number)
     smi = None
-    if not a.no_smi and world == 1:     # (single-GPU runs only: the multi-rank path stays exactly the timed region + its reduction)
+    if a.full and not a.no_smi and world == 1:     # (single-GPU runs only: the multi-rank path stays exactly the timed region + its reduction)
         smi = SmiSampler()
         smi.__enter__()
         for _ in range(max(1, min(a.steps, 3))):
@@ -620,7 +656,7 @@ def main():
     # copied from PINNED host memory inside the timed region (1 MiB per slice).  Reported beside `value`, which keeps the
     # bench contract's definition (inputs resident in HBM when the timed region starts).
     h2d = None
-    if world == 1 and a.sampler == "ddim":
+    if a.full and world == 1 and a.sampler == "ddim":
         x_host = x.cpu().pin_memory()
         x_dev = torch.empty_like(x)
 
@@ -659,7 +695,7 @@ def main():
                        "collective; 1 all-gather of the output volume"},
             "ms_per_unet_forward_per_slice": round(dt / a.steps / a.ddim_steps / B * 1e3, 3),
             "alg_tflops_sustained": round(ALG_GFLOP_PER_FORWARD * a.ddim_steps * slices / dt / 1e3, 1),
-            "inputs": "resident in HBM when the timed region starts (bench contract); `h2d_inclusive` repeats the region with the "
+            "inputs": "resident in HBM when the timed region starts (bench contract); `h2d_inclusive` (--full) repeats the region with the "
                       "pinned-host -> device copy of the LDCT batch inside it (SURVEY section 8d)",
             "h2d_inclusive": h2d,
             "box_during_untimed_replay": smi.summary() if smi else None,
@@ -675,19 +711,19 @@ def main():
         elif a.precision != "bf16" or a.ddim_steps != S_DDIM:
             res["config"]["workload"] = (f"BASELINE configs[4] geometry: 512x512 slice, {a.ddim_steps}-step DDIM, full FoundDiff "
                                          f"UNet + DA-CLIP RN50 cond, precision {a.precision}")
-        if not a.no_roofline and a.precision == "bf16":
+        if a.full and not a.no_roofline and a.precision == "bf16":
             res["roofline"] = roofline_leg(dif, x, noise, t_measured_ms=res["ms_per_unet_forward_per_slice"],
                                            clock_replay=not a.no_clock_replay)
-        if world == 1 and not a.no_extra_legs and a.precision == "bf16" and a.sampler == "ddim":
+        if a.full and world == 1 and not a.no_extra_legs and a.precision == "bf16" and a.sampler == "ddim":
             res["fp8_25step"] = fp8_leg(dev, x, noise)
             res["ancestral_config3"] = ancestral_leg(dev, x)
             res["latency_b1"] = latency_leg(dev, x, noise)
-        if world == 1 and not a.no_fp32_leg and a.precision == "bf16":
+        if a.full and world == 1 and not a.no_fp32_leg and a.precision == "bf16":
             # the 16-bit engine on the binary16 build: the bf16 mode's speed class at L2 <= 1e-3 against the oracle over the loop
             res["fp16_mode"] = fp32_parity_leg(dev, x, noise, steps=2, precision="fp16")
             res["fp32s_parity_mode"] = fp32_parity_leg(dev, x, noise, precision="fp32s")
             res["fp32_parity_mode"] = fp32_parity_leg(dev, x, noise)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline_leg(w, x, noise)
         print(json.dumps(res), flush=True)
     if world > 1:

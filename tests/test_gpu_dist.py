@@ -58,7 +58,7 @@ def test_bench_self_launch_single_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["FOUNDDIFF_BENCH_FORCE_LAUNCH"] = "1"
     cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0",
-           "--batch", "1", "--no-roofline", "--no-cpu-baseline", "--no-fp32-leg"]
+           "--batch", "1", "--full", "--no-roofline", "--no-cpu-baseline", "--no-fp32-leg"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     import json

@@ -170,6 +170,33 @@ def test_bench_self_launch_command(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_dump_outputs_cap(tmp_path):
+    """bench.dump_outputs: float32 .npy per array, 64 MB in all; an array over its share is cut to the same seeded sample of its
+    slices every time.  And bench.py refuses --steps 0 before it touches a GPU."""
+    import subprocess
+    import sys as _sys
+    import numpy as np
+    sys_path0 = list(_sys.path)
+    _sys.path.insert(0, ROOT)
+    try:
+        import bench
+    finally:
+        _sys.path[:] = sys_path0
+    small = torch.arange(2 * 3 * 4, dtype=torch.float64).reshape(2, 1, 3, 4)
+    big = torch.randn(40, 1, 512, 512, generator=torch.Generator().manual_seed(0))          # 40 MB: over a 32 MB share
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("small", "big")}
+    assert a["small"].dtype == np.float32 and np.array_equal(a["small"], small.float().numpy())
+    assert a["big"].dtype == np.float32 and a["big"].shape == (32, 1, 512, 512)
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_CAP_BYTES
+    rows = [int(np.flatnonzero((big.numpy() == r).all(axis=(1, 2, 3)))[0]) for r in a["big"]]
+    assert rows == sorted(set(rows))                                                          # distinct slices, in order
+    assert np.array_equal(np.load(tmp_path / "b" / "big.npy"), a["big"])
+    r = subprocess.run([_sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
 def test_inspect_checkpoint_tool(tmp_path):
     """tools/inspect_checkpoint.py: the key / shape diff of a `model-N.pt` / `Dose-CLIP.pth` against
     arch.da_unet_spec, on synthetic checkpoints in the reference's format (src/DADiff.py:1626-1669): a good one with

@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
 """Kernel resource usage (VGPR / scratch / occupancy) of one csrc/*.hip file, compactly."""
-import os, re, subprocess, sys
+import atexit, os, re, shutil, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from founddiff_amd import build as _build          # the library's own compiler and flags (HIPCC from the environment, include path from __file__)
 HIPCC = _build.HIPCC
 CFLAGS = [f for f in _build.FLAGS if not f.startswith("-Rpass") and f != "-fPIC"]
 src = sys.argv[1]
+TMP = tempfile.mkdtemp(prefix="kres_")           # private scratch: a fixed path may belong to another user
+atexit.register(shutil.rmtree, TMP, ignore_errors=True)
 if src == "--check-drain":          # (the ISA checks at the end of this file)
     src = None
-r = subprocess.run([HIPCC] + CFLAGS + ["-c", src, "-o", "/tmp/kres.o", "-Rpass-analysis=kernel-resource-usage"],
+r = subprocess.run([HIPCC] + CFLAGS + ["-c", src, "-o", os.path.join(TMP, "kres.o"), "-Rpass-analysis=kernel-resource-usage"],
                    capture_output=True, text=True) if src else subprocess.CompletedProcess([], 0, "", "")
 cur = {}
 for line in r.stderr.splitlines():
@@ -35,7 +37,7 @@ if r.returncode:
 # a consumer above it.  This check reads the ISA anyway: between the last v_mfma in front of a drain block and the block itself
 # no VALU instruction may read a register any of the preceding MFMAs writes.
 def isa_lines(src):
-    asm = "/tmp/kres_%s.s" % os.path.basename(src)
+    asm = os.path.join(TMP, "%s.s" % os.path.basename(src))
     r = subprocess.run([HIPCC] + CFLAGS + ["-S", "--cuda-device-only", src, "-o", asm], capture_output=True, text=True)
     if r.returncode:
         raise RuntimeError(r.stderr[-2000:])

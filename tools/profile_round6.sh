@@ -13,13 +13,13 @@ done
 python3 tools/traffic.py $OUT/FETCH_SIZE $OUT/WRITE_SIZE $OUT/traffic.json > $OUT/traffic_summary.txt 2>&1
 cp $OUT/traffic.json profiles/traffic.json
 # 2. the benches WITHOUT a profiler (the numbers, with clock / power of the timed region)
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
-FOUNDDIFF_STREAMS=1 python3 bench.py --batch 8 --no-cpu-baseline --no-fp32-leg --no-extra-legs --no-roofline > $OUT/bench_one_stream_b8.json 2> $OUT/bench_s1.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+FOUNDDIFF_STREAMS=1 python3 bench.py --full --batch 8 --no-cpu-baseline --no-fp32-leg --no-extra-legs --no-roofline > $OUT/bench_one_stream_b8.json 2> $OUT/bench_s1.err
 # 3. rocprofv3 kernel stats of the default bench and of the one-stream batch-8 bench (exclusive durations)
-rocprofv3 --kernel-trace --stats -d $OUT/stats -o bench --output-format csv -- python3 bench.py --no-cpu-baseline --no-fp32-leg --no-extra-legs --no-clock-replay > $OUT/bench_under_rocprof.json 2> $OUT/bench_prof.err
+rocprofv3 --kernel-trace --stats -d $OUT/stats -o bench --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-fp32-leg --no-extra-legs --no-clock-replay > $OUT/bench_under_rocprof.json 2> $OUT/bench_prof.err
 find $OUT/stats -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats_default_bench.csv \;
 export FOUNDDIFF_STREAMS=1
-rocprofv3 --kernel-trace --stats -d $OUT/stats_s1 -o bench --output-format csv -- python3 bench.py --batch 8 --no-cpu-baseline --no-fp32-leg --no-extra-legs --no-clock-replay > $OUT/bench_one_stream_b8_under_rocprof.json 2> $OUT/bench_prof_s1.err
+rocprofv3 --kernel-trace --stats -d $OUT/stats_s1 -o bench --output-format csv -- python3 bench.py --full --batch 8 --no-cpu-baseline --no-fp32-leg --no-extra-legs --no-clock-replay > $OUT/bench_one_stream_b8_under_rocprof.json 2> $OUT/bench_prof_s1.err
 unset FOUNDDIFF_STREAMS
 find $OUT/stats_s1 -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats_one_stream_b8.csv \;
 # 4. SQ / LDS counters (6 forwards: the one-off DA-CLIP encode is < 4 % of the sums)
