@@ -1,0 +1,433 @@
+// fd_scan_bwd.hip -- the backward of fd_selective_scan_fwd_f32 (fd_scan_ref.hip), i.e. of the reference extension's
+//     selective_scan_cuda_core.bwd(u, delta, A, B, C, D, delta_bias, dout, x, delta_softplus, nrows)
+// in the same operand layout: fp32, L contiguous; u / delta / dout (b, KD, L); A (KD, N); B / C (b, K, N, L);
+// D / delta_bias (KD) or null; channel d reads group g = d / (KD / K).
+//
+//     dt_t = softplus(delta_t + bias) (or without softplus),  a_t = exp(dt_t A),  h_t = a_t h_{t-1} + dt_t B_t u_t
+//     g_t  = dL/dh_t = dout_t C_t + a_{t+1} g_{t+1}                          (the reverse affine recurrence)
+//     dC = sum_{d in g} dout h          dB = sum_{d in g} g dt u          du = D dout + sum_n g dt B
+//     ddt = sum_n g (B u + A a h_{t-1}) ddelta = ddt * sigmoid(delta + bias) (softplus, below its threshold of 20)
+//     dA[d,n] = sum_{b,t} g dt a h_{t-1}   dD[d] = sum_{b,t} dout u   ddelta_bias[d] = sum_{b,t} ddelta
+//
+// Nothing of the forward is stored: the h and g of every position are recomputed from tile carries.  A tile is one
+// wave's span, 64 lanes x 4 consecutive positions.  Four launches (plus one when the rows of a group are split):
+//   1. carry:  per (row, tile, n) the tile's composite Pa = prod a, its local end state H (from h = 0) and its local
+//              reverse composite G (the a_{t0} g_{t0} the tile hands to its predecessor, from a zero carry);
+//   2. chain:  per (row, n) a sequential pass over the tiles turns H into each tile's carry-in h and G into its carry-in g;
+//   3. main:   per (batch, group, tile, row split) a workgroup of 4 waves walks the split's rows, wave w taking every fourth,
+//              replays h forward and g backward inside the tile (wave-level scans), writes du and ddelta per row, keeps dB
+//              and dC of the tile in registers and sums the four waves through LDS in a fixed order; per (row, tile) partials
+//              of dA, dD and ddelta_bias go to the workspace.  Rows are split over workgroups only where (batch, group,
+//              tile) alone would leave the chip idle (the deep levels: L = 1024, up to 1024 rows per group); the splits
+//              then write dB / dC partials that launch 5 sums in split order;
+//   4. params: one workgroup per channel sums the dA / dD / ddelta_bias partials over (batch, tile) in a fixed order.
+// No float atomics anywhere: two calls on the same inputs give the same bits.  States beyond NC = 4 / 8 are walked in
+// chunks of NC; du and the un-scaled ddt then accumulate in place over the chunks (same lane, same addresses).
+#include "fd_common.h"
+
+namespace {
+
+constexpr int SB_E = 4, SB_TILE = 64 * SB_E, SB_T = 256, SB_W = SB_T / 64;
+
+__device__ __forceinline__ void sb_load4(const float *p, int64_t l0, int64_t L, bool vec, float (&v)[SB_E]) {
+    if (vec && l0 + SB_E <= L) {
+        const f32x4 q = *(const f32x4 *)(p + l0);
+        v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+    } else {
+#pragma unroll
+        for (int i = 0; i < SB_E; ++i) v[i] = l0 + i < L ? p[l0 + i] : 0.f;
+    }
+}
+
+__device__ __forceinline__ void sb_store4(float *p, int64_t l0, int64_t L, bool vec, const float (&v)[SB_E]) {
+    if (vec && l0 + SB_E <= L) {
+        *(f32x4 *)(p + l0) = (f32x4){v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int i = 0; i < SB_E; ++i)
+            if (l0 + i < L) p[l0 + i] = v[i];
+    }
+}
+
+// dt of 4 positions (0 past the end: the identity map a = 1, b = 0) and d dt / d delta
+__device__ __forceinline__ void sb_dt(const float (&dl)[SB_E], float bias, int softplus, int64_t l0, int64_t L,
+                                      float (&dt)[SB_E], float (&fac)[SB_E]) {
+#pragma unroll
+    for (int i = 0; i < SB_E; ++i) {
+        const float v = dl[i] + bias;
+        float t = v, f = 1.f;
+        if (softplus) {
+            t = fd_softplus(v);
+            f = v > 20.0f ? 1.f : 1.f / (1.f + __expf(-v));
+        }
+        dt[i] = l0 + i < L ? t : 0.f;
+        fac[i] = f;
+    }
+}
+
+__device__ __forceinline__ float sb_wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// ---- 1. tile composites -------------------------------------------------------------------------------------------
+// ws_pa / ws_h / ws_g: [tile][row][n]
+__global__ __launch_bounds__(SB_T) void scan_bwd_carry_kernel(const float *__restrict__ u, const float *__restrict__ delta,
+                                                             const float *__restrict__ A, const float *__restrict__ Bm,
+                                                             const float *__restrict__ Cm, const float *__restrict__ dbias,
+                                                             const float *__restrict__ dout, int softplus,
+                                                             float *__restrict__ ws_pa, float *__restrict__ ws_h,
+                                                             float *__restrict__ ws_g, int KD, int K, int N, int64_t L,
+                                                             int ntiles, int64_t rows) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int tgroups = (ntiles + SB_W - 1) / SB_W;
+    const int64_t row = blockIdx.x / tgroups;
+    const int tile = (int)(blockIdx.x - row * tgroups) * SB_W + wave;
+    if (tile >= ntiles) return;
+    const int b = (int)(row / KD), d = (int)(row - (int64_t)b * KD);
+    const int g = d / (KD / K);
+    const bool vec = (L & 3) == 0;
+    const int64_t l0 = (int64_t)tile * SB_TILE + lane * SB_E;
+    const float *Bg = Bm + ((int64_t)b * K + g) * N * L, *Cg = Cm + ((int64_t)b * K + g) * N * L;
+    float uu[SB_E], dl[SB_E], dy[SB_E], dt[SB_E], fac[SB_E];
+    sb_load4(u + row * L, l0, L, vec, uu);
+    sb_load4(delta + row * L, l0, L, vec, dl);
+    sb_load4(dout + row * L, l0, L, vec, dy);
+    sb_dt(dl, dbias ? dbias[d] : 0.f, softplus, l0, L, dt, fac);
+    for (int n = 0; n < N; ++n) {
+        const float An = A[(int64_t)d * N + n];
+        float Bv[SB_E], Cv[SB_E], a[SB_E];
+        sb_load4(Bg + (int64_t)n * L, l0, L, vec, Bv);
+        sb_load4(Cg + (int64_t)n * L, l0, L, vec, Cv);
+        float Pa = 1.f, Pb = 0.f, Qb = 0.f;
+#pragma unroll
+        for (int i = 0; i < SB_E; ++i) {
+            a[i] = __expf(dt[i] * An);
+            Pb = a[i] * Pb + dt[i] * Bv[i] * uu[i];
+            Pa = a[i] * Pa;
+        }
+#pragma unroll
+        for (int i = SB_E - 1; i >= 0; --i) Qb = a[i] * (dy[i] * Cv[i] + Qb);
+        // lane 0 composes lanes [0, 2o) from [0, o) and [o, 2o): forward map 1 then 2, reverse map 2 then 1
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const float pa = __shfl_down(Pa, o, 64), pb = __shfl_down(Pb, o, 64), qb = __shfl_down(Qb, o, 64);
+            Pb = pa * Pb + pb;
+            Qb = Pa * qb + Qb;
+            Pa = Pa * pa;
+        }
+        if (lane == 0) {
+            const int64_t k = ((int64_t)tile * rows + row) * N + n;
+            ws_pa[k] = Pa;
+            ws_h[k] = Pb;
+            ws_g[k] = Qb;
+        }
+    }
+}
+
+// ---- 2. carries: H -> h entering tile j, G -> a_{t+1} g_{t+1} entering tile j from its end ----------------------------
+__global__ __launch_bounds__(SB_T) void scan_bwd_chain_kernel(const float *__restrict__ ws_pa, float *__restrict__ ws_h,
+                                                             float *__restrict__ ws_g, int64_t RN, int ntiles) {
+    const int64_t i = (int64_t)blockIdx.x * SB_T + threadIdx.x;
+    if (i >= RN) return;
+    float h = 0.f;
+    for (int j = 0; j < ntiles; ++j) {
+        const int64_t k = (int64_t)j * RN + i;
+        const float a = ws_pa[k], hb = ws_h[k];
+        ws_h[k] = h;
+        h = a * h + hb;
+    }
+    float x = 0.f;
+    for (int j = ntiles - 1; j >= 0; --j) {
+        const int64_t k = (int64_t)j * RN + i;
+        const float a = ws_pa[k], gb = ws_g[k];
+        ws_g[k] = x;
+        x = a * x + gb;
+    }
+}
+
+// ---- 3. the gradients ---------------------------------------------------------------------------------------------------
+// dBo / dCo: [split][b][K][N][L] (split 0 = the outputs themselves when S == 1); part: [N + 2][KD][b][tile]
+template <int NC>
+__global__ __launch_bounds__(SB_T) void scan_bwd_main_kernel(
+    const float *__restrict__ u, const float *__restrict__ delta, const float *__restrict__ A, const float *__restrict__ Bm,
+    const float *__restrict__ Cm, const float *__restrict__ Dv, const float *__restrict__ dbias, const float *__restrict__ dout,
+    int softplus, float *__restrict__ du, float *__restrict__ ddelta, float *__restrict__ dBo, float *__restrict__ dCo,
+    const float *__restrict__ hin, const float *__restrict__ gin, float *__restrict__ part, int batch, int KD, int K, int N,
+    int64_t L, int ntiles, int S) {
+    __shared__ float s_red[SB_W - 1][2][SB_TILE];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int tile = (int)(blockIdx.x % ntiles);
+    const int rest = (int)(blockIdx.x / ntiles);
+    const int s = rest % S, bg = rest / S;
+    const int b = bg / K, g = bg - b * K;
+    const int Dg = KD / K;
+    const int r0 = (int)((int64_t)Dg * s / S), r1 = (int)((int64_t)Dg * (s + 1) / S);
+    const int64_t rows = (int64_t)batch * KD, M = (int64_t)batch * ntiles;
+    const bool vec = (L & 3) == 0;
+    const int64_t l0 = (int64_t)tile * SB_TILE + lane * SB_E;
+    const float *Bg = Bm + (int64_t)bg * N * L, *Cg = Cm + (int64_t)bg * N * L;
+    float *dBs = dBo + ((int64_t)s * batch * K + bg) * N * L, *dCs = dCo + ((int64_t)s * batch * K + bg) * N * L;
+    for (int n0 = 0; n0 < N; n0 += NC) {
+        const bool first = n0 == 0, last = n0 + NC >= N;
+        float accB[NC][SB_E], accC[NC][SB_E];
+#pragma unroll
+        for (int j = 0; j < NC; ++j)
+#pragma unroll
+            for (int i = 0; i < SB_E; ++i) accB[j][i] = accC[j][i] = 0.f;
+        for (int dd = r0 + wave; dd < r1; dd += SB_W) {
+            const int d = g * Dg + dd;
+            const int64_t row = (int64_t)b * KD + d;
+            float uu[SB_E], dl[SB_E], dy[SB_E], dt[SB_E], fac[SB_E], gu[SB_E], gt[SB_E];
+            sb_load4(u + row * L, l0, L, vec, uu);
+            sb_load4(delta + row * L, l0, L, vec, dl);
+            sb_load4(dout + row * L, l0, L, vec, dy);
+            sb_dt(dl, dbias ? dbias[d] : 0.f, softplus, l0, L, dt, fac);
+            if (first) {
+                const float Dd = Dv ? Dv[d] : 0.f;
+#pragma unroll
+                for (int i = 0; i < SB_E; ++i) gu[i] = Dd * dy[i], gt[i] = 0.f;
+            } else {                                         // the chunks before this one left du and the un-scaled ddt
+                sb_load4(du + row * L, l0, L, vec, gu);
+                sb_load4(ddelta + row * L, l0, L, vec, gt);
+            }
+            float pA[NC];
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                pA[j] = 0.f;
+                const int n = n0 + j;
+                if (n >= N) continue;
+                const float An = A[(int64_t)d * N + n];
+                float Bv[SB_E], Cv[SB_E], a[SB_E], hp[SB_E], hv[SB_E];
+                sb_load4(Bg + (int64_t)n * L, l0, L, vec, Bv);
+                sb_load4(Cg + (int64_t)n * L, l0, L, vec, Cv);
+                float Pa = 1.f, Pb = 0.f, Qb = 0.f;
+#pragma unroll
+                for (int i = 0; i < SB_E; ++i) {
+                    a[i] = __expf(dt[i] * An);
+                    hv[i] = dt[i] * Bv[i] * uu[i];           // b_t for now, h_t after the replay
+                    Pb = a[i] * Pb + hv[i];
+                    Pa = a[i] * Pa;
+                }
+#pragma unroll
+                for (int i = SB_E - 1; i >= 0; --i) Qb = a[i] * (dy[i] * Cv[i] + Qb);
+                // inclusive scans over the wave: forward over the lanes before, reverse over the lanes after
+                float fa = Pa, fb = Pb, ra = Pa, rb = Qb;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const float pa = __shfl_up(fa, o, 64), pb = __shfl_up(fb, o, 64);
+                    const float qa = __shfl_down(ra, o, 64), qb = __shfl_down(rb, o, 64);
+                    if (lane >= o) {
+                        fb = fa * pb + fb;
+                        fa = fa * pa;
+                    }
+                    if (lane + o < 64) {
+                        rb = ra * qb + rb;
+                        ra = ra * qa;
+                    }
+                }
+                float ea = __shfl_up(fa, 1, 64), eb = __shfl_up(fb, 1, 64);
+                float xa = __shfl_down(ra, 1, 64), xb = __shfl_down(rb, 1, 64);
+                if (lane == 0) ea = 1.f, eb = 0.f;
+                if (lane == 63) xa = 1.f, xb = 0.f;
+                const int64_t k = ((int64_t)tile * rows + row) * N + n;
+                float h = ea * hin[k] + eb;
+#pragma unroll
+                for (int i = 0; i < SB_E; ++i) {
+                    hp[i] = h;
+                    h = a[i] * h + hv[i];
+                    hv[i] = h;
+                }
+                float X = xa * gin[k] + xb;              // a_{t+1} g_{t+1} after this lane's last position
+#pragma unroll
+                for (int i = SB_E - 1; i >= 0; --i) {
+                    const float gi = dy[i] * Cv[i] + X;
+                    X = a[i] * gi;
+                    const float gdt = gi * dt[i], w = X * hp[i];       // w = g a h_{t-1}
+                    accC[j][i] += dy[i] * hv[i];
+                    accB[j][i] += gdt * uu[i];
+                    gu[i] += gdt * Bv[i];
+                    gt[i] += gi * Bv[i] * uu[i] + An * w;
+                    pA[j] += dt[i] * w;
+                }
+            }
+            float pD = 0.f, pBias = 0.f;
+            if (first)
+#pragma unroll
+                for (int i = 0; i < SB_E; ++i) pD += dy[i] * uu[i];
+            if (last)
+#pragma unroll
+                for (int i = 0; i < SB_E; ++i) {
+                    gt[i] *= fac[i];
+                    if (l0 + i < L) pBias += gt[i];
+                }
+            sb_store4(du + row * L, l0, L, vec, gu);
+            sb_store4(ddelta + row * L, l0, L, vec, gt);
+            const int64_t pk = ((int64_t)d * batch + b) * ntiles + tile, qs = (int64_t)KD * M;
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                if (n0 + j >= N) continue;
+                const float v = sb_wave_sum(pA[j]);
+                if (lane == 0) part[(n0 + j) * qs + pk] = v;
+            }
+            if (first) {
+                const float v = sb_wave_sum(pD);
+                if (lane == 0) part[N * qs + pk] = v;
+            }
+            if (last) {
+                const float v = sb_wave_sum(pBias);
+                if (lane == 0) part[(N + 1) * qs + pk] = v;
+            }
+        }
+        // dB / dC of the tile: wave 0 + wave 1 + wave 2 + wave 3
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            if (n0 + j >= N) continue;
+            if (wave > 0)
+#pragma unroll
+                for (int i = 0; i < SB_E; ++i) {
+                    s_red[wave - 1][0][lane * SB_E + i] = accB[j][i];
+                    s_red[wave - 1][1][lane * SB_E + i] = accC[j][i];
+                }
+            __syncthreads();
+            if (wave == 0) {
+                float vb[SB_E], vc[SB_E];
+#pragma unroll
+                for (int i = 0; i < SB_E; ++i) {
+                    vb[i] = accB[j][i];
+                    vc[i] = accC[j][i];
+#pragma unroll
+                    for (int w = 0; w < SB_W - 1; ++w) {
+                        vb[i] += s_red[w][0][lane * SB_E + i];
+                        vc[i] += s_red[w][1][lane * SB_E + i];
+                    }
+                }
+                sb_store4(dBs + (int64_t)(n0 + j) * L, l0, L, vec, vb);
+                sb_store4(dCs + (int64_t)(n0 + j) * L, l0, L, vec, vc);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// ---- 4. dA / dD / ddelta_bias: one workgroup per channel, partials over (batch, tile) in a fixed order ------------------
+__global__ __launch_bounds__(SB_T) void scan_bwd_param_kernel(const float *__restrict__ part, int KD, int N, int64_t M,
+                                                             float *__restrict__ dA, float *__restrict__ dD,
+                                                             float *__restrict__ dbias) {
+    __shared__ float s[SB_T];
+    const int tid = threadIdx.x, d = blockIdx.x;
+    for (int q = 0; q < N + 2; ++q) {
+        float *dst = q < N ? dA + (int64_t)d * N + q : q == N ? (dD ? dD + d : nullptr) : (dbias ? dbias + d : nullptr);
+        if (!dst) continue;
+        const float *p = part + ((int64_t)q * KD + d) * M;
+        float v = 0.f;
+        for (int64_t m = tid; m < M; m += SB_T) v += p[m];
+        s[tid] = v;
+        __syncthreads();
+        for (int o = SB_T / 2; o > 0; o >>= 1) {
+            if (tid < o) s[tid] += s[tid + o];
+            __syncthreads();
+        }
+        if (tid == 0) *dst = s[0];
+        __syncthreads();
+    }
+}
+
+// ---- 5. dB / dC over the row splits, in split order ---------------------------------------------------------------------
+__global__ __launch_bounds__(SB_T) void scan_bwd_bc_kernel(const float *__restrict__ pB, const float *__restrict__ pC,
+                                                          int S, int64_t tot, float *__restrict__ dB, float *__restrict__ dC) {
+    const int64_t i = (int64_t)blockIdx.x * SB_T + threadIdx.x;
+    if (i >= tot) return;
+    float vb = 0.f, vc = 0.f;
+    for (int s = 0; s < S; ++s) {
+        vb += pB[(int64_t)s * tot + i];
+        vc += pC[(int64_t)s * tot + i];
+    }
+    dB[i] = vb;
+    dC[i] = vc;
+}
+
+int sb_ntiles(int64_t L) { return (int)((L + SB_TILE - 1) / SB_TILE); }
+
+// row splits per (batch, group, tile): enough workgroups to fill the chip, at least 16 rows (4 per wave) per split
+int sb_splits(int batch, int KD, int K, int64_t L) {
+    const int64_t wg = (int64_t)batch * K * sb_ntiles(L);
+    const int Dg = KD / K;
+    int S = 1;
+    while (wg * S < 1024 && S * 2 * 16 <= Dg) S *= 2;
+    return S;
+}
+
+int64_t sb_round4(int64_t n) { return (n + 3) & ~(int64_t)3; }
+
+struct SbLayout {
+    int ntiles, S;
+    int64_t comp, part, bc, total;        // floats: each of the 3 composite arrays, the parameter partials, each dB / dC slab set
+};
+
+SbLayout sb_layout(int batch, int KD, int K, int N, int64_t L) {
+    SbLayout w;
+    w.ntiles = sb_ntiles(L);
+    w.S = sb_splits(batch, KD, K, L);
+    w.comp = sb_round4((int64_t)w.ntiles * batch * KD * N);
+    w.part = sb_round4((int64_t)(N + 2) * KD * batch * w.ntiles);
+    w.bc = w.S > 1 ? sb_round4((int64_t)w.S * batch * K * N * L) : 0;
+    w.total = 3 * w.comp + w.part + 2 * w.bc;
+    return w;
+}
+
+}  // namespace
+
+extern "C" int64_t fd_selective_scan_bwd_ws_floats(int batch, int KD, int K, int N, int64_t L) {
+    if (batch <= 0 || KD <= 0 || K <= 0 || N <= 0 || L <= 0 || KD % K) return 0;
+    return sb_layout(batch, KD, K, N, L).total;
+}
+
+extern "C" int fd_selective_scan_bwd_f32(const float *u, const float *delta, const float *A, const float *B, const float *C,
+                                         const float *D, const float *delta_bias, const float *dout, int delta_softplus,
+                                         int nrows, int batch, int KD, int K, int N, int64_t L, float *du, float *ddelta,
+                                         float *dA, float *dB, float *dC, float *dD, float *ddelta_bias, float *ws,
+                                         void *stream) {
+    FD_REQUIRE(u && delta && A && B && C && dout && du && ddelta && dA && dB && dC && ws,
+               "fd_selective_scan_bwd_f32: null pointer");
+    FD_REQUIRE(!D == !dD, "fd_selective_scan_bwd_f32: dD must be given exactly when D is");
+    FD_REQUIRE(!delta_bias == !ddelta_bias, "fd_selective_scan_bwd_f32: ddelta_bias must be given exactly when delta_bias is");
+    FD_REQUIRE(nrows >= 1 && nrows <= 4, "fd_selective_scan_bwd_f32: nrows=%d not in 1..4", nrows);
+    FD_REQUIRE(batch > 0 && KD > 0 && K > 0 && L > 0 && KD % (K * nrows) == 0,
+               "fd_selective_scan_bwd_f32: u.shape[1]=%d must be a multiple of B.shape[1]*nrows=%d*%d", KD, K, nrows);
+    FD_REQUIRE(N >= 1 && N <= 256, "fd_selective_scan_bwd_f32: d_state=%d not in 1..256", N);
+    FD_REQUIRE((((uintptr_t)u | (uintptr_t)delta | (uintptr_t)B | (uintptr_t)C | (uintptr_t)dout | (uintptr_t)du |
+                 (uintptr_t)ddelta | (uintptr_t)dB | (uintptr_t)dC | (uintptr_t)ws) & 15) == 0,
+               "fd_selective_scan_bwd_f32: tensors must be 16-byte aligned");
+    const SbLayout w = sb_layout(batch, KD, K, N, L);
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t rows = (int64_t)batch * KD, RN = rows * N;
+    float *pa = ws, *hh = ws + w.comp, *gg = ws + 2 * w.comp, *part = ws + 3 * w.comp;
+    float *pB = w.S > 1 ? part + w.part : dB, *pC = w.S > 1 ? part + w.part + w.bc : dC;
+    const int tgroups = (w.ntiles + SB_W - 1) / SB_W;
+    hipLaunchKernelGGL(scan_bwd_carry_kernel, dim3((unsigned)(rows * tgroups)), dim3(SB_T), 0, st, u, delta, A, B, C,
+                       delta_bias, dout, delta_softplus, pa, hh, gg, KD, K, N, L, w.ntiles, rows);
+    FD_LAUNCH_OK("fd_selective_scan_bwd_f32 (carry)");
+    hipLaunchKernelGGL(scan_bwd_chain_kernel, dim3((unsigned)((RN + SB_T - 1) / SB_T)), dim3(SB_T), 0, st, pa, hh, gg, RN,
+                       w.ntiles);
+    FD_LAUNCH_OK("fd_selective_scan_bwd_f32 (chain)");
+    const dim3 grid((unsigned)((int64_t)batch * K * w.S * w.ntiles));
+    if (N <= 4)
+        hipLaunchKernelGGL(scan_bwd_main_kernel<4>, grid, dim3(SB_T), 0, st, u, delta, A, B, C, D, delta_bias, dout,
+                           delta_softplus, du, ddelta, pB, pC, hh, gg, part, batch, KD, K, N, L, w.ntiles, w.S);
+    else
+        hipLaunchKernelGGL(scan_bwd_main_kernel<8>, grid, dim3(SB_T), 0, st, u, delta, A, B, C, D, delta_bias, dout,
+                           delta_softplus, du, ddelta, pB, pC, hh, gg, part, batch, KD, K, N, L, w.ntiles, w.S);
+    FD_LAUNCH_OK("fd_selective_scan_bwd_f32 (main)");
+    hipLaunchKernelGGL(scan_bwd_param_kernel, dim3((unsigned)KD), dim3(SB_T), 0, st, part, KD, N, (int64_t)batch * w.ntiles,
+                       dA, dD, ddelta_bias);
+    FD_LAUNCH_OK("fd_selective_scan_bwd_f32 (params)");
+    if (w.S > 1) {
+        const int64_t tot = (int64_t)batch * K * N * L;
+        hipLaunchKernelGGL(scan_bwd_bc_kernel, dim3((unsigned)((tot + SB_T - 1) / SB_T)), dim3(SB_T), 0, st, pB, pC, w.S,
+                           tot, dB, dC);
+        FD_LAUNCH_OK("fd_selective_scan_bwd_f32 (dB / dC splits)");
+    }
+    return FD_OK;
+}

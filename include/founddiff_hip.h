@@ -356,6 +356,16 @@ int fd_selective_scan_fwd_f32(const float *u, const float *delta, const float *A
                               const float *C, const float *D, const float *delta_bias, int delta_softplus,
                               int nrows, int batch, int KD, int K, int N, int64_t L, float *out, float *x_last,
                               void *stream);
+/* Its backward (selective_scan_cuda_core.bwd, src/emamba2.py:172): the same operands plus dout [batch,KD,L]; writes
+ *   du, ddelta [batch,KD,L]   dA [KD,N]   dB, dC [batch,K,N,L]   dD, ddelta_bias [KD] (NULL exactly when D / delta_bias are)
+ * No forward state is read: h and dL/dh are recomputed from tile carries the call computes itself (fd_scan_bwd.hip).
+ * Deterministic (fixed-order reductions, no float atomics).  ws: fd_selective_scan_bwd_ws_floats(...) floats, 16-byte
+ * aligned.  nrows, K and alignment are validated as in the forward.                                           */
+int64_t fd_selective_scan_bwd_ws_floats(int batch, int KD, int K, int N, int64_t L);
+int fd_selective_scan_bwd_f32(const float *u, const float *delta, const float *A, const float *B, const float *C,
+                              const float *D, const float *delta_bias, const float *dout, int delta_softplus, int nrows,
+                              int batch, int KD, int K, int N, int64_t L, float *du, float *ddelta, float *dA, float *dB,
+                              float *dC, float *dD, float *ddelta_bias, float *ws, void *stream);
 
 /* ---- channel ("transposed") attention, src/DADiff.py:263-285 ------------------------------
  * fd_chan_attn_gram: per (b, head) partial 32x32 Gram q^T k and sums of squares over pixel
