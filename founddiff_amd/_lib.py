@@ -98,6 +98,10 @@ SIGNATURES = {
     "fd_selective_scan_bwd_ws_floats": (i64, [i32, i32, i32, i32, i64]),
     "fd_selective_scan_bwd_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64,
                                         vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "fd_cross_scan_fwd_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "fd_cross_scan_bwd_ws_floats": (i64, [i32, i32, i32, i32, i32, i32]),
+    "fd_cross_scan_bwd_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32,
+                                    vp]),
     "fd_chan_attn_nblk": (i32, [i64]),
     "fd_chan_attn_gram": (i32, [i32, vp, i32, i64, i32, vp, vp]),
     "fd_chan_attn_weff": (i32, [i32, vp, i32, vp, vp, vp, i32, i32, vp]),

@@ -367,6 +367,28 @@ int fd_selective_scan_bwd_f32(const float *u, const float *delta, const float *A
                               int batch, int KD, int K, int N, int64_t L, float *du, float *ddelta, float *dA, float *dB,
                               float *dC, float *dD, float *ddelta_bias, float *ws, void *stream);
 
+/* ---- The reference's cross_selective_scan (src/emamba2.py:295-367) up to out_norm, for training, fp32 (fd_cross_scan_bwd.hip).
+ * Forward: x [B,D,H,W] (NCHW, forward_corev2's layout) -> xc [B,H,W,D] (NHWC), the x_proj gather as fd_conv2d with ndir = 4
+ * (exact fp32) -> xdbl [4,B,L,CD], fd_selective_scan in FD_F32 -> y [B,H,W,D] at the merged pixels.  Operands as for
+ * fd_selective_scan: x_proj_w [4][CD][D], dtw [4,D,R], dtb [4,D], A [4*D,N] (= -exp(A_logs)), Ds [4*D]; ws: fd_scan_ws_floats(...)
+ * floats.  xc and xdbl are everything the backward reads of the forward.
+ * Backward: dy [B,H,W,D] (the gradient of y) -> dx [B,D,H,W] (NCHW), dx_proj_w [4][CD][D], ddtw [4,D,R], ddtb [4,D], dA [4*D,N],
+ * dDs [4*D], all written (not accumulated).  The selective-scan gradients of fd_selective_scan_bwd_f32 on the gathered
+ * operands, the dt_proj and x_proj einsums' backwards and the gather / merge as index maps: no activation-sized tensor is
+ * written besides dx.  Odd H / W: the padded positions take part with u = 0, a zero x_dbl row and dy = 0, as in the
+ * reference's EfficientScan / EfficientMerge (src/emamba2.py:191-199, 253-260).  Deterministic (fixed-order sums, no float
+ * atomics); tile sizes, channel splits and reduction orders depend on (H, W, D, N, R) only, so a slice's dx is the same bits
+ * alone or in a batch.  ws: fd_cross_scan_bwd_ws_floats(...) floats, 0 for an unsupported shape.  D % 64 == 0,
+ * N in {4, 8, 16, 32}, R in {2, 4, 8, 16, 32}; xc, dy, ws 16-byte aligned.                                                 */
+int fd_cross_scan_fwd_f32(const float *x, const float *x_proj_w, const float *dtw, const float *dtb, const float *A,
+                          const float *Ds, float *xc, float *xdbl, float *y, float *ws, int B, int H, int W, int D, int N,
+                          int R, void *stream);
+int64_t fd_cross_scan_bwd_ws_floats(int B, int H, int W, int D, int N, int R);
+int fd_cross_scan_bwd_f32(const float *xc, const float *xdbl, const float *x_proj_w, const float *dtw, const float *dtb,
+                          const float *A, const float *Ds, const float *dy, float *dx, float *dx_proj_w, float *ddtw,
+                          float *ddtb, float *dA, float *dDs, float *ws, int B, int H, int W, int D, int N, int R,
+                          void *stream);
+
 /* ---- channel ("transposed") attention, src/DADiff.py:263-285 ------------------------------
  * fd_chan_attn_gram: per (b, head) partial 32x32 Gram q^T k and sums of squares over pixel
  *   blocks.  qkv [B,HW,3C] (dtype).  partial: fp32 [B][heads][nblk][32*32+64].
