@@ -102,6 +102,14 @@ SIGNATURES = {
     "fd_cross_scan_bwd_ws_floats": (i64, [i32, i32, i32, i32, i32, i32]),
     "fd_cross_scan_bwd_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32,
                                     vp]),
+    "fd_cross_scan_fwd_nhwc_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "fd_cross_scan_bwd_nhwc_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32,
+                                         i32, vp]),
+    "fd_dwconv3x3_silu_bwd_ws_floats": (i64, [i32, i32, i32, i32]),
+    "fd_dwconv3x3_silu_bwd_f32": (i32, [vp, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "fd_ln_silu_gate_fwd_f32": (i32, [vp, vp, vp, f32, vp, i32, i32, vp, i32, vp, vp, i32, i64, i32, vp]),
+    "fd_ln_silu_gate_bwd_ws_floats": (i64, [i32, i64, i32]),
+    "fd_ln_silu_gate_bwd_f32": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, i32, i64, i32, vp]),
     "fd_chan_attn_nblk": (i32, [i64]),
     "fd_chan_attn_gram": (i32, [i32, vp, i32, i64, i32, vp, vp]),
     "fd_chan_attn_weff": (i32, [i32, vp, i32, vp, vp, vp, i32, i32, vp]),

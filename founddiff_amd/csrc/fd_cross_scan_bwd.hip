@@ -28,6 +28,10 @@
 //   6. the dx_proj_w partials and 7. the parameter partials summed over (batch, block) in a fixed order.
 // Tile length, channel split and every reduction order are functions of (H, W, D, N, R) only, never of the batch: a slice's
 // y and dx are the same bits alone or in a batch.  No float atomics.  fp32 throughout; the same code in both library builds.
+// fd_cross_scan_fwd_nhwc_f32 / fd_cross_scan_bwd_nhwc_f32 (founddiff_amd.ss2d_train) are the same launches with NHWC on both
+// sides: the forward without the layout move, the backward with the kernels' NHWC template parameter set (a second instantiation: the NCHW one
+// is the code it was, register for register) -- launch 3 sends du back through the slab
+// buffer and stores it as the slab was loaded, launch 5 adds W^T dxdbl in its lane = channel loop.
 #include "fd_common.h"
 
 namespace {
@@ -59,8 +63,8 @@ __device__ __forceinline__ float cs_wave_sum(float v) {
 
 // ---- 1. / 3. carry and main ---------------------------------------------------------------------------------------------
 // ws_pa / ws_h / ws_g: [tile][row][n], row = b 4D + k D + d.  dxp: [split][4][B][L][CD].  part: [b ntiles + tile][4D][N + R + 2]
-// (dA n | ddtw r | dD | ddtb).
-template <int N, int R, bool MAIN>
+// (dA n | ddtw r | dD | ddtb).  NHWC (MAIN only): dx is [B,H,W,D] (fd_cross_scan_bwd_nhwc_f32) instead of [B,D,H,W].
+template <int N, int R, bool MAIN, bool NHWC = false>
 __global__ __launch_bounds__(CS_T) void cs_scan_kernel(const float *__restrict__ xc, const float *__restrict__ xdbl,
                                                       const float *__restrict__ dy, const float *__restrict__ dtw,
                                                       const float *__restrict__ dtb, const float *__restrict__ A,
@@ -229,6 +233,12 @@ __global__ __launch_bounds__(CS_T) void cs_scan_kernel(const float *__restrict__
                         pA[n] += dt[i] * w;
                     }
                 }
+                if constexpr (NHWC) {
+                    // NHWC dx: du, complete here, goes back over this channel's u in the slab buffer (read by this lane alone,
+                    // above) and the slab leaves as it came, 16 bytes per (pixel, 4 channels), after the channel loop
+#pragma unroll
+                    for (int i = 0; i < E; ++i) sU[cl * TP + p0 + i] = gu[i];
+                }
                 float pD = 0.f, pBias = 0.f, pR[R];
 #pragma unroll
                 for (int i = 0; i < E; ++i) {
@@ -246,11 +256,13 @@ __global__ __launch_bounds__(CS_T) void cs_scan_kernel(const float *__restrict__
                         pR[r] += gt[i] * sT[r * TP + p0 + i];
                     }
                 }
-                float *dxd = dx + ((int64_t)b * g.D + d) * HW;
+                if constexpr (!NHWC) {
+                    float *dxd = dx + ((int64_t)b * g.D + d) * HW;
 #pragma unroll
-                for (int i = 0; i < E; ++i) {
-                    const int pix = sPix[p0 + i];
-                    if (pix >= 0) dxd[pix] = gu[i];
+                    for (int i = 0; i < E; ++i) {
+                        const int pix = sPix[p0 + i];
+                        if (pix >= 0) dxd[pix] = gu[i];
+                    }
                 }
                 float *pp = part + ((int64_t)b * g.ntiles + tile) * (4 * (int64_t)g.D * J) + (int64_t)kd * J;
 #pragma unroll
@@ -268,6 +280,17 @@ __global__ __launch_bounds__(CS_T) void cs_scan_kernel(const float *__restrict__
                     pp[N + R] = vD;
                     pp[N + R + 1] = vB;
                 }
+            }
+        }
+        if constexpr (MAIN && NHWC) {
+            __syncthreads();
+            for (int idx = threadIdx.x; idx < TILE * (CS_SLAB / 4); idx += CS_T) {
+                const int lt = idx >> 2, q = idx & 3;
+                const int pix = sPix[lt];
+                if (pix < 0) continue;
+                const f32x4 v = {sU[(4 * q) * TP + lt], sU[(4 * q + 1) * TP + lt], sU[(4 * q + 2) * TP + lt],
+                                 sU[(4 * q + 3) * TP + lt]};
+                *(f32x4 *)(dx + ((int64_t)b * HW + pix) * g.D + cs + 4 * q) = v;
             }
         }
     }
@@ -351,9 +374,10 @@ __global__ __launch_bounds__(CS_T) void cs_param_kernel(const float *__restrict_
 // ---- 5. the x_proj einsum's backward -------------------------------------------------------------------------------------
 // One wave per (256 sub-grid rows, batch x direction, 64 channels), in blocks of 64 rows: dx[b, d, p] += sum_c W[k, c, d] dxdbl[c]
 // with lane = row (W's 64 x CD slab in LDS, read as broadcasts), then lane = channel: wpart[b nxb + blk][k][c][d] +=
-// dxdbl[c] u over the rows in order (u from xc: 256 coalesced bytes per pixel).
+// dxdbl[c] u over the rows in order (u from xc: 256 coalesced bytes per pixel).  NHWC dx: the dx += moves into the second loop
+// (lane = channel, 256 coalesced bytes per pixel there too), the sum over c in the same order.
 constexpr int XB = 64, XBL = 4;
-template <int N, int R>
+template <int N, int R, bool NHWC = false>
 __global__ __launch_bounds__(64) void cs_xproj_kernel(const float *__restrict__ xc, const float *__restrict__ dxdbl,
                                                      const float *__restrict__ xw, float *__restrict__ dx,
                                                      float *__restrict__ wpart, const CsGeom g) {
@@ -395,7 +419,7 @@ __global__ __launch_bounds__(64) void cs_xproj_kernel(const float *__restrict__ 
 #pragma unroll
             for (int c = 0; c < CD; ++c) v[c] = sX[lane * CS + c];
             const int pix = sP[lane];
-            if (pix >= 0) {
+            if (!NHWC && pix >= 0) {
                 float *dxp = dx + ((int64_t)b * g.D + d0) * HW + pix;
                 for (int j = 0; j < 64; ++j) {
                     float t = 0.f;
@@ -409,9 +433,16 @@ __global__ __launch_bounds__(64) void cs_xproj_kernel(const float *__restrict__ 
         for (int r = 0; r < XB; ++r) {
             const int pix = sP[r];
             if (pix < 0) continue;
-            const float u = xc[((int64_t)b * HW + pix) * g.D + d0 + lane];
+            const int64_t o = ((int64_t)b * HW + pix) * g.D + d0 + lane;
+            const float u = xc[o];
 #pragma unroll
             for (int c = 0; c < CD; ++c) acc[c] += sX[r * CS + c] * u;
+            if constexpr (NHWC) {
+                float t = 0.f;
+#pragma unroll
+                for (int c = 0; c < CD; ++c) t += sW[c * 64 + lane] * sX[r * CS + c];
+                dx[o] += t;
+            }
         }
     }
     float *wp = wpart + (((int64_t)b * g.nxb + blk) * 4 + k) * CD * g.D + d0 + lane;
@@ -467,7 +498,7 @@ bool cs_shape_ok(int B, int H, int W, int D, int N, int R) {
            (R == 2 || R == 4 || R == 8 || R == 16 || R == 32) && (int64_t)H * W * D * 4 < (1ll << 31);
 }
 
-template <int N, int R>
+template <int N, int R, bool NHWC>
 void cs_launch(const CsLayout &w, const float *xc, const float *xdbl, const float *xw, const float *dtw, const float *dtb,
                const float *A, const float *Ds, const float *dy, float *dx, float *dxw, float *ddtw, float *ddtb, float *dA,
                float *dDs, float *ws, hipStream_t st) {
@@ -479,13 +510,13 @@ void cs_launch(const CsLayout &w, const float *xc, const float *xdbl, const floa
                        dx, nullptr, nullptr, g);
     const int64_t RN = (int64_t)g.B * 4 * g.D * N;
     hipLaunchKernelGGL(cs_chain_kernel, dim3((unsigned)((RN + CS_T - 1) / CS_T)), dim3(CS_T), 0, st, pa, hh, gg, RN, g.ntiles);
-    hipLaunchKernelGGL((cs_scan_kernel<N, R, true>), grid, dim3(CS_T), 0, st, xc, xdbl, dy, dtw, dtb, A, Ds, pa, hh, gg, dx,
+    hipLaunchKernelGGL((cs_scan_kernel<N, R, true, NHWC>), grid, dim3(CS_T), 0, st, xc, xdbl, dy, dtw, dtb, A, Ds, pa, hh, gg, dx,
                        g.S > 1 ? dxp : dxd, part, g);
     if (g.S > 1) {
         const int64_t tot = (int64_t)4 * g.B * g.L * g.CD;
         hipLaunchKernelGGL(cs_sum_kernel, dim3((unsigned)((tot + CS_T - 1) / CS_T)), dim3(CS_T), 0, st, dxp, g.S, tot, dxd);
     }
-    hipLaunchKernelGGL((cs_xproj_kernel<N, R>), dim3((unsigned)g.nxb, (unsigned)(g.B * 4), (unsigned)(g.D / 64)), dim3(64), 0,
+    hipLaunchKernelGGL((cs_xproj_kernel<N, R, NHWC>), dim3((unsigned)g.nxb, (unsigned)(g.B * 4), (unsigned)(g.D / 64)), dim3(64), 0,
                        st, xc, dxd, xw, dx, wpart, g);
     const int64_t Qw = (int64_t)4 * g.CD * g.D;
     hipLaunchKernelGGL(cs_sum_kernel, dim3((unsigned)((Qw + CS_T - 1) / CS_T)), dim3(CS_T), 0, st, wpart, g.B * g.nxb, Qw, dxw);
@@ -501,23 +532,13 @@ extern "C" int64_t fd_cross_scan_bwd_ws_floats(int B, int H, int W, int D, int N
     return cs_layout(B, H, W, D, N, R).total;
 }
 
-extern "C" int fd_cross_scan_fwd_f32(const float *x, const float *x_proj_w, const float *dtw, const float *dtb, const float *A,
-                                     const float *Ds, float *xc, float *xdbl, float *y, float *ws, int B, int H, int W, int D,
-                                     int N, int R, void *stream) {
-    FD_REQUIRE(x && x_proj_w && dtw && dtb && A && Ds && xc && xdbl && y && ws, "fd_cross_scan_fwd_f32: null pointer");
-    FD_REQUIRE(cs_shape_ok(B, H, W, D, N, R),
-               "fd_cross_scan_fwd_f32: unsupported shape B=%d H=%d W=%d d_inner=%d d_state=%d dt_rank=%d (d_inner %% 64 == 0, "
-               "N in {4,8,16,32}, R in {2,4,8,16,32})", B, H, W, D, N, R);
-    FD_REQUIRE((((uintptr_t)x | (uintptr_t)xc | (uintptr_t)xdbl | (uintptr_t)y | (uintptr_t)x_proj_w) & 15) == 0,
-               "fd_cross_scan_fwd_f32: tensors must be 16-byte aligned");
-    const hipStream_t st = (hipStream_t)stream;
-    const int64_t HW = (int64_t)H * W;
-    hipLaunchKernelGGL(cs_nchw_nhwc_kernel, dim3((unsigned)((HW + 63) / 64), (unsigned)(D / 64), (unsigned)B), dim3(CS_T), 0,
-                       st, x, xc, D, HW);
-    FD_LAUNCH_OK("fd_cross_scan_fwd_f32 (layout)");
+namespace {
+
+// the x_proj gather (src/emamba2.py:335) as the engine's fp32 parity mode runs it -- 4 stride-2 sub-grids, exact fp32, out-of-image
+// pixels of odd sizes zero-filled -- and the scan, from xc [B,H,W,D]
+int cs_fwd_from_xc(const float *xc, const float *x_proj_w, const float *dtw, const float *dtb, const float *A, const float *Ds,
+                   float *xdbl, float *y, float *ws, int B, int H, int W, int D, int N, int R, void *stream) {
     const int H2 = (H + 1) / 2, W2 = (W + 1) / 2, CD = R + 2 * N;
-    // the x_proj gather (src/emamba2.py:335) as the engine's fp32 parity mode runs it: 4 stride-2 sub-grids, exact fp32,
-    // out-of-image pixels of odd sizes zero-filled
     fd_conv_params p = {};
     p.dtype = FD_F32;
     p.out_f32 = 1;
@@ -539,20 +560,23 @@ extern "C" int fd_cross_scan_fwd_f32(const float *x, const float *x_proj_w, cons
     return fd_selective_scan(FD_F32, xc, xdbl, dtw, dtb, A, Ds, y, ws, B, H, W, D, N, R, stream);
 }
 
-extern "C" int fd_cross_scan_bwd_f32(const float *xc, const float *xdbl, const float *x_proj_w, const float *dtw,
-                                     const float *dtb, const float *A, const float *Ds, const float *dy, float *dx, float *dx_proj_w,
-                                     float *ddtw, float *ddtb, float *dA, float *dDs, float *ws, int B, int H, int W, int D, int N,
-                                     int R, void *stream) {
+int cs_bwd(const char *name, int nhwc, const float *xc, const float *xdbl, const float *x_proj_w, const float *dtw,
+           const float *dtb, const float *A, const float *Ds, const float *dy, float *dx, float *dx_proj_w, float *ddtw,
+           float *ddtb, float *dA, float *dDs, float *ws, int B, int H, int W, int D, int N, int R, void *stream) {
     FD_REQUIRE(xc && xdbl && x_proj_w && dtw && dtb && A && Ds && dy && dx && dx_proj_w && ddtw && ddtb && dA && dDs && ws,
-               "fd_cross_scan_bwd_f32: null pointer");
+               "%s: null pointer", name);
     FD_REQUIRE(cs_shape_ok(B, H, W, D, N, R),
-               "fd_cross_scan_bwd_f32: unsupported shape B=%d H=%d W=%d d_inner=%d d_state=%d dt_rank=%d (d_inner %% 64 == 0, "
-               "N in {4,8,16,32}, R in {2,4,8,16,32})", B, H, W, D, N, R);
-    FD_REQUIRE((((uintptr_t)xc | (uintptr_t)dy | (uintptr_t)ws) & 15) == 0, "fd_cross_scan_bwd_f32: tensors must be 16-byte aligned");
+               "%s: unsupported shape B=%d H=%d W=%d d_inner=%d d_state=%d dt_rank=%d (d_inner %% 64 == 0, "
+               "N in {4,8,16,32}, R in {2,4,8,16,32})", name, B, H, W, D, N, R);
+    FD_REQUIRE((((uintptr_t)xc | (uintptr_t)dy | (uintptr_t)ws | (nhwc ? (uintptr_t)dx : 0)) & 15) == 0,
+               "%s: tensors must be 16-byte aligned", name);
     const CsLayout w = cs_layout(B, H, W, D, N, R);
     const hipStream_t st = (hipStream_t)stream;
 #define FD_CS_R(NN, RR) \
-    case RR: cs_launch<NN, RR>(w, xc, xdbl, x_proj_w, dtw, dtb, A, Ds, dy, dx, dx_proj_w, ddtw, ddtb, dA, dDs, ws, st); break;
+    case RR:                                                                                                            \
+        if (nhwc) cs_launch<NN, RR, true>(w, xc, xdbl, x_proj_w, dtw, dtb, A, Ds, dy, dx, dx_proj_w, ddtw, ddtb, dA, dDs, ws, st); \
+        else cs_launch<NN, RR, false>(w, xc, xdbl, x_proj_w, dtw, dtb, A, Ds, dy, dx, dx_proj_w, ddtw, ddtb, dA, dDs, ws, st);    \
+        break;
 #define FD_CS_N(NN)                                                                          \
     case NN:                                                                                 \
         switch (R) { FD_CS_R(NN, 2) FD_CS_R(NN, 4) FD_CS_R(NN, 8) FD_CS_R(NN, 16) FD_CS_R(NN, 32) } \
@@ -560,6 +584,53 @@ extern "C" int fd_cross_scan_bwd_f32(const float *xc, const float *xdbl, const f
     switch (N) { FD_CS_N(4) FD_CS_N(8) FD_CS_N(16) FD_CS_N(32) }
 #undef FD_CS_N
 #undef FD_CS_R
-    FD_LAUNCH_OK("fd_cross_scan_bwd_f32");
+    FD_LAUNCH_OK(name);
     return FD_OK;
+}
+
+}  // namespace
+
+extern "C" int fd_cross_scan_fwd_f32(const float *x, const float *x_proj_w, const float *dtw, const float *dtb, const float *A,
+                                     const float *Ds, float *xc, float *xdbl, float *y, float *ws, int B, int H, int W, int D,
+                                     int N, int R, void *stream) {
+    FD_REQUIRE(x && x_proj_w && dtw && dtb && A && Ds && xc && xdbl && y && ws, "fd_cross_scan_fwd_f32: null pointer");
+    FD_REQUIRE(cs_shape_ok(B, H, W, D, N, R),
+               "fd_cross_scan_fwd_f32: unsupported shape B=%d H=%d W=%d d_inner=%d d_state=%d dt_rank=%d (d_inner %% 64 == 0, "
+               "N in {4,8,16,32}, R in {2,4,8,16,32})", B, H, W, D, N, R);
+    FD_REQUIRE((((uintptr_t)x | (uintptr_t)xc | (uintptr_t)xdbl | (uintptr_t)y | (uintptr_t)x_proj_w) & 15) == 0,
+               "fd_cross_scan_fwd_f32: tensors must be 16-byte aligned");
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W;
+    hipLaunchKernelGGL(cs_nchw_nhwc_kernel, dim3((unsigned)((HW + 63) / 64), (unsigned)(D / 64), (unsigned)B), dim3(CS_T), 0,
+                       st, x, xc, D, HW);
+    FD_LAUNCH_OK("fd_cross_scan_fwd_f32 (layout)");
+    return cs_fwd_from_xc(xc, x_proj_w, dtw, dtb, A, Ds, xdbl, y, ws, B, H, W, D, N, R, stream);
+}
+
+extern "C" int fd_cross_scan_fwd_nhwc_f32(const float *xc, const float *x_proj_w, const float *dtw, const float *dtb,
+                                          const float *A, const float *Ds, float *xdbl, float *y, float *ws, int B, int H, int W,
+                                          int D, int N, int R, void *stream) {
+    FD_REQUIRE(xc && x_proj_w && dtw && dtb && A && Ds && xdbl && y && ws, "fd_cross_scan_fwd_nhwc_f32: null pointer");
+    FD_REQUIRE(cs_shape_ok(B, H, W, D, N, R),
+               "fd_cross_scan_fwd_nhwc_f32: unsupported shape B=%d H=%d W=%d d_inner=%d d_state=%d dt_rank=%d (d_inner %% 64 == 0, "
+               "N in {4,8,16,32}, R in {2,4,8,16,32})", B, H, W, D, N, R);
+    FD_REQUIRE((((uintptr_t)xc | (uintptr_t)xdbl | (uintptr_t)y | (uintptr_t)x_proj_w) & 15) == 0,
+               "fd_cross_scan_fwd_nhwc_f32: tensors must be 16-byte aligned");
+    return cs_fwd_from_xc(xc, x_proj_w, dtw, dtb, A, Ds, xdbl, y, ws, B, H, W, D, N, R, stream);
+}
+
+extern "C" int fd_cross_scan_bwd_f32(const float *xc, const float *xdbl, const float *x_proj_w, const float *dtw,
+                                     const float *dtb, const float *A, const float *Ds, const float *dy, float *dx, float *dx_proj_w,
+                                     float *ddtw, float *ddtb, float *dA, float *dDs, float *ws, int B, int H, int W, int D, int N,
+                                     int R, void *stream) {
+    return cs_bwd("fd_cross_scan_bwd_f32", 0, xc, xdbl, x_proj_w, dtw, dtb, A, Ds, dy, dx, dx_proj_w, ddtw, ddtb, dA, dDs, ws, B,
+                  H, W, D, N, R, stream);
+}
+
+extern "C" int fd_cross_scan_bwd_nhwc_f32(const float *xc, const float *xdbl, const float *x_proj_w, const float *dtw,
+                                          const float *dtb, const float *A, const float *Ds, const float *dy, float *dxc,
+                                          float *dx_proj_w, float *ddtw, float *ddtb, float *dA, float *dDs, float *ws, int B, int H,
+                                          int W, int D, int N, int R, void *stream) {
+    return cs_bwd("fd_cross_scan_bwd_nhwc_f32", 1, xc, xdbl, x_proj_w, dtw, dtb, A, Ds, dy, dxc, dx_proj_w, ddtw, ddtb, dA, dDs, ws,
+                  B, H, W, D, N, R, stream);
 }

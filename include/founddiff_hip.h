@@ -389,6 +389,48 @@ int fd_cross_scan_bwd_f32(const float *xc, const float *xdbl, const float *x_pro
                           float *ddtb, float *dA, float *dDs, float *ws, int B, int H, int W, int D, int N, int R,
                           void *stream);
 
+/* The same two with NHWC on both sides, for callers that already hold the activation channel-last (fd_ss2d_train.hip's
+ * neighbours): the forward takes xc [B,H,W,D] itself (no layout launch; xdbl, y and ws as above), the backward writes
+ * dxc [B,H,W,D] (16-byte aligned) in place of dx -- du leaves through the LDS slab that brought u in, 16 bytes per (pixel,
+ * 4 channels), and the x_proj term is added with lane = channel.  Everything else, the workspace included, as above.       */
+int fd_cross_scan_fwd_nhwc_f32(const float *xc, const float *x_proj_w, const float *dtw, const float *dtb, const float *A,
+                               const float *Ds, float *xdbl, float *y, float *ws, int B, int H, int W, int D, int N, int R,
+                               void *stream);
+int fd_cross_scan_bwd_nhwc_f32(const float *xc, const float *xdbl, const float *x_proj_w, const float *dtw, const float *dtb,
+                               const float *A, const float *Ds, const float *dy, float *dxc, float *dx_proj_w, float *ddtw,
+                               float *ddtb, float *dA, float *dDs, float *ws, int B, int H, int W, int D, int N, int R,
+                               void *stream);
+
+/* ---- The rest of SS2D.forward (src/emamba2.py:713-751) around the scan, for training, fp32, NHWC (fd_ss2d_train.hip).  The
+ * operands are the halves of in_proj's output xz [B,H,W,2D] and of its gradient, read and written in place through a pixel
+ * stride (ld) and a channel offset (off).  Deterministic (per-workgroup partials summed in a fixed order, no float atomics);
+ * tile sizes and the order of every per-slice sum depend on (H, W, C) only.  C % 64 == 0; pointers 16-byte aligned.
+ *
+ * fd_dwconv3x3_silu_bwd_f32: backward of xc = SiLU(dwconv3x3(x) + bias), fd_dwconv3x3(FD_F32, ..., silu = 1)'s forward.
+ *   x [B,H,W,ld_in] channels [off_in, +C); weight [9][C] tap-major and bias [C] or NULL as fd_dwconv3x3 takes them;
+ *   dout [B,H,W,C] dense, the gradient of xc: OVERWRITTEN with the gradient of the pre-activation (which is recomputed from
+ *   x, not stored by the forward); dx [B,H,W,ld_dx] channels [off_dx, +C), the other channels untouched; dweight [9][C];
+ *   dbias [C], NULL exactly when bias is.  Zero padding at the border as the forward.  ld / off multiples of 8.
+ *   ws: fd_dwconv3x3_silu_bwd_ws_floats(...) floats, 0 for an unsupported shape.
+ * fd_ln_silu_gate_fwd_f32: out = LN(y) * SiLU(z) + local[b]  (out_norm, * act(z), + local: src/emamba2.py:365, 720, 747-748).
+ *   fd_ln_gate with the activation of z inside.  y, out [B,hw,C] dense; z [B,hw,ldz] channels [offz, +C) (the z half of
+ *   xz, NOT activated); local [B][local_ld] or NULL; stats [B,hw,2] receives (mean, rstd) per pixel for the backward.
+ *   C <= 1024; ld / off multiples of 4.
+ * fd_ln_silu_gate_bwd_f32: dout [B,hw,C] -> dy [B,hw,C] dense, dz [B,hw,lddz] channels [offdz, +C) (the z half of dxz),
+ *   dgamma [C], dbeta [C], dlocal [B][C] (the sum of dout over the slice's pixels) or NULL.  Reads y, z and stats; nothing
+ *   else of the forward.  ws: fd_ln_silu_gate_bwd_ws_floats(...) floats, 0 for an unsupported shape.                       */
+int64_t fd_dwconv3x3_silu_bwd_ws_floats(int B, int H, int W, int C);
+int fd_dwconv3x3_silu_bwd_f32(const float *x, int ld_in, int off_in, const float *weight, const float *bias, float *dout,
+                              float *dx, int ld_dx, int off_dx, float *dweight, float *dbias, float *ws, int B, int H, int W,
+                              int C, void *stream);
+int fd_ln_silu_gate_fwd_f32(const float *y, const float *gamma, const float *beta, float eps, const float *z, int ldz, int offz,
+                            const float *local, int local_ld, float *out, float *stats, int B, int64_t hw, int C,
+                            void *stream);
+int64_t fd_ln_silu_gate_bwd_ws_floats(int B, int64_t hw, int C);
+int fd_ln_silu_gate_bwd_f32(const float *dout, const float *y, const float *stats, const float *gamma, const float *beta,
+                            const float *z, int ldz, int offz, float *dy, float *dz, int lddz, int offdz, float *dgamma,
+                            float *dbeta, float *dlocal, float *ws, int B, int64_t hw, int C, void *stream);
+
 /* ---- channel ("transposed") attention, src/DADiff.py:263-285 ------------------------------
  * fd_chan_attn_gram: per (b, head) partial 32x32 Gram q^T k and sums of squares over pixel
  *   blocks.  qkv [B,HW,3C] (dtype).  partial: fp32 [B][heads][nblk][32*32+64].
