@@ -110,6 +110,12 @@ SIGNATURES = {
     "fd_ln_silu_gate_fwd_f32": (i32, [vp, vp, vp, f32, vp, i32, i32, vp, i32, vp, vp, i32, i64, i32, vp]),
     "fd_ln_silu_gate_bwd_ws_floats": (i64, [i32, i64, i32]),
     "fd_ln_silu_gate_bwd_f32": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, i32, i64, i32, vp]),
+    "fd_chan_attn_fwd_ws_floats": (i64, [i32, i64, i32]),
+    "fd_chan_attn_fwd_f32": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp]),
+    "fd_chan_attn_bwd_ws_floats": (i64, [i32, i64, i32]),
+    "fd_chan_attn_bwd_f32": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i64, i32, vp]),
+    "fd_dwconv3x3_bwd_ws_floats": (i64, [i32, i32, i32, i32]),
+    "fd_dwconv3x3_bwd_f32": (i32, [vp, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "fd_chan_attn_nblk": (i32, [i64]),
     "fd_chan_attn_gram": (i32, [i32, vp, i32, i64, i32, vp, vp]),
     "fd_chan_attn_weff": (i32, [i32, vp, i32, vp, vp, vp, i32, i32, vp]),

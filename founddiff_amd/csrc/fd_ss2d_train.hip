@@ -2,6 +2,7 @@
 // fp32, NHWC, on the halves of in_proj's output xz [B,H,W,2D] in place:
 //
 //   fd_dwconv3x3_silu_bwd_f32   backward of xc = SiLU(dwconv3x3(x) + bias)     (the forward is fd_dwconv3x3 with silu = 1)
+//   fd_dwconv3x3_bwd_f32        the same without the activation (TransposedAttention's qkv_dwconv): dout is only read
 //   fd_ln_silu_gate_fwd_f32     out = LN(y) * SiLU(z) + local[b]               (out_norm, the gate, + local; 2 floats of
 //   fd_ln_silu_gate_bwd_f32     its backward                                     LayerNorm statistics kept per pixel)
 //
@@ -84,6 +85,8 @@ bool dwb_shape_ok(int B, int H, int W, int C) {
            (H + DB_TY - 1) / DB_TY < 65536;
 }
 
+// SILU = false: the linear conv (qkv_dwconv): dpre = dout, which is only read
+template <bool SILU>
 __global__ __launch_bounds__(256) void dwb_pre_kernel(const float *__restrict__ x, int ld_in, int off_in,
                                                      const float *__restrict__ w, const float *__restrict__ bias,
                                                      float *__restrict__ dout, float *__restrict__ part, int H, int W, int C,
@@ -139,12 +142,16 @@ __global__ __launch_bounds__(256) void dwb_pre_kernel(const float *__restrict__ 
             if (ok) {
                 float *gp = dout + ((img * H + yo) * W + xo) * C + c0;
                 const f32x4 g = *(const f32x4 *)gp;
+                if constexpr (SILU) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float s = sigmoid_f(pre[e]);
-                    d[e] = g[e] * (s * (1.0f + pre[e] * (1.0f - s)));
+                    for (int e = 0; e < 4; ++e) {
+                        const float s = sigmoid_f(pre[e]);
+                        d[e] = g[e] * (s * (1.0f + pre[e] * (1.0f - s)));
+                    }
+                    *(f32x4 *)gp = d;
+                } else {
+                    d = g;
                 }
-                *(f32x4 *)gp = d;
             }
             db += d;
 #pragma unroll
@@ -370,30 +377,48 @@ extern "C" int64_t fd_dwconv3x3_silu_bwd_ws_floats(int B, int H, int W, int C) {
     return dwb_plan(B, H, W, C).total;
 }
 
-extern "C" int fd_dwconv3x3_silu_bwd_f32(const float *x, int ld_in, int off_in, const float *weight, const float *bias, float *dout,
-                                         float *dx, int ld_dx, int off_dx, float *dweight, float *dbias, float *ws, int B, int H,
-                                         int W, int C, void *stream) {
-    FD_REQUIRE(x && weight && dout && dx && dweight && ws, "fd_dwconv3x3_silu_bwd_f32: null pointer");
-    FD_REQUIRE((bias == nullptr) == (dbias == nullptr), "fd_dwconv3x3_silu_bwd_f32: dbias must be NULL exactly when bias is");
-    FD_REQUIRE(dwb_shape_ok(B, H, W, C), "fd_dwconv3x3_silu_bwd_f32: unsupported shape B=%d H=%d W=%d C=%d (C %% 64 == 0)", B, H, W, C);
+// the two backwards of fd_dwconv3x3's fp32 form: name = the entry point, for its messages
+template <bool SILU>
+static int dwb_run(const char *name, const float *x, int ld_in, int off_in, const float *weight, const float *bias, float *dout,
+                   float *dx, int ld_dx, int off_dx, float *dweight, float *dbias, float *ws, int B, int H, int W, int C,
+                   void *stream) {
+    FD_REQUIRE(x && weight && dout && dx && dweight && ws, "%s: null pointer", name);
+    FD_REQUIRE((bias == nullptr) == (dbias == nullptr), "%s: dbias must be NULL exactly when bias is", name);
+    FD_REQUIRE(dwb_shape_ok(B, H, W, C), "%s: unsupported shape B=%d H=%d W=%d C=%d (C %% 64 == 0)", name, B, H, W, C);
     FD_REQUIRE(ld_in >= off_in + C && ld_dx >= off_dx + C && off_in >= 0 && off_dx >= 0 && ld_in % 8 == 0 && off_in % 8 == 0 &&
                    ld_dx % 8 == 0 && off_dx % 8 == 0,
-               "fd_dwconv3x3_silu_bwd_f32: strides / offsets must be multiples of 8 with off + C <= ld (ld_in=%d off_in=%d ld_dx=%d "
-               "off_dx=%d)", ld_in, off_in, ld_dx, off_dx);
-    FD_REQUIRE(al16(x) && al16(weight) && al16(bias) && al16(dout) && al16(dx) && al16(ws),
-               "fd_dwconv3x3_silu_bwd_f32: tensors must be 16-byte aligned");
+               "%s: strides / offsets must be multiples of 8 with off + C <= ld (ld_in=%d off_in=%d ld_dx=%d off_dx=%d)", name, ld_in,
+               off_in, ld_dx, off_dx);
+    FD_REQUIRE(al16(x) && al16(weight) && al16(bias) && al16(dout) && al16(dx) && al16(ws), "%s: tensors must be 16-byte aligned", name);
     const hipStream_t st = (hipStream_t)stream;
     const DwbPlan p = dwb_plan(B, H, W, C);
     float *part = ws, *stage = part + p.part, *wflip = stage + p.stage;
     hipLaunchKernelGGL(dwb_flip_kernel, dim3((unsigned)((9 * C + 255) / 256)), dim3(256), 0, st, weight, wflip, C);
-    hipLaunchKernelGGL(dwb_pre_kernel, dim3((unsigned)(p.ngx * p.cblocks), (unsigned)p.tiles_y, (unsigned)B), dim3(256), 0, st, x,
+    hipLaunchKernelGGL(dwb_pre_kernel<SILU>, dim3((unsigned)(p.ngx * p.cblocks), (unsigned)p.tiles_y, (unsigned)B), dim3(256), 0, st, x,
                        ld_in, off_in, weight, bias, dout, part, H, W, C, p.cblocks, p.tpb, p.ngx, p.tiles_x);
     launch_sum(part, 10 * (int64_t)C, 0, (int)p.M, 10 * C, DB_G, stage, 10 * (int64_t)C, 0, 1, st);
     launch_sum(stage, 10 * (int64_t)C, 0, (int)p.M1, 9 * C, (int)p.M1, dweight, 0, 0, 1, st);
     if (dbias) launch_sum(stage + 9 * (int64_t)C, 10 * (int64_t)C, 0, (int)p.M1, C, (int)p.M1, dbias, 0, 0, 1, st);
-    FD_LAUNCH_OK("fd_dwconv3x3_silu_bwd_f32");
+    FD_LAUNCH_OK(name);
     // dx = the mirrored taps over dpre
     return fd_dwconv3x3(FD_F32, dout, C, 0, wflip, nullptr, 0, dx, ld_dx, off_dx, B, H, W, C, stream);
+}
+
+extern "C" int fd_dwconv3x3_silu_bwd_f32(const float *x, int ld_in, int off_in, const float *weight, const float *bias, float *dout,
+                                         float *dx, int ld_dx, int off_dx, float *dweight, float *dbias, float *ws, int B, int H,
+                                         int W, int C, void *stream) {
+    return dwb_run<true>("fd_dwconv3x3_silu_bwd_f32", x, ld_in, off_in, weight, bias, dout, dx, ld_dx, off_dx, dweight, dbias, ws, B,
+                         H, W, C, stream);
+}
+
+extern "C" int64_t fd_dwconv3x3_bwd_ws_floats(int B, int H, int W, int C) { return fd_dwconv3x3_silu_bwd_ws_floats(B, H, W, C); }
+
+// (the kernel takes dout through the pointer type of the SiLU form and, with SILU = false, only reads it)
+extern "C" int fd_dwconv3x3_bwd_f32(const float *x, int ld_in, int off_in, const float *weight, const float *bias, const float *dout,
+                                    float *dx, int ld_dx, int off_dx, float *dweight, float *dbias, float *ws, int B, int H, int W,
+                                    int C, void *stream) {
+    return dwb_run<false>("fd_dwconv3x3_bwd_f32", x, ld_in, off_in, weight, bias, const_cast<float *>(dout), dx, ld_dx, off_dx, dweight,
+                          dbias, ws, B, H, W, C, stream);
 }
 
 #define FD_LSG_VPL(KERNEL, ...)                                                                      \

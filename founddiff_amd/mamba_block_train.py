@@ -1,0 +1,77 @@
+"""The reference's Mamba_block (src/DADiff.py:453-488) for training: both branches channel-last on HIP kernels.
+
+    x = x + gate_msa * SS2D(modulate(norm1(x), shift_msa, scale_msa), c)                  ss2d_train.ss2d_forward
+    x = x + gate_mlp * TransposedAttention(modulate(norm2(x), shift_mlp, scale_mlp))      tattn_train.transposed_attention_nhwc
+
+NCHW goes in as a permute view and comes out as a permute view, as in the reference; in between everything is (B, H, W, C).  The
+reference's two permute().contiguous() copies around its NCHW TransposedAttention do not exist here.  The two LayerNorms,
+modulate, the gates and the residual adds stay with torch.
+
+Binding for a training run:
+
+    import DADiff, founddiff_amd.mamba_block_train as mbt
+    DADiff.Mamba_block.forward = mbt.mamba_block_forward
+
+`MambaBlock(hidden_size, d_state, time_emb_dim, dropout=0.0)` is a module with the reference's parameter names and shapes (its
+state dict loads with strict=True) for code that does not import the reference.
+"""
+import torch
+
+from .ss2d_train import SS2D, ss2d_forward
+from .tattn_train import TransposedAttention, transposed_attention_nhwc
+
+__all__ = ["mamba_block_forward", "MambaBlock"]
+
+
+def _modulate(x, shift, scale):
+    return x * (1 + scale[:, None, None, :]) + shift[:, None, None, :]
+
+
+def mamba_block_forward(self, x, c, t):
+    """Mamba_block.forward (src/DADiff.py:477-488): x (B, C, H, W), c (B, 1, 256), t (B, time_emb_dim) -> (B, C, H, W), a permute
+    view of a channel-last tensor as in the reference.  Reads the reference's attribute names (norm1, mamba, norm2,
+    adaLN_modulation, attn_blk, cross).  Raises RuntimeError, before anything is launched, for cross=True (a CrossAttention
+    attn_blk), CPU tensors, inconsistent shapes and whatever ss2d_forward / transposed_attention_nhwc do not support (a
+    hidden_size that is not a multiple of 64 or is above 512 among them)."""
+    if getattr(self, "cross", False):
+        raise RuntimeError("mamba_block_forward: cross=True (a CrossAttention attn_blk) is not supported")
+    for name, v in (("x", x), ("c", c), ("t", t)):
+        if not isinstance(v, torch.Tensor):
+            raise RuntimeError(f"mamba_block_forward: {name} must be a tensor (got {type(v).__name__})")
+    C = self.norm1.normalized_shape[0]
+    if x.dim() != 4 or x.shape[1] != C or t.dim() != 2 or t.shape[0] != x.shape[0]:
+        raise RuntimeError(f"mamba_block_forward: inconsistent shapes x{tuple(x.shape)} t{tuple(t.shape)} (expected x (B, {C}, H, W), "
+                           "t (B, time_emb_dim))")
+    heads = getattr(self.attn_blk, "num_heads", None)
+    if heads is None or heads * 32 != C or C % 64 or C > 512:
+        raise RuntimeError(f"mamba_block_forward: unsupported hidden_size={C} with num_heads={heads} (hidden_size a multiple of 64, at "
+                           "most 512, heads of 32 channels)")
+    for name, v in (("x", x), ("c", c), ("t", t)):
+        if not v.is_cuda:
+            raise RuntimeError(f"mamba_block_forward: {name} must live on the GPU (there is no CPU path)")
+    x = x.permute(0, 2, 3, 1)
+    shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp = self.adaLN_modulation(t).chunk(6, dim=1)
+    x = x + gate_msa[:, None, None, :] * ss2d_forward(self.mamba, _modulate(self.norm1(x), shift_msa, scale_msa), c)
+    x = x + gate_mlp[:, None, None, :] * transposed_attention_nhwc(self.attn_blk, _modulate(self.norm2(x), shift_mlp, scale_mlp))
+    return x.permute(0, 3, 1, 2)
+
+
+class MambaBlock(torch.nn.Module):
+    """The reference's Mamba_block with cross=False: norm1 = LayerNorm(hidden_size), mamba = SS2D(hidden_size, d_state), norm2 =
+    LayerNorm(hidden_size, no affine, eps 1e-6), adaLN_modulation = SiLU + Linear(time_emb_dim, 6 hidden_size) initialised to
+    zero (adaLN-Zero: both branches start gated off), attn_blk = TransposedAttention(hidden_size, hidden_size // 32).  Parameter
+    names and shapes are the reference's."""
+
+    def __init__(self, hidden_size, d_state, time_emb_dim, dropout=0.0):
+        super().__init__()
+        nn = torch.nn
+        self.norm1 = nn.LayerNorm(hidden_size)
+        self.mamba = SS2D(hidden_size, d_state, dropout=dropout)
+        self.norm2 = nn.LayerNorm(hidden_size, elementwise_affine=False, eps=1e-6)
+        self.adaLN_modulation = nn.Sequential(nn.SiLU(), nn.Linear(time_emb_dim, 6 * hidden_size, bias=True))
+        self.cross = False
+        self.attn_blk = TransposedAttention(hidden_size, hidden_size // 32)
+        nn.init.constant_(self.adaLN_modulation[-1].weight, 0)
+        nn.init.constant_(self.adaLN_modulation[-1].bias, 0)
+
+    forward = mamba_block_forward

@@ -431,6 +431,35 @@ int fd_ln_silu_gate_bwd_f32(const float *dout, const float *y, const float *stat
                             const float *z, int ldz, int offz, float *dy, float *dz, int lddz, int offdz, float *dgamma,
                             float *dbeta, float *dlocal, float *ws, int B, int64_t hw, int C, void *stream);
 
+/* ---- The core of TransposedAttention.forward (src/DADiff.py:263-285) for training, fp32, NHWC (fd_tattn_train.hip, and
+ * fd_dwconv3x3_bwd_f32 in fd_ss2d_train.hip).  q, k, v are the three C-wide thirds of qkv [B,hw,ld] channels [off, +3C), read in
+ * place; heads are 32 channels wide (heads = C / 32); per (b, head), i and j run over the head's channels.  Deterministic (Gram
+ * partials per pixel block summed in a fixed order, no float atomics); the block size and the order of every per-slice sum
+ * depend on (hw, C) only.  C % 64 == 0, C <= 512; ld / off multiples of 4; pointers 16-byte aligned.
+ *
+ * fd_chan_attn_fwd_f32: G = q^T k over the pixels, nq / nk = max(column norm, 1e-12) (F.normalize), ghat = G / (nq nk^T),
+ *   attn = softmax_j(ghat * temperature[head]) with expf-accuracy exponentials, out[p,i] = sum_j attn[i][j] v[p,j].
+ *   temperature [heads]; out [B,hw,C] dense; attn, ghat [B][heads][32][32]; nrm [B][heads][64] (nq then nk): the three small
+ *   tensors are all the backward needs beyond qkv.  ws: fd_chan_attn_fwd_ws_floats(...) floats, 0 for an unsupported shape.
+ * fd_chan_attn_bwd_f32: dout [B,hw,C] dense -> dqkv [B,hw,ld_d] channels [off_d, +3C) (dq | dk | dv, the other channels
+ *   untouched) and dtemperature [heads] (summed over the batch in order).  Three launches over the activation: a Gram pass over
+ *   dout and v, a per-(b, head) kernel, one pass that reads q, k, dout and writes dqkv.
+ *   ws: fd_chan_attn_bwd_ws_floats(...) floats, 0 for an unsupported shape.
+ * fd_dwconv3x3_bwd_f32: backward of y = dwconv3x3(x) + bias, fd_dwconv3x3(FD_F32, ..., silu = 0)'s forward (qkv_dwconv):
+ *   fd_dwconv3x3_silu_bwd_f32 without the activation, same operands, but dout [B,H,W,C] is only read.  C % 64 == 0 (3 * 512 =
+ *   1536 included); ld / off multiples of 8.  ws: fd_dwconv3x3_bwd_ws_floats(...) floats, 0 for an unsupported shape.          */
+int64_t fd_chan_attn_fwd_ws_floats(int B, int64_t hw, int C);
+int fd_chan_attn_fwd_f32(const float *qkv, int ld, int off, const float *temperature, float *out, float *attn, float *ghat,
+                         float *nrm, float *ws, int B, int64_t hw, int C, void *stream);
+int64_t fd_chan_attn_bwd_ws_floats(int B, int64_t hw, int C);
+int fd_chan_attn_bwd_f32(const float *qkv, int ld, int off, const float *temperature, const float *attn, const float *ghat,
+                         const float *nrm, const float *dout, float *dqkv, int ld_d, int off_d, float *dtemperature, float *ws,
+                         int B, int64_t hw, int C, void *stream);
+int64_t fd_dwconv3x3_bwd_ws_floats(int B, int H, int W, int C);
+int fd_dwconv3x3_bwd_f32(const float *x, int ld_in, int off_in, const float *weight, const float *bias, const float *dout,
+                         float *dx, int ld_dx, int off_dx, float *dweight, float *dbias, float *ws, int B, int H, int W, int C,
+                         void *stream);
+
 /* ---- channel ("transposed") attention, src/DADiff.py:263-285 ------------------------------
  * fd_chan_attn_gram: per (b, head) partial 32x32 Gram q^T k and sums of squares over pixel
  *   blocks.  qkv [B,HW,3C] (dtype).  partial: fp32 [B][heads][nblk][32*32+64].
