@@ -460,6 +460,31 @@ int fd_dwconv3x3_bwd_f32(const float *x, int ld_in, int off_in, const float *wei
                          float *dx, int ld_dx, int off_dx, float *dweight, float *dbias, float *ws, int B, int H, int W, int C,
                          void *stream);
 
+/* ---- The backward of the reference's ResnetBlock (src/DADiff.py:139-154, 213-229, 397-430) for training, fp32, NHWC
+ * (fd_resblock_train.hip): out = SiLU(GroupNorm(h)) (+ res) with h = conv3x3(x, w) + bias.  The forward is fd_conv2d(FD_F32) with
+ * stats_partial, fd_gn_finalize and fd_gn_silu_apply; the gradient of res is dout itself; the gradient of x is fd_conv2d(FD_F32)
+ * over dh with the weight wd[c][kh][kw][n] = w[n][2-kh][2-kw][c].  Deterministic (per-workgroup partials summed in a fixed order,
+ * no float atomics); chunk and tile sizes, the split count and every order of summation depend on the shape only, and nothing in
+ * one slice's dh depends on the batch.  Pointers 16-byte aligned.
+ *
+ * fd_gn_silu_bwd_f32: dout [B,hw,C] (the gradient of out) and the raw convolution output h [B,hw,C], both only read; mean_rstd
+ *   [B][groups][2] as fd_gn_finalize leaves it; gamma, beta [C].  -> dh [B,hw,C] (the gradient of h), dgamma, dbeta [C] and
+ *   dbias [C] or NULL (the sum of dh over batch and pixels: the convolution's bias gradient).  The SiLU input is recomputed, not
+ *   stored.  C % 32 == 0, C <= 512, C % groups == 0, (C / groups) % 4 == 0.
+ *   ws: fd_gn_silu_bwd_ws_floats(...) floats, 0 for an unsupported shape.
+ * fd_conv3x3_wgrad_f32: dw[n][kh][kw][c] = sum over (b, y, x) of dh[b,y,x,n] x[b,y+kh-1,x+kw-1,c] with zero padding, in
+ *   fd_conv2d's weight layout [Cout][9 Cin], on the exact-f32 MFMA.  x [B,H,W,ld_x] channels [off_x, +Cin); dh [B,H,W,Cout]
+ *   dense; dw written, not accumulated.  The pixels are split over workgroups, whose partial results go to ws and are added in
+ *   order.  Cin % 16 == 0, Cin <= 1024; Cout % 32 == 0, Cout <= 512; ld_x / off_x multiples of 4.
+ *   ws: fd_conv3x3_wgrad_ws_floats(...) floats, 0 for an unsupported shape.                                                  */
+int64_t fd_gn_silu_bwd_ws_floats(int B, int64_t hw, int C, int groups);
+int fd_gn_silu_bwd_f32(const float *dout, const float *h, const float *mean_rstd, const float *gamma, const float *beta,
+                       float *dh, float *dgamma, float *dbeta, float *dbias, float *ws, int B, int64_t hw, int C, int groups,
+                       void *stream);
+int64_t fd_conv3x3_wgrad_ws_floats(int B, int H, int W, int Cin, int Cout);
+int fd_conv3x3_wgrad_f32(const float *x, int ld_x, int off_x, const float *dh, float *dw, float *ws, int B, int H, int W, int Cin,
+                         int Cout, void *stream);
+
 /* ---- channel ("transposed") attention, src/DADiff.py:263-285 ------------------------------
  * fd_chan_attn_gram: per (b, head) partial 32x32 Gram q^T k and sums of squares over pixel
  *   blocks.  qkv [B,HW,3C] (dtype).  partial: fp32 [B][heads][nblk][32*32+64].
