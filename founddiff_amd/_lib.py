@@ -120,6 +120,9 @@ SIGNATURES = {
     "fd_gn_silu_bwd_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, vp]),
     "fd_conv3x3_wgrad_ws_floats": (i64, [i32, i32, i32, i32, i32]),
     "fd_conv3x3_wgrad_f32": (i32, [vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "fd_conv_sub2x_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "fd_corr4x4s2_ws_floats": (i64, [i32, i32, i32, i32, i32]),
+    "fd_corr4x4s2_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "fd_chan_attn_nblk": (i32, [i64]),
     "fd_chan_attn_gram": (i32, [i32, vp, i32, i64, i32, vp, vp]),
     "fd_chan_attn_weff": (i32, [i32, vp, i32, vp, vp, vp, i32, i32, vp]),

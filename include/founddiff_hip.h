@@ -485,6 +485,31 @@ int64_t fd_conv3x3_wgrad_ws_floats(int B, int H, int W, int Cin, int Cout);
 int fd_conv3x3_wgrad_f32(const float *x, int ld_x, int off_x, const float *dh, float *dw, float *ws, int B, int H, int W, int Cin,
                          int Cout, void *stream);
 
+/* ---- The resampling convolutions of the U-Net (src/DADiff.py:128-136) for training, fp32, NHWC (fd_resample_train.hip).  Down =
+ * Conv2d(4, stride 2, pad 1), Up = nearest x2 -> Conv2d(3, pad 1); each is the other's transpose up to a fixed fold of the taps, so
+ * these two and fd_conv2d(FD_F32) cover the forward and every gradient of both (founddiff_amd/resample_train.py).  Exact-f32 MFMA,
+ * deterministic (no float atomics; tile sizes, the split count and every order of summation depend on the shape only).  Channel
+ * counts multiples of 32, at most 512; tensors dense, pointers 16-byte aligned; anything else fails with FD_ERR_ARG.
+ *
+ * fd_conv_sub2x_f32: in [B,H,W,Cin] -> out [B,2H,2W,Cout], w2 [Cout][4][2][2][Cin], bias [Cout] or NULL:
+ *     out[b, 2i+a, 2j+b', n] = bias[n] + sum_{r,s,c} w2[n][2a+b'][r][s][c] in[b, i+a+r-1, j+b'+s-1, c],  r, s in {0, 1},
+ *   zero outside `in`: output pixel (2i+a, 2j+b') reads source pixels (i+a+r-1, j+b'+s-1).  The Up forward takes the 3x3 taps that
+ *   land on one source pixel summed, the layout of fd_conv_params.weight_up2x (a = 0: r = 0 <- kh 0, r = 1 <- kh 1 + 2; a = 1:
+ *   r = 0 <- kh 0 + 1, r = 1 <- kh 2; columns likewise).  The input gradient of Down has the same index map with no summing:
+ *   dx[2i+a, 2j+b', c] = sum_{r,s,n} dout[i+a+r-1, j+b'+s-1, n] w[n, c, kh(a,r), kw(b',s)] with kh(0,0) = 3, kh(0,1) = 1,
+ *   kh(1,0) = 2, kh(1,1) = 0 and kw likewise, i.e. w2[c][2a+b'][r][s][n] = w[n][c][kh(a,r)][kw(b',s)].  One slice's result does not
+ *   depend on the batch.
+ * fd_corr4x4s2_f32: coarse [B,H,W,P], fine [B,2H,2W,Q] -> g [P][4][4][Q], written, not accumulated:
+ *     g[p][t][u][q] = sum_{b,i,j} coarse[b,i,j,p] fine[b, 2i+t-1, 2j+u-1, q],  zero outside `fine`.
+ *   Down's weight gradient is coarse = dout, fine = x: dweight[n][kh][kw][c] in fd_conv2d's weight layout.  Up's is coarse = x,
+ *   fine = dout, then dweight[n][c][kh][kw] = sum_{t in {2-kh, 3-kh}} sum_{u in {2-kw, 3-kw}} g[c][t][u][n].  The coarse pixels
+ *   are split over workgroups, whose partial results go to ws and are added in order; one split writes g directly.
+ *   ws: fd_corr4x4s2_ws_floats(...) floats, 0 for an unsupported shape.                                                      */
+int fd_conv_sub2x_f32(const float *in, const float *w2, const float *bias, float *out, int B, int H, int W, int Cin, int Cout,
+                      void *stream);
+int64_t fd_corr4x4s2_ws_floats(int B, int H, int W, int P, int Q);
+int fd_corr4x4s2_f32(const float *coarse, const float *fine, float *g, float *ws, int B, int H, int W, int P, int Q, void *stream);
+
 /* ---- channel ("transposed") attention, src/DADiff.py:263-285 ------------------------------
  * fd_chan_attn_gram: per (b, head) partial 32x32 Gram q^T k and sums of squares over pixel
  *   blocks.  qkv [B,HW,3C] (dtype).  partial: fp32 [B][heads][nblk][32*32+64].
