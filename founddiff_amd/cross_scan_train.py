@@ -16,11 +16,10 @@ Binding for a training run; forward_corev2 looks 
 `cross_scan_fn(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds)` is the autograd function underneath: y before
 out_norm as (B, H, W, d_inner) fp32, for code that does not import the reference.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib as L
+from ._train import HALF, cast_grads, check_devices, empty, f32, ptr, stream, workspace
 
 __all__ = ["cross_selective_scan", "cross_scan_fn"]
 
@@ -28,15 +27,10 @@ _N_OK, _R_OK = (4, 8, 16, 32), (2, 4, 8, 16, 32)
 
 
 def _f32(name, t):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError(f"cross_selective_scan: {name} must be a tensor (got {type(t).__name__})")
-    if t.dtype in (torch.float16, torch.bfloat16):
-        t = t.float()            # as selective_scan_train: the op runs in fp32
-    if t.dtype != torch.float32:
+    """a tensor _check (or autograd) let through, as the kernels take it: the op runs in fp32, as selective_scan_train"""
+    if t.dtype not in (torch.float32,) + HALF:
         raise RuntimeError(f"cross_selective_scan: {name} must be float32 / float16 / bfloat16 (got {t.dtype})")
-    if not t.is_cuda:
-        raise RuntimeError(f"cross_selective_scan: {name} must live on the GPU (there is no CPU path)")
-    return t.contiguous()
+    return f32(t).contiguous()
 
 
 def _check(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds):
@@ -64,14 +58,8 @@ def _check(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds):
     if D % 64 or N not in _N_OK or R not in _R_OK or B < 1 or H < 1 or W < 1:
         raise RuntimeError(f"cross_selective_scan: unsupported shape d_inner={D} (multiple of 64), d_state={N} (one of {_N_OK}), "
                            f"dt_rank={R} (one of {_R_OK}), image {H}x{W}, batch {B}")
-    for name, t in named[1:]:
-        if t.device != x.device:
-            raise RuntimeError(f"cross_selective_scan: {name} lives on {t.device}, x on {x.device}")
+    check_devices("cross_selective_scan", named)
     return B, D, H, W, N, R
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
 
 
 class _CrossScan(torch.autograd.Function):
@@ -87,14 +75,11 @@ class _CrossScan(torch.autograd.Function):
         L2 = ((H + 1) // 2) * ((W + 1) // 2)
         dev = x.device
         with torch.cuda.device(dev):
-            xc = torch.empty(B, H, W, D, device=dev, dtype=torch.float32)
-            xdbl = torch.empty(4, B, L2, R + 2 * N, device=dev, dtype=torch.float32)
-            y = torch.empty(B, H, W, D, device=dev, dtype=torch.float32)
-            nws = int(L.lib().fd_scan_ws_floats(B, H, W, D, N))
-            ws = torch.empty(max(nws, 4), device=dev, dtype=torch.float32)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            L.call("fd_cross_scan_fwd_f32", _p(x), _p(xw), _p(dtw), _p(dtb), _p(A), _p(Dv), _p(xc), _p(xdbl), _p(y), _p(ws),
-                   B, H, W, D, N, R, stream)
+            new = empty(dev)
+            xc, xdbl, y = new(B, H, W, D), new(4, B, L2, R + 2 * N), new(B, H, W, D)
+            ws = workspace("fd_scan_ws_floats", dev, B, H, W, D, N)
+            L.call("fd_cross_scan_fwd_f32", ptr(x), ptr(xw), ptr(dtw), ptr(dtb), ptr(A), ptr(Dv), ptr(xc), ptr(xdbl), ptr(y), ptr(ws),
+                   B, H, W, D, N, R, stream(dev))
         ctx.dims = (B, D, H, W, N, R)
         ctx.save_for_backward(xc, xdbl, xw, dtw, dtb, A, Dv)
         return y
@@ -111,14 +96,12 @@ class _CrossScan(torch.autograd.Function):
             dx = torch.empty(B, D, H, W, device=dev, dtype=torch.float32)
             dxw, ddtw, ddtb = torch.empty_like(xw), torch.empty_like(dtw), torch.empty(4 * D, device=dev, dtype=torch.float32)
             dA, dDs = torch.empty_like(A), torch.empty_like(Dv)
-            nws = int(L.lib().fd_cross_scan_bwd_ws_floats(B, H, W, D, N, R))
-            ws = torch.empty(max(nws, 4), device=dev, dtype=torch.float32)     # the caching allocator's blocks are 512-byte aligned
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            L.call("fd_cross_scan_bwd_f32", _p(xc), _p(xdbl), _p(xw), _p(dtw), _p(dtb), _p(A), _p(Dv), _p(dy), _p(dx), _p(dxw),
-                   _p(ddtw), _p(ddtb), _p(dA), _p(dDs), _p(ws), B, H, W, D, N, R, stream)
+            ws = workspace("fd_cross_scan_bwd_ws_floats", dev, B, H, W, D, N, R)
+            L.call("fd_cross_scan_bwd_f32", ptr(xc), ptr(xdbl), ptr(xw), ptr(dtw), ptr(dtb), ptr(A), ptr(Dv), ptr(dy), ptr(dx),
+                   ptr(dxw), ptr(ddtw), ptr(ddtb), ptr(dA), ptr(dDs), ptr(ws), B, H, W, D, N, R, stream(dev))
         dA_logs = dA * A                                     # A = -exp(A_logs): dA_logs = dA * dA/dA_logs = dA * A
         grads = (dx, dxw, ddtw, ddtb.view(ctx.bias_shape), dA_logs, dDs)
-        return tuple(g.to(dt) if g.dtype != dt else g for g, dt in zip(grads, ctx.dtypes))
+        return cast_grads(grads, ctx.dtypes)
 
 
 def cross_scan_fn(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds):

@@ -32,7 +32,7 @@
 // sides: the forward without the layout move, the backward with the kernels' NHWC template parameter set (a second instantiation: the NCHW one
 // is the code it was, register for register) -- launch 3 sends du back through the slab
 // buffer and stores it as the slab was loaded, launch 5 adds W^T dxdbl in its lane = channel loop.
-#include "fd_common.h"
+#include "fd_train_common.h"
 
 namespace {
 
@@ -464,8 +464,6 @@ __global__ __launch_bounds__(CS_T) void cs_nchw_nhwc_kernel(const float *__restr
         if (p0 + p < HW) out[((int64_t)b * HW + p0 + p) * D + c0 + tx] = t[tx][p];
 }
 
-int64_t cs_round4(int64_t n) { return (n + 3) & ~(int64_t)3; }
-
 struct CsLayout {
     CsGeom g;
     int64_t comp, part, dxd, dxp, wpart, total;   // floats: each composite array, parameter partials, dxdbl, its split partials,
@@ -484,11 +482,11 @@ CsLayout cs_layout(int B, int H, int W, int D, int N, int R) {
     while (4 * g.ntiles * g.S < 512 && D % (2 * g.S * 64) == 0) g.S *= 2;
     g.nxb = (g.L + XB * XBL - 1) / (XB * XBL);
     const int64_t rows = (int64_t)B * 4 * D;
-    w.comp = cs_round4((int64_t)g.ntiles * rows * N);
-    w.part = cs_round4((int64_t)B * g.ntiles * 4 * D * (N + R + 2));
-    w.dxd = cs_round4((int64_t)4 * B * g.L * g.CD);
-    w.dxp = g.S > 1 ? cs_round4((int64_t)g.S * 4 * B * g.L * g.CD) : 0;
-    w.wpart = cs_round4((int64_t)B * g.nxb * 4 * g.CD * D);
+    w.comp = round4((int64_t)g.ntiles * rows * N);
+    w.part = round4((int64_t)B * g.ntiles * 4 * D * (N + R + 2));
+    w.dxd = round4((int64_t)4 * B * g.L * g.CD);
+    w.dxp = g.S > 1 ? round4((int64_t)g.S * 4 * B * g.L * g.CD) : 0;
+    w.wpart = round4((int64_t)B * g.nxb * 4 * g.CD * D);
     w.total = 3 * w.comp + w.part + w.dxd + w.dxp + w.wpart;
     return w;
 }

@@ -27,25 +27,20 @@
 //                  per 256 MFMAs) and its A fragments one 16-byte global load of w2 (a row of 16 lanes reads 64 contiguous bytes;
 //                  w2 is small and stays in L2: 64 MACs per weight byte read).
 //      Traffic   : in x (Cout / 32) (+ 41 % halo) + out once + w2 once per pixel tile, from L2.
-// 2. fd_corr4x4s2_f32: a GEMM with M = P, N = 16 Q, K = B H W coarse pixels.  Both operands are K-major as stored, so the LDS
-//    images are [pixel][channel] and a fragment is one ds_read_b32 per lane, as in fd_conv3x3_wgrad_f32.
-//      workgroup = 4 waves, output tile 64 p x 16 taps x 32 q; wave w owns p in [16 w, +16): 32 accumulator tiles (128 VGPRs).
-//      K step    = a tile of 4 x 8 coarse pixels: coarse [32][64] (row stride 80 floats) and the (2*4+2) x (2*8+2) halo of fine
-//                  [180][32] (row stride 40 floats: the four coarse pixels of one MFMA K step are two fine pixels apart, 80 floats,
-//                  and fall into different banks) in LDS; the halo serves all 16 taps.  The next tile's global loads are issued
-//                  before the 8 x 32 MFMAs of the current one.
-//      split K   : the B tiles_y tiles_x pixel tiles are cut into S contiguous ranges, S = min(tiles, ceil(1024 / output tiles),
-//                  256, (coarse + fine elements) / (2 x 16 P Q)): the partials never take more than half of what the two
-//                  activations do (256 splits at down0, 3 of 8 MB each at ups0).  Split s writes its partial [P][16 Q] to the
-//                  workspace and a second launch adds the S partials in order.  S = 1 (one pixel tile) writes g directly.
+// 2. fd_corr4x4s2_f32: a GEMM with M = P, N = 16 Q, K = B H W coarse pixels: the tap correlation of fd_train_common.h, as
+//    fd_conv3x3_wgrad_f32, here tapcorr_kernel<KT = 4 taps per axis, STRIDE = 2, TY x TX = 4 x 8 coarse pixels per K step, LDB = 40
+//    floats per halo row in LDS> with f = fine read densely (ld = Q, off = 0).
+//      workgroup = 4 waves, output tile 64 p x 16 taps x 32 q; wave w owns p in [16 w, +16): 32 accumulator tiles (128 AGPRs).
+//      K step    = coarse [32][64] and the (2*4+2) x (2*8+2) halo of fine [180][32] in LDS (the four coarse pixels of one MFMA K
+//                  step are two fine pixels apart, 80 floats, and fall into different banks); the halo serves all 16 taps.  The
+//                  next tile's global loads are issued before the 8 x 32 MFMAs of the current one.
+//      split K   : S = min(tiles, ceil(1024 / output tiles), 256, (coarse + fine elements) / (2 x 16 P Q)) contiguous ranges of
+//                  the pixel tiles: the partials never take more than half of what the two activations do (256 splits at down0, 3
+//                  of 8 MB each at ups0); tapcorr_reduce_kernel adds them in order.  S = 1 (one pixel tile) writes g directly.
 //      Traffic   : coarse x (Q / 32) + fine x ceil(P / 64) (+ 41 % halo) + 2 S partials.
-#include "fd_common.h"
+#include "fd_train_common.h"
 
 namespace {
-
-bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-int64_t round4(int64_t n) { return (n + 3) & ~(int64_t)3; }
 
 bool chan_ok(int c) { return c > 0 && c % 32 == 0 && c <= 512; }
 
@@ -149,146 +144,18 @@ __global__ __launch_bounds__(256) void sub2x_kernel(const float *__restrict__ in
 }
 
 // ---- 2. the 4x4 / stride 2 correlation -----------------------------------------------------------------------------------------
-constexpr int CR_TY = 4, CR_TX = 8, CR_PIX = CR_TY * CR_TX, CR_HX = 2 * CR_TX + 2, CR_HY = 2 * CR_TY + 2, CR_HPIX = CR_HX * CR_HY;
-constexpr int CR_PB = 64, CR_QB = 32, CR_LDA = 80, CR_LDB = 40;
-constexpr int CR_AV = CR_PIX * (CR_PB / 4) / 256;                        // 16-byte vectors of coarse per thread and tile: 2
-constexpr int CR_BV = (CR_HPIX * (CR_QB / 4) + 255) / 256;               // of the halo of fine: 6 (the last one partly)
-
-struct CrPlan {
-    int tiles_x, tiles_y, pblk, qblk, tps, S;
-    int64_t ntiles, out;
-};
+constexpr int CR_TY = 4, CR_TX = 8;
+constexpr auto cr_launch = tapcorr_launch<4, 2, CR_TY, CR_TX, 40>;
 
 bool cr_shape_ok(int B, int H, int W, int P, int Q) {
     return B > 0 && H > 0 && W > 0 && H < (1 << 29) && W < (1 << 29) && chan_ok(P) && chan_ok(Q) &&
            (int64_t)B * ((H + CR_TY - 1) / CR_TY) * ((W + CR_TX - 1) / CR_TX) < (1ll << 31);
 }
 
-CrPlan cr_plan(int B, int H, int W, int P, int Q) {
-    CrPlan p;
-    p.tiles_x = (W + CR_TX - 1) / CR_TX;
-    p.tiles_y = (H + CR_TY - 1) / CR_TY;
-    p.ntiles = (int64_t)B * p.tiles_y * p.tiles_x;
-    p.pblk = (P + CR_PB - 1) / CR_PB;
-    p.qblk = Q / CR_QB;
-    p.out = (int64_t)P * 16 * Q;
-    int64_t want = (1024 + p.pblk * p.qblk - 1) / (p.pblk * p.qblk);
-    if (want > 256) want = 256;
-    const int64_t cap = (int64_t)B * H * W * (P + 4 * (int64_t)Q) / (2 * p.out);      // partials <= half the two activations
-    if (want > cap) want = cap;
-    if (want < 1) want = 1;
-    if (want > p.ntiles) want = p.ntiles;
-    p.tps = (int)((p.ntiles + want - 1) / want);
-    p.S = (int)((p.ntiles + p.tps - 1) / p.tps);
-    return p;
-}
-
-// grid (split, p block x q block); out = the workspace [S][P][16 Q], or g itself when S = 1
-__global__ __launch_bounds__(256) void corr_kernel(const float *__restrict__ coarse, const float *__restrict__ fine,
-                                                  float *__restrict__ out, int H, int W, int P, int Q, int tiles_x, int tiles_y,
-                                                  int64_t ntiles, int tps, int qblk) {
-    __shared__ __attribute__((aligned(16))) float sA[CR_PIX * CR_LDA];
-    __shared__ __attribute__((aligned(16))) float sB[CR_HPIX * CR_LDB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int g = lane >> 4, r = lane & 15;
-    const int pb = blockIdx.y / qblk, qb = blockIdx.y - pb * qblk;
-    const int p_base = pb * CR_PB, q_base = qb * CR_QB;
-    const bool wave_on = p_base + 16 * wave < P;
-    const int64_t t0 = (int64_t)blockIdx.x * tps;
-    const int64_t t1 = min(ntiles, t0 + tps);
-    const int64_t FH = 2 * (int64_t)H, FW = 2 * (int64_t)W;
-    f32x4 acc[16][2];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) acc[t][0] = acc[t][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 ra[CR_AV], rb[CR_BV];
-    auto gload = [&](int64_t t) {
-        const int tx = (int)(t % tiles_x);
-        const int64_t tq = t / tiles_x;
-        const int ty = (int)(tq % tiles_y);
-        const int64_t b = tq / tiles_y;
-        const int y0 = ty * CR_TY, x0 = tx * CR_TX;
-#pragma unroll
-        for (int i = 0; i < CR_AV; ++i) {
-            const int idx = tid + 256 * i;
-            const int v = idx & 15, px = idx >> 4;
-            const int yy = y0 + (px >> 3), xx = x0 + (px & 7), pc = p_base + 4 * v;
-            f32x4 val = {0.f, 0.f, 0.f, 0.f};
-            if (yy < H && xx < W && pc < P) val = *(const f32x4 *)(coarse + ((b * H + yy) * W + xx) * P + pc);
-            ra[i] = val;
-        }
-#pragma unroll
-        for (int i = 0; i < CR_BV; ++i) {
-            const int idx = tid + 256 * i;
-            const int v = idx & 7, px = idx >> 3;
-            const int hy = px / CR_HX, hx = px - hy * CR_HX;
-            const int64_t yy = 2 * (int64_t)y0 + hy - 1, xx = 2 * (int64_t)x0 + hx - 1;
-            f32x4 val = {0.f, 0.f, 0.f, 0.f};
-            if (px < CR_HPIX && yy >= 0 && yy < FH && xx >= 0 && xx < FW)
-                val = *(const f32x4 *)(fine + ((b * FH + yy) * FW + xx) * Q + q_base + 4 * v);
-            rb[i] = val;
-        }
-    };
-    auto lstore = [&]() {
-#pragma unroll
-        for (int i = 0; i < CR_AV; ++i) {
-            const int idx = tid + 256 * i;
-            *(f32x4 *)(sA + (idx >> 4) * CR_LDA + 4 * (idx & 15)) = ra[i];
-        }
-#pragma unroll
-        for (int i = 0; i < CR_BV; ++i) {
-            const int idx = tid + 256 * i;
-            if ((idx >> 3) < CR_HPIX) *(f32x4 *)(sB + (idx >> 3) * CR_LDB + 4 * (idx & 7)) = rb[i];
-        }
-    };
-    if (t0 < t1) gload(t0);
-    for (int64_t t = t0; t < t1; ++t) {
-        __syncthreads();                       // the previous tile's fragment reads are done
-        lstore();
-        __syncthreads();
-        if (t + 1 < t1) gload(t + 1);
-        if (wave_on) {
-            // lane (g, r): A[p = 16 wave + r][k = k0 + g], B[k = k0 + g][q = 16 j + r]; coarse pixel k = (k >> 3, k & 7) of the tile,
-            // whose tap (t, u) is pixel (2 (k >> 3) + t, 2 (k & 7) + u) of the halo
-            const float *ap = sA + g * CR_LDA + 16 * wave + r;
-            const float *bp = sB + 2 * g * CR_LDB + r;
-#pragma unroll 2
-            for (int k0 = 0; k0 < CR_PIX; k0 += 4) {
-                const float a = ap[k0 * CR_LDA];
-                const float *bq = bp + (2 * (k0 >> 3) * CR_HX + 2 * (k0 & 7)) * CR_LDB;
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const float *bt = bq + (tt * CR_HX + u) * CR_LDB;
-                        acc[tt * 4 + u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bt[0], acc[tt * 4 + u][0], 0, 0, 0);
-                        acc[tt * 4 + u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bt[16], acc[tt * 4 + u][1], 0, 0, 0);
-                    }
-            }
-        }
-    }
-    if (!wave_on) return;
-    // D: lane (g, r) holds rows p = 4 g + i, column q = r of each 16 x 16 tile
-    float *op = out + (int64_t)blockIdx.x * P * 16 * Q;
-#pragma unroll
-    for (int t = 0; t < 16; ++t)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int q = q_base + 16 * j + r;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int p = p_base + 16 * wave + 4 * g + i;
-                op[((int64_t)p * 16 + t) * Q + q] = acc[t][j][i];
-            }
-        }
-}
-
-// g[i] = the S partials in order
-__global__ __launch_bounds__(256) void corr_reduce_kernel(const float *__restrict__ ws, int S, int64_t n, float *__restrict__ g) {
-    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i >= n) return;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < S; ++s) v += *(const f32x4 *)(ws + (int64_t)s * n + i);
-    *(f32x4 *)(g + i) = v;
+TapPlan cr_plan(int B, int H, int W, int P, int Q) {
+    // partials <= half the two activations
+    const int64_t cap = (int64_t)B * H * W * (P + 4 * (int64_t)Q) / (2 * (int64_t)P * 16 * Q);
+    return tap_plan(4, CR_TY, CR_TX, B, H, W, P, Q, cap);
 }
 
 }  // namespace
@@ -309,8 +176,7 @@ extern "C" int fd_conv_sub2x_f32(const float *in, const float *w2, const float *
 
 extern "C" int64_t fd_corr4x4s2_ws_floats(int B, int H, int W, int P, int Q) {
     if (!cr_shape_ok(B, H, W, P, Q)) return 0;
-    const CrPlan p = cr_plan(B, H, W, P, Q);
-    return p.S > 1 ? round4((int64_t)p.S * p.out) : 4;
+    return tap_ws_floats(cr_plan(B, H, W, P, Q));
 }
 
 extern "C" int fd_corr4x4s2_f32(const float *coarse, const float *fine, float *g, float *ws, int B, int H, int W, int P, int Q,
@@ -319,12 +185,7 @@ extern "C" int fd_corr4x4s2_f32(const float *coarse, const float *fine, float *g
     FD_REQUIRE(cr_shape_ok(B, H, W, P, Q),
                "fd_corr4x4s2_f32: unsupported shape B=%d H=%d W=%d P=%d Q=%d (P, Q %% 32 == 0, at most 512)", B, H, W, P, Q);
     FD_REQUIRE(al16(coarse) && al16(fine) && al16(g) && al16(ws), "fd_corr4x4s2_f32: tensors must be 16-byte aligned");
-    const hipStream_t st = (hipStream_t)stream;
-    const CrPlan p = cr_plan(B, H, W, P, Q);
-    hipLaunchKernelGGL(corr_kernel, dim3((unsigned)p.S, (unsigned)(p.pblk * p.qblk)), dim3(256), 0, st, coarse, fine,
-                       p.S > 1 ? ws : g, H, W, P, Q, p.tiles_x, p.tiles_y, p.ntiles, p.tps, p.qblk);
-    if (p.S > 1)
-        hipLaunchKernelGGL(corr_reduce_kernel, dim3((unsigned)((p.out / 4 + 255) / 256)), dim3(256), 0, st, ws, p.S, p.out, g);
+    cr_launch(cr_plan(B, H, W, P, Q), coarse, fine, Q, 0, g, ws, H, W, P, Q, (hipStream_t)stream);
     FD_LAUNCH_OK("fd_corr4x4s2_f32");
     return FD_OK;
 }

@@ -15,46 +15,22 @@
 //      dh = rstd_g (gamma_c dz - S1 - hn S2),  dbias_c = sum_{b,p} dh.
 //    Two streaming passes over (dout, h), lane = 4 consecutive channels, 16-byte accesses; z is recomputed in both.
 //      pass 1: per (b, chunk of pixels) the channel sums of dz, dz hn and hn -> one partial row [3][C] per workgroup, summed by two
-//              launches of a fixed-order kernel; S1 and S2 from the channel sums in double; dgamma, dbeta over the batch in order;
+//              launches of partial_sum_kernel; S1 and S2 from the channel sums in double; dgamma, dbeta over the batch in order;
 //              dbias in closed form, sum_b rstd (gamma A1 - hw S1 - S2 A3) with A1 = sum_p dz, A3 = sum_p hn, in double.
 //      pass 2: dh.
 //    Traffic: 2 A + (2 A + A) = 5 A for an activation of A bytes (algorithmic: 3 A).
 // 2. 3x3 weight gradient: dw[n][kh][kw][c] = sum_{b,y,x} dh[b,y,x,n] x[b,y+kh-1,x+kw-1,c], a GEMM with M = Cout, N = 9 Cin,
-//    K = B H W on v_mfma_f32_16x16x4_f32 (exact fp32: an fmaf chain).  Both operands are K-major as stored (a pixel's channels are
-//    contiguous), so the LDS images are [pixel][channel] and a fragment is one ds_read_b32 per lane.
-//      workgroup = 4 waves, output tile 64 n x 9 taps x 32 c; wave w owns n in [16 w, +16): 18 accumulator tiles (72 VGPRs).
-//      K step   = a tile of 8 x 16 pixels: dh [128][64] and the (8+2) x (16+2) halo of x [180][32] in LDS (row strides 80 and 48
-//                 floats: the four pixels of one MFMA K step fall into different banks); the halo serves all nine taps.  The next
-//                 tile's global loads are issued before the 32 x 18 MFMAs of the current one.
-//      split K  : the B tiles_y tiles_x pixel tiles are cut into S contiguous ranges, S = min(tiles, ceil(1024 / output tiles),
-//                 256); split s writes its partial [Cout][9 Cin] to the workspace and a second launch adds the S partials in
-//                 order: 256 splits at down0 (2 output tiles, 4 096 pixel tiles), 6 at ups0 (192 output tiles, 64 pixel tiles).
-//                 S = 1 (one pixel tile) writes dweight directly.
-#include "fd_common.h"
+//    K = B H W: the tap correlation of fd_train_common.h with a = dh and f = x, tapcorr_kernel<KT = 3 taps per axis, STRIDE = 1,
+//    TY x TX = 8 x 16 pixels per K step, LDB = 48 floats per halo row in LDS>.
+//      workgroup = 4 waves, output tile 64 n x 9 taps x 32 c; wave w owns n in [16 w, +16): 18 accumulator tiles (72 AGPRs).
+//      K step   = dh [128][64] and the (8+2) x (16+2) halo of x [180][32] in LDS; the halo serves all nine taps.  The next tile's
+//                 global loads are issued before the 32 x 18 MFMAs of the current one.
+//      split K  : S = min(tiles, ceil(1024 / output tiles), 256) contiguous ranges of the B tiles_y tiles_x pixel tiles, added in
+//                 order by tapcorr_reduce_kernel: 256 splits at down0 (2 output tiles, 4 096 pixel tiles), 6 at ups0 (192 output
+//                 tiles, 64 pixel tiles).  S = 1 (one pixel tile) writes dweight directly.
+#include "fd_train_common.h"
 
 namespace {
-
-constexpr float LOG2E = 1.4426950408889634f;
-
-__device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-LOG2E * x)); }
-
-int64_t round4(int64_t n) { return (n + 3) & ~(int64_t)3; }
-
-bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-// out[b][j][q] = sum of p[b][m][q] over m in [j G, min((j + 1) G, M)) in order; rows Q floats apart
-__global__ __launch_bounds__(256) void rb_sum_kernel(const float *__restrict__ p, int M, int Q, int G, float *__restrict__ out,
-                                                    int Mo) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= Q) return;
-    const int j = blockIdx.y;
-    const int64_t b = blockIdx.z;
-    const int m1 = min(M, (j + 1) * G);
-    const float *pp = p + b * M * Q + q;
-    float v = 0.f;
-    for (int m = j * G; m < m1; ++m) v += pp[(int64_t)m * Q];
-    out[(b * Mo + j) * Q + q] = v;
-}
 
 // ---- 1. GroupNorm + SiLU backward ----------------------------------------------------------------------------------------------
 constexpr int GSB_G = 16;
@@ -198,143 +174,15 @@ __global__ __launch_bounds__(256) void gsb_dh_kernel(const float *__restrict__ d
 }
 
 // ---- 2. 3x3 weight gradient --------------------------------------------------------------------------------------------------
-constexpr int WG_TY = 8, WG_TX = 16, WG_PIX = WG_TY * WG_TX, WG_HX = WG_TX + 2, WG_HY = WG_TY + 2, WG_HPIX = WG_HX * WG_HY;
-constexpr int WG_NB = 64, WG_CB = 32, WG_LDA = 80, WG_LDB = 48;
-constexpr int WG_AV = WG_PIX * (WG_NB / 4) / 256;                        // 16-byte vectors of dh per thread and tile: 8
-constexpr int WG_BV = (WG_HPIX * (WG_CB / 4) + 255) / 256;               // of the halo of x: 6 (the last one partly)
-
-struct WgPlan {
-    int tiles_x, tiles_y, nblk, cblk, tps, S;
-    int64_t ntiles, out;
-};
+constexpr int WG_TY = 8, WG_TX = 16;
+constexpr auto wg_launch = tapcorr_launch<3, 1, WG_TY, WG_TX, 48>;
 
 bool wg_shape_ok(int B, int H, int W, int Cin, int Cout) {
     return B > 0 && H > 0 && W > 0 && Cin > 0 && Cin % 16 == 0 && Cin <= 1024 && Cout > 0 && Cout % 32 == 0 && Cout <= 512 &&
            (int64_t)B * ((H + WG_TY - 1) / WG_TY) * ((W + WG_TX - 1) / WG_TX) < (1ll << 31);
 }
 
-WgPlan wg_plan(int B, int H, int W, int Cin, int Cout) {
-    WgPlan p;
-    p.tiles_x = (W + WG_TX - 1) / WG_TX;
-    p.tiles_y = (H + WG_TY - 1) / WG_TY;
-    p.ntiles = (int64_t)B * p.tiles_y * p.tiles_x;
-    p.nblk = (Cout + WG_NB - 1) / WG_NB;
-    p.cblk = (Cin + WG_CB - 1) / WG_CB;
-    int64_t want = (1024 + p.nblk * p.cblk - 1) / (p.nblk * p.cblk);
-    if (want > 256) want = 256;
-    if (want > p.ntiles) want = p.ntiles;
-    p.tps = (int)((p.ntiles + want - 1) / want);
-    p.S = (int)((p.ntiles + p.tps - 1) / p.tps);
-    p.out = (int64_t)Cout * 9 * Cin;
-    return p;
-}
-
-// grid (split, n block x c block); out = the workspace [S][Cout][9 Cin], or dweight itself when S = 1
-__global__ __launch_bounds__(256) void wgrad_kernel(const float *__restrict__ x, int ld_x, int off_x, const float *__restrict__ dh,
-                                                   float *__restrict__ out, int H, int W, int Cin, int Cout, int tiles_x,
-                                                   int tiles_y, int64_t ntiles, int tps, int cblk) {
-    __shared__ __attribute__((aligned(16))) float sA[WG_PIX * WG_LDA];
-    __shared__ __attribute__((aligned(16))) float sB[WG_HPIX * WG_LDB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int g = lane >> 4, r = lane & 15;
-    const int nb = blockIdx.y / cblk, cb = blockIdx.y - nb * cblk;
-    const int n_base = nb * WG_NB, c_base = cb * WG_CB;
-    const bool wave_on = n_base + 16 * wave < Cout;
-    const int64_t t0 = (int64_t)blockIdx.x * tps;
-    const int64_t t1 = min(ntiles, t0 + tps);
-    f32x4 acc[9][2];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) acc[t][0] = acc[t][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 ra[WG_AV], rb[WG_BV];
-    auto gload = [&](int64_t t) {
-        const int tx = (int)(t % tiles_x);
-        const int64_t q = t / tiles_x;
-        const int ty = (int)(q % tiles_y);
-        const int64_t b = q / tiles_y;
-        const int y0 = ty * WG_TY, x0 = tx * WG_TX;
-#pragma unroll
-        for (int i = 0; i < WG_AV; ++i) {
-            const int idx = tid + 256 * i;
-            const int v = idx & 15, p = idx >> 4;
-            const int yy = y0 + (p >> 4), xx = x0 + (p & 15), n = n_base + 4 * v;
-            f32x4 val = {0.f, 0.f, 0.f, 0.f};
-            if (yy < H && xx < W && n < Cout) val = *(const f32x4 *)(dh + ((b * H + yy) * W + xx) * Cout + n);
-            ra[i] = val;
-        }
-#pragma unroll
-        for (int i = 0; i < WG_BV; ++i) {
-            const int idx = tid + 256 * i;
-            const int v = idx & 7, p = idx >> 3;
-            const int hy = p / WG_HX, hx = p - hy * WG_HX;
-            const int yy = y0 + hy - 1, xx = x0 + hx - 1, c = c_base + 4 * v;
-            f32x4 val = {0.f, 0.f, 0.f, 0.f};
-            if (p < WG_HPIX && yy >= 0 && yy < H && xx >= 0 && xx < W && c < Cin)
-                val = *(const f32x4 *)(x + ((b * H + yy) * W + xx) * ld_x + off_x + c);
-            rb[i] = val;
-        }
-    };
-    auto lstore = [&]() {
-#pragma unroll
-        for (int i = 0; i < WG_AV; ++i) {
-            const int idx = tid + 256 * i;
-            *(f32x4 *)(sA + (idx >> 4) * WG_LDA + 4 * (idx & 15)) = ra[i];
-        }
-#pragma unroll
-        for (int i = 0; i < WG_BV; ++i) {
-            const int idx = tid + 256 * i;
-            if ((idx >> 3) < WG_HPIX) *(f32x4 *)(sB + (idx >> 3) * WG_LDB + 4 * (idx & 7)) = rb[i];
-        }
-    };
-    if (t0 < t1) gload(t0);
-    for (int64_t t = t0; t < t1; ++t) {
-        __syncthreads();                       // the previous tile's fragment reads are done
-        lstore();
-        __syncthreads();
-        if (t + 1 < t1) gload(t + 1);
-        if (wave_on) {
-            // lane (g, r): A[n = 16 wave + r][k = k0 + g], B[k = k0 + g][c = 16 j + r]; pixel k = (k >> 4, k & 15) of the tile
-            const float *ap = sA + g * WG_LDA + 16 * wave + r;
-            const float *bp = sB + g * WG_LDB + r;
-#pragma unroll 2
-            for (int k0 = 0; k0 < WG_PIX; k0 += 4) {
-                const float a = ap[k0 * WG_LDA];
-                const float *bq = bp + ((k0 >> 4) * WG_HX + (k0 & 15)) * WG_LDB;
-#pragma unroll
-                for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-                    for (int kw = 0; kw < 3; ++kw) {
-                        const float *bt = bq + (kh * WG_HX + kw) * WG_LDB;
-                        acc[kh * 3 + kw][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bt[0], acc[kh * 3 + kw][0], 0, 0, 0);
-                        acc[kh * 3 + kw][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bt[16], acc[kh * 3 + kw][1], 0, 0, 0);
-                    }
-            }
-        }
-    }
-    if (!wave_on) return;
-    // D: lane (g, r) holds rows n = 4 g + i, column c = r of each 16 x 16 tile
-    float *op = out + (int64_t)blockIdx.x * Cout * 9 * Cin;
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int c = c_base + 16 * j + r;
-            if (c >= Cin) continue;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int n = n_base + 16 * wave + 4 * g + i;
-                op[((int64_t)n * 9 + t) * Cin + c] = acc[t][j][i];
-            }
-        }
-}
-
-// dw[i] = the S partials in order
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restrict__ ws, int S, int64_t n, float *__restrict__ dw) {
-    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i >= n) return;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < S; ++s) v += *(const f32x4 *)(ws + (int64_t)s * n + i);
-    *(f32x4 *)(dw + i) = v;
-}
+TapPlan wg_plan(int B, int H, int W, int Cin, int Cout) { return tap_plan(3, WG_TY, WG_TX, B, H, W, Cout, Cin); }
 
 }  // namespace
 
@@ -358,9 +206,8 @@ extern "C" int fd_gn_silu_bwd_f32(const float *dout, const float *h, const float
     const int Q = 3 * C;
     hipLaunchKernelGGL(gsb_sums_kernel, dim3((unsigned)p.nchunk, (unsigned)B), dim3((unsigned)p.nthr), 0, st, dout, h, mean_rstd, gamma,
                        beta, part, hw, C, groups, p.lpr, p.rpb, p.ch);
-    hipLaunchKernelGGL(rb_sum_kernel, dim3((unsigned)((Q + 255) / 256), (unsigned)p.M1, (unsigned)B), dim3(256), 0, st, part, p.nchunk, Q,
-                       GSB_G, stage, p.M1);
-    hipLaunchKernelGGL(rb_sum_kernel, dim3((unsigned)((Q + 255) / 256), 1, (unsigned)B), dim3(256), 0, st, stage, p.M1, Q, p.M1, fin, 1);
+    launch_sum(part, Q, (int64_t)p.nchunk * Q, p.nchunk, Q, GSB_G, stage, Q, (int64_t)p.M1 * Q, B, st);
+    launch_sum(stage, Q, (int64_t)p.M1 * Q, p.M1, Q, p.M1, fin, Q, Q, B, st);
     hipLaunchKernelGGL(gsb_coef_kernel, dim3((unsigned)((B * groups + 255) / 256)), dim3(256), 0, st, fin, gamma, B, C, groups,
                        1.0 / ((double)hw * (C / groups)), coef);
     hipLaunchKernelGGL(gsb_param_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, fin, coef, mean_rstd, gamma, B, C, groups,
@@ -373,8 +220,7 @@ extern "C" int fd_gn_silu_bwd_f32(const float *dout, const float *h, const float
 
 extern "C" int64_t fd_conv3x3_wgrad_ws_floats(int B, int H, int W, int Cin, int Cout) {
     if (!wg_shape_ok(B, H, W, Cin, Cout)) return 0;
-    const WgPlan p = wg_plan(B, H, W, Cin, Cout);
-    return p.S > 1 ? round4((int64_t)p.S * p.out) : 4;
+    return tap_ws_floats(wg_plan(B, H, W, Cin, Cout));
 }
 
 extern "C" int fd_conv3x3_wgrad_f32(const float *x, int ld_x, int off_x, const float *dh, float *dw, float *ws, int B, int H, int W,
@@ -386,12 +232,7 @@ extern "C" int fd_conv3x3_wgrad_f32(const float *x, int ld_x, int off_x, const f
     FD_REQUIRE(off_x >= 0 && ld_x >= off_x + Cin && ld_x % 4 == 0 && off_x % 4 == 0,
                "fd_conv3x3_wgrad_f32: stride / offset must be multiples of 4 with off + Cin <= ld (ld_x=%d off_x=%d)", ld_x, off_x);
     FD_REQUIRE(al16(x) && al16(dh) && al16(dw) && al16(ws), "fd_conv3x3_wgrad_f32: tensors must be 16-byte aligned");
-    const hipStream_t st = (hipStream_t)stream;
-    const WgPlan p = wg_plan(B, H, W, Cin, Cout);
-    hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)p.S, (unsigned)(p.nblk * p.cblk)), dim3(256), 0, st, x, ld_x, off_x, dh,
-                       p.S > 1 ? ws : dw, H, W, Cin, Cout, p.tiles_x, p.tiles_y, p.ntiles, p.tps, p.cblk);
-    if (p.S > 1)
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((p.out / 4 + 255) / 256)), dim3(256), 0, st, ws, p.S, p.out, dw);
+    wg_launch(wg_plan(B, H, W, Cin, Cout), dh, x, ld_x, off_x, dw, ws, H, W, Cout, Cin, (hipStream_t)stream);
     FD_LAUNCH_OK("fd_conv3x3_wgrad_f32");
     return FD_OK;
 }

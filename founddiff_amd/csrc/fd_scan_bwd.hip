@@ -23,7 +23,7 @@
 //   4. params: one workgroup per channel sums the dA / dD / ddelta_bias partials over (batch, tile) in a fixed order.
 // No float atomics anywhere: two calls on the same inputs give the same bits.  States beyond NC = 4 / 8 are walked in
 // chunks of NC; du and the un-scaled ddt then accumulate in place over the chunks (same lane, same addresses).
-#include "fd_common.h"
+#include "fd_train_common.h"
 
 namespace {
 
@@ -359,8 +359,6 @@ int sb_splits(int batch, int KD, int K, int64_t L) {
     return S;
 }
 
-int64_t sb_round4(int64_t n) { return (n + 3) & ~(int64_t)3; }
-
 struct SbLayout {
     int ntiles, S;
     int64_t comp, part, bc, total;        // floats: each of the 3 composite arrays, the parameter partials, each dB / dC slab set
@@ -370,9 +368,9 @@ SbLayout sb_layout(int batch, int KD, int K, int N, int64_t L) {
     SbLayout w;
     w.ntiles = sb_ntiles(L);
     w.S = sb_splits(batch, KD, K, L);
-    w.comp = sb_round4((int64_t)w.ntiles * batch * KD * N);
-    w.part = sb_round4((int64_t)(N + 2) * KD * batch * w.ntiles);
-    w.bc = w.S > 1 ? sb_round4((int64_t)w.S * batch * K * N * L) : 0;
+    w.comp = round4((int64_t)w.ntiles * batch * KD * N);
+    w.part = round4((int64_t)(N + 2) * KD * batch * w.ntiles);
+    w.bc = w.S > 1 ? round4((int64_t)w.S * batch * K * N * L) : 0;
     w.total = 3 * w.comp + w.part + 2 * w.bc;
     return w;
 }

@@ -7,9 +7,9 @@
 //   fd_ln_silu_gate_bwd_f32     its backward                                     LayerNorm statistics kept per pixel)
 //
 // All three are streaming kernels: lane = 4 consecutive channels, 16-byte loads and stores along the channel axis.  Parameter
-// gradients are per-workgroup partials in the workspace, summed by dwb/lsg-independent launches of sum_kernel in a fixed order
-// (no float atomics): bit-repeatable.  Tile sizes, rows per workgroup and every order of summation that concerns one slice
-// depend on (H, W, C) only, never on the batch.
+// gradients are per-workgroup partials in the workspace, summed by dwb/lsg-independent launches of partial_sum_kernel
+// (fd_train_common.h) in a fixed order (no float atomics): bit-repeatable.  Tile sizes, rows per workgroup and every order of
+// summation that concerns one slice depend on (H, W, C) only, never on the batch.
 //
 // 1. dwconv + SiLU backward, two launches over the activation:
 //      pre:  workgroup = tpb tiles of 8 x 16 pixels x 64 channels; the (8+2) x (16+2) halo of x in LDS (x is read 1.41 times),
@@ -24,34 +24,9 @@
 // 2. LN + SiLU gate, one launch each way (+ the partial sums): a row (pixel) sits in lpr = 16 / 32 / 64 neighbouring lanes,
 //    VPL 16-byte vectors per lane; two-pass statistics in registers.  Forward: y, z in, out out = 3 A (algorithmic).  Backward:
 //    dout, y, z in, dy, dz out = 5 A (algorithmic); dgamma / dbeta / dlocal ride in registers over the rows of a workgroup.
-#include "fd_common.h"
+#include "fd_train_common.h"
 
 namespace {
-
-constexpr float LOG2E = 1.4426950408889634f;
-
-__device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-LOG2E * x)); }
-
-int64_t round4(int64_t n) { return (n + 3) & ~(int64_t)3; }
-
-// out[b][j][q] = sum of p[b][m][q] over m in [j G, min((j + 1) G, M)) in order; p rows ldp floats apart, out rows ldo
-__global__ __launch_bounds__(256) void sum_kernel(const float *__restrict__ p, int64_t ldp, int64_t p_bstride, int M, int Q, int G,
-                                                  float *__restrict__ out, int64_t ldo, int64_t o_bstride) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= Q) return;
-    const int j = blockIdx.y, b = blockIdx.z;
-    const int m1 = min(M, (j + 1) * G);
-    const float *pp = p + (int64_t)b * p_bstride + q;
-    float v = 0.f;
-    for (int m = j * G; m < m1; ++m) v += pp[(int64_t)m * ldp];
-    out[(int64_t)b * o_bstride + (int64_t)j * ldo + q] = v;
-}
-
-void launch_sum(const float *p, int64_t ldp, int64_t p_bstride, int M, int Q, int G, float *out, int64_t ldo, int64_t o_bstride,
-                int nb, hipStream_t st) {
-    hipLaunchKernelGGL(sum_kernel, dim3((unsigned)((Q + 255) / 256), (unsigned)((M + G - 1) / G), (unsigned)nb), dim3(256), 0, st,
-                       p, ldp, p_bstride, M, Q, G, out, ldo, o_bstride);
-}
 
 // ---- 1. SiLU(dwconv3x3 + bias) backward ----------------------------------------------------------------------------------
 constexpr int DB_TY = 8, DB_TX = 16, DB_CB = 64, DB_HX = DB_TX + 2, DB_HY = DB_TY + 2, DB_G = 32;
@@ -367,8 +342,6 @@ __global__ __launch_bounds__(256) void lsg_finish_kernel(const float *__restrict
     dgamma[c] = g;
     dbeta[c] = bt;
 }
-
-bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 

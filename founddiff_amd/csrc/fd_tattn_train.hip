@@ -26,7 +26,7 @@
 // Deterministic: Gram partials per pixel block in the workspace, summed in a fixed order; dtemperature summed over the batch in
 // order; no float atomics.  The pixel-block size and every order of summation depend on hw only: a slice's results are the same
 // bits alone or in a batch.  C % 64 == 0, C <= 512, heads of 32 channels.
-#include "fd_common.h"
+#include "fd_train_common.h"
 
 namespace {
 
@@ -37,8 +37,6 @@ constexpr int TA_ROWS = 256;               // pixels per workgroup of the stream
 // pixels per Gram block, the rule of fd_attn.hip: a function of the image size only
 inline int ta_pb(int64_t hw) { return hw >= 65536 ? 1024 : 256; }
 inline int ta_nblk(int64_t hw) { return (int)((hw + ta_pb(hw) - 1) / ta_pb(hw)); }
-int64_t ta_round4(int64_t n) { return (n + 3) & ~(int64_t)3; }
-
 bool ta_shape_ok(int B, int64_t hw, int C) {
     return B > 0 && B < 65536 && hw > 0 && hw < (1ll << 31) && C > 0 && C % 64 == 0 && C <= 512 && (int64_t)B * (C / 32) < 65536;
 }
@@ -338,8 +336,6 @@ __global__ __launch_bounds__(256) void ta_bwd_stream_kernel(const float *__restr
     }
 }
 
-bool ta_al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 void ta_gram(const float *a, int lda, int offa, const float *bm, int ldb, int offb, float *partial, int B, int64_t hw, int C,
              hipStream_t st) {
     const int nblk = ta_nblk(hw), heads = C / 32;
@@ -353,7 +349,7 @@ void ta_gram(const float *a, int lda, int offa, const float *bm, int ldb, int of
 
 extern "C" int64_t fd_chan_attn_fwd_ws_floats(int B, int64_t hw, int C) {
     if (!ta_shape_ok(B, hw, C)) return 0;
-    return ta_round4((int64_t)B * (C / 32) * ta_nblk(hw) * TA_SLOT);
+    return round4((int64_t)B * (C / 32) * ta_nblk(hw) * TA_SLOT);
 }
 
 extern "C" int fd_chan_attn_fwd_f32(const float *qkv, int ld, int off, const float *temperature, float *out, float *attn,
@@ -363,7 +359,7 @@ extern "C" int fd_chan_attn_fwd_f32(const float *qkv, int ld, int off, const flo
                (long long)hw, C);
     FD_REQUIRE(ld % 4 == 0 && off % 4 == 0 && off >= 0 && ld >= off + 3 * C,
                "fd_chan_attn_fwd_f32: stride / offset must be multiples of 4 with off + 3 C <= ld (ld=%d off=%d C=%d)", ld, off, C);
-    FD_REQUIRE(ta_al16(qkv) && ta_al16(out) && ta_al16(ws), "fd_chan_attn_fwd_f32: tensors must be 16-byte aligned");
+    FD_REQUIRE(al16(qkv) && al16(out) && al16(ws), "fd_chan_attn_fwd_f32: tensors must be 16-byte aligned");
     const hipStream_t st = (hipStream_t)stream;
     const int heads = C / 32;
     ta_gram(qkv, ld, off, qkv, ld, off + C, ws, B, hw, C, st);
@@ -378,7 +374,7 @@ extern "C" int fd_chan_attn_fwd_f32(const float *qkv, int ld, int off, const flo
 extern "C" int64_t fd_chan_attn_bwd_ws_floats(int B, int64_t hw, int C) {
     if (!ta_shape_ok(B, hw, C)) return 0;
     const int64_t bh = (int64_t)B * (C / 32);
-    return ta_round4(bh * ta_nblk(hw) * TA_SLOT) + ta_round4(bh * TA_SLOT) + ta_round4(bh);
+    return round4(bh * ta_nblk(hw) * TA_SLOT) + round4(bh * TA_SLOT) + round4(bh);
 }
 
 extern "C" int fd_chan_attn_bwd_f32(const float *qkv, int ld, int off, const float *temperature, const float *attn,
@@ -391,11 +387,11 @@ extern "C" int fd_chan_attn_bwd_f32(const float *qkv, int ld, int off, const flo
                    ld_d >= off_d + 3 * C,
                "fd_chan_attn_bwd_f32: strides / offsets must be multiples of 4 with off + 3 C <= ld (ld=%d off=%d ld_d=%d off_d=%d "
                "C=%d)", ld, off, ld_d, off_d, C);
-    FD_REQUIRE(ta_al16(qkv) && ta_al16(dout) && ta_al16(dqkv) && ta_al16(ws), "fd_chan_attn_bwd_f32: tensors must be 16-byte aligned");
+    FD_REQUIRE(al16(qkv) && al16(dout) && al16(dqkv) && al16(ws), "fd_chan_attn_bwd_f32: tensors must be 16-byte aligned");
     const hipStream_t st = (hipStream_t)stream;
     const int heads = C / 32;
     const int64_t bh = (int64_t)B * heads;
-    float *partial = ws, *coef = partial + ta_round4(bh * ta_nblk(hw) * TA_SLOT), *dtpart = coef + ta_round4(bh * TA_SLOT);
+    float *partial = ws, *coef = partial + round4(bh * ta_nblk(hw) * TA_SLOT), *dtpart = coef + round4(bh * TA_SLOT);
     ta_gram(dout, C, 0, qkv, ld, off + 2 * C, partial, B, hw, C, st);
     hipLaunchKernelGGL(ta_bwd_small_kernel, dim3((unsigned)heads, (unsigned)B), dim3(64), 0, st, partial, ta_nblk(hw), temperature,
                        attn, ghat, nrm, coef, dtpart, hw == 1 ? 1 : 0);

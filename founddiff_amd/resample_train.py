@@ -26,7 +26,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .tattn_train import _HALF, _cast, _check, _check_devices, _dout, _f32, _p, _strided, _ws
+from ._train import HALF, cast_grads, check_devices, check_tensors, conv2d_f32, f32, grad_out, ptr, stream, strided, workspace
 
 __all__ = ["downsample_fn", "upsample_fn", "conv3x3_fn", "resample_nhwc", "up_weight_4x4", "up_weight_unfold", "sub2x_weight"]
 
@@ -73,7 +73,7 @@ def _shape_ok(cin, cout):
 
 def _check_fn(fn, x, weight, bias, k, even=False):
     named = [("x", x), ("weight", weight), ("bias", bias)]
-    _check(fn, named)
+    check_tensors(fn, named)
     shapes = " ".join(f"{n}{tuple(t.shape)}" for n, t in named)
     if x.dim() != 4 or min(x.shape) < 1:
         raise RuntimeError(f"{fn}: inconsistent shapes {shapes} (x is (B, H, W, Cin))")
@@ -86,37 +86,14 @@ def _check_fn(fn, x, weight, bias, k, even=False):
         raise RuntimeError(f"{fn}: unsupported shape Cin={x.shape[3]} Cout={cout} ({_SUPPORTED})")
     if even and (x.shape[1] % 2 or x.shape[2] % 2):
         raise RuntimeError(f"{fn}: unsupported shape H={x.shape[1]} W={x.shape[2]} (both must be even)")
-    _check_devices(fn, named)
+    check_devices(fn, named)
     return x.shape[0], x.shape[1], x.shape[2], x.shape[3], cout
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _conv2d(x, ld, off, cin, wk, bias, cout, dims, k, stride):
-    """fd_conv2d, exact fp32, k x k / stride / padding 1: x channels [off, off + cin) of (B, H, W, ld); wk [cout][k k cin], K
-    order (kh, kw, c)"""
-    B, H, W = dims
-    OH, OW = (H + 2 - k) // stride + 1, (W + 2 - k) // stride + 1
-    out = torch.empty(B, OH, OW, cout, device=x.device, dtype=torch.float32)
-    p = L.ConvParams()
-    p.dtype, p.out_f32 = L.FD_F32, 0
-    p.in0, p.c0, p.ld0, p.off0 = x.data_ptr() - 4 * off, cin, ld, off
-    p.B, p.H, p.W, p.OH, p.OW = B, H, W, OH, OW
-    p.KH, p.KW, p.stride, p.pad_h, p.pad_w, p.ndir = k, k, stride, 1, 1, 1
-    p.weight, p.bias = wk.data_ptr(), (None if bias is None else bias.data_ptr())
-    p.Cout, p.out, p.ldo, p.offo = cout, out.data_ptr(), cout, 0
-    p.epilogue, p.ld_res, p.gn_groups = L.EPI_NONE, cout, 1
-    p.f32_split = 0
-    L.call("fd_conv2d", C.byref(p), _stream(x.device))
-    return out
 
 
 def _sub2x(x, w2, bias, dims, cin, cout):
     B, H, W = dims
     out = torch.empty(B, 2 * H, 2 * W, cout, device=x.device, dtype=torch.float32)
-    L.call("fd_conv_sub2x_f32", _p(x), _p(w2), _p(bias), _p(out), B, H, W, cin, cout, _stream(x.device))
+    L.call("fd_conv_sub2x_f32", ptr(x), ptr(w2), ptr(bias), ptr(out), B, H, W, cin, cout, stream(x.device))
     return out
 
 
@@ -124,8 +101,8 @@ def _corr(coarse, fine, dims, P, Q):
     """g [P][4][4][Q]; coarse (B, H, W, P), fine (B, 2H, 2W, Q)"""
     B, H, W = dims
     g = torch.empty(P, 4, 4, Q, device=coarse.device, dtype=torch.float32)
-    ws = _ws("fd_corr4x4s2_ws_floats", coarse.device, B, H, W, P, Q)
-    L.call("fd_corr4x4s2_f32", _p(coarse), _p(fine), _p(g), _p(ws), B, H, W, P, Q, _stream(coarse.device))
+    ws = workspace("fd_corr4x4s2_ws_floats", coarse.device, B, H, W, P, Q)
+    L.call("fd_corr4x4s2_f32", ptr(coarse), ptr(fine), ptr(g), ptr(ws), B, H, W, P, Q, stream(coarse.device))
     return g
 
 
@@ -134,10 +111,10 @@ class _Down(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         B, H, W, cin, cout = _check_fn("downsample_fn", x, weight, bias, 4, even=True)
         ctx.dtypes, ctx.dims = (x.dtype, weight.dtype, bias.dtype), (B, H, W, cin, cout)
-        x, w, bias = _f32(x).contiguous(), _f32(weight), _f32(bias).contiguous()
+        x, w, bias = f32(x).contiguous(), f32(weight), f32(bias).contiguous()
         with torch.cuda.device(x.device):
             wk = w.permute(0, 2, 3, 1).contiguous()                     # [Cout][kh][kw][c], as fd_conv2d takes it
-            out = _conv2d(x, cin, 0, cin, wk, bias, cout, (B, H, W), 4, 2)
+            out = conv2d_f32(x, cin, 0, cin, wk, bias, cout, (B, H, W), 4, 2)
         ctx.save_for_backward(x, w)
         return out
 
@@ -145,14 +122,14 @@ class _Down(torch.autograd.Function):
     def backward(ctx, dout):
         x, w = ctx.saved_tensors
         B, H, W, cin, cout = ctx.dims
-        dout = _dout("downsample_fn", dout, (B, H // 2, W // 2, cout))
+        dout = grad_out("downsample_fn", dout, (B, H // 2, W // 2, cout))
         with torch.cuda.device(x.device):
             w2 = sub2x_weight(w.transpose(0, 1))                        # [c][2a+b][r][s][n] = w[n][c][kh(a,r)][kw(b,s)]
             dx = _sub2x(dout, w2, None, (B, H // 2, W // 2), cout, cin)
             del w2
             g = _corr(dout, x, (B, H // 2, W // 2), cout, cin)          # [n][kh][kw][c]
             dbias = dout.sum((0, 1, 2))
-        return _cast((dx, g.permute(0, 3, 1, 2), dbias), ctx.dtypes)
+        return cast_grads((dx, g.permute(0, 3, 1, 2), dbias), ctx.dtypes)
 
 
 class _Up(torch.autograd.Function):
@@ -160,7 +137,7 @@ class _Up(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         B, H, W, cin, cout = _check_fn("upsample_fn", x, weight, bias, 3)
         ctx.dtypes, ctx.dims = (x.dtype, weight.dtype, bias.dtype), (B, H, W, cin, cout)
-        x, w, bias = _f32(x).contiguous(), _f32(weight), _f32(bias).contiguous()
+        x, w, bias = f32(x).contiguous(), f32(weight), f32(bias).contiguous()
         with torch.cuda.device(x.device):
             w2 = sub2x_weight(up_weight_4x4(w))
             out = _sub2x(x, w2, bias, (B, H, W), cin, cout)
@@ -171,15 +148,15 @@ class _Up(torch.autograd.Function):
     def backward(ctx, dout):
         x, w = ctx.saved_tensors
         B, H, W, cin, cout = ctx.dims
-        dout = _dout("upsample_fn", dout, (B, 2 * H, 2 * W, cout))
+        dout = grad_out("upsample_fn", dout, (B, 2 * H, 2 * W, cout))
         with torch.cuda.device(x.device):
             wd = up_weight_4x4(w).permute(1, 2, 3, 0).contiguous()      # wd[c][t][u][n]: Down-shaped, dout -> dx
-            dx = _conv2d(dout, cout, 0, cout, wd, None, cin, (B, 2 * H, 2 * W), 4, 2)
+            dx = conv2d_f32(dout, cout, 0, cout, wd, None, cin, (B, 2 * H, 2 * W), 4, 2)
             del wd
             g = _corr(x, dout, (B, H, W), cin, cout)                    # [c][t][u][n]
             dw = up_weight_unfold(g.permute(3, 0, 1, 2))
             dbias = dout.sum((0, 1, 2))
-        return _cast((dx, dw, dbias), ctx.dtypes)
+        return cast_grads((dx, dw, dbias), ctx.dtypes)
 
 
 class _Conv3(torch.autograd.Function):
@@ -187,11 +164,11 @@ class _Conv3(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         B, H, W, cin, cout = _check_fn("conv3x3_fn", x, weight, bias, 3)
         ctx.dtypes, ctx.dims = (x.dtype, weight.dtype, bias.dtype), (B, H, W, cin, cout)
-        x, ld, off = _strided(_f32(x), cin)
-        w, bias = _f32(weight), _f32(bias).contiguous()
+        x, ld, off = strided(f32(x), cin)
+        w, bias = f32(weight), f32(bias).contiguous()
         with torch.cuda.device(x.device):
             wk = w.permute(0, 2, 3, 1).contiguous()
-            out = _conv2d(x, ld, off, cin, wk, bias, cout, (B, H, W), 3, 1)
+            out = conv2d_f32(x, ld, off, cin, wk, bias, cout, (B, H, W), 3, 1)
         ctx.ld_off = (ld, off)
         ctx.save_for_backward(x, w)
         return out
@@ -201,18 +178,18 @@ class _Conv3(torch.autograd.Function):
         x, w = ctx.saved_tensors
         B, H, W, cin, cout = ctx.dims
         ld, off = ctx.ld_off
-        dout = _dout("conv3x3_fn", dout, (B, H, W, cout))
+        dout = grad_out("conv3x3_fn", dout, (B, H, W, cout))
         dev = x.device
         with torch.cuda.device(dev):
             dwk = torch.empty(cout, 3, 3, cin, device=dev, dtype=torch.float32)
-            ws = _ws("fd_conv3x3_wgrad_ws_floats", dev, B, H, W, cin, cout)
-            L.call("fd_conv3x3_wgrad_f32", C.c_void_p(x.data_ptr() - 4 * off), ld, off, _p(dout), _p(dwk), _p(ws), B, H, W, cin, cout,
-                   _stream(dev))
+            ws = workspace("fd_conv3x3_wgrad_ws_floats", dev, B, H, W, cin, cout)
+            L.call("fd_conv3x3_wgrad_f32", C.c_void_p(x.data_ptr() - 4 * off), ld, off, ptr(dout), ptr(dwk), ptr(ws), B, H, W, cin,
+                   cout, stream(dev))
             del ws
             wd = w.flip(2, 3).permute(1, 2, 3, 0).contiguous()          # wd[c][kh][kw][n] = w[n][c][2 - kh][2 - kw]
-            dx = _conv2d(dout, cout, 0, cout, wd, None, cin, (B, H, W), 3, 1)
+            dx = conv2d_f32(dout, cout, 0, cout, wd, None, cin, (B, H, W), 3, 1)
             dbias = dout.sum((0, 1, 2))
-        return _cast((dx, dwk.permute(0, 3, 1, 2), dbias), ctx.dtypes)
+        return cast_grads((dx, dwk.permute(0, 3, 1, 2), dbias), ctx.dtypes)
 
 
 def downsample_fn(x, weight, bias):
@@ -272,7 +249,7 @@ def resample_nhwc(module, x):
         raise RuntimeError(f"{fn}: the convolution must have a bias")
     if not isinstance(x, torch.Tensor):
         raise RuntimeError(f"{fn}: x must be a tensor (got {type(x).__name__})")
-    if x.dtype not in (torch.float32,) + _HALF:
+    if x.dtype not in (torch.float32,) + HALF:
         raise RuntimeError(f"{fn}: x must be float32 / float16 / bfloat16 (got {x.dtype})")
     if x.dim() != 4 or x.shape[3] != conv.in_channels or min(x.shape) < 1:
         raise RuntimeError(f"{fn}: inconsistent shapes x{tuple(x.shape)} (expected (B, H, W, {conv.in_channels}))")

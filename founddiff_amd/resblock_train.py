@@ -26,7 +26,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .tattn_train import _HALF, _cast, _check, _check_devices, _dout, _f32, _p, _strided, _ws
+from ._train import HALF, cast_grads, check_devices, check_tensors, conv2d_f32, empty, f32, grad_out, ptr, stream, workspace
+from ._train import strided as _strided
 
 __all__ = ["block_core_fn", "ws_weight", "resnet_block_nhwc", "resnet_block_forward", "ResnetBlock"]
 
@@ -41,7 +42,7 @@ def _shape_ok(cin, cout, groups):
 
 def _check_core(fn, x, weight, bias, gn_weight, gn_bias, res, groups):
     named = [("x", x), ("weight", weight), ("bias", bias), ("gn_weight", gn_weight), ("gn_bias", gn_bias), ("res", res)]
-    _check(fn, named, optional=("res",))
+    check_tensors(fn, named, optional=("res",))
     shapes = " ".join(f"{n}{tuple(t.shape)}" for n, t in named if t is not None)
     if x.dim() != 4 or min(x.shape) < 1:
         raise RuntimeError(f"{fn}: inconsistent shapes {shapes} (x is (B, H, W, Cin))")
@@ -55,26 +56,8 @@ def _check_core(fn, x, weight, bias, gn_weight, gn_bias, res, groups):
         raise RuntimeError(f"{fn}: inconsistent shapes {shapes} (res is (B, H, W, Cout) or None)")
     if not isinstance(groups, int) or not _shape_ok(x.shape[3], cout, groups):
         raise RuntimeError(f"{fn}: unsupported shape Cin={x.shape[3]} Cout={cout} groups={groups} ({_SUPPORTED})")
-    _check_devices(fn, named)
+    check_devices(fn, named)
     return dims
-
-
-def _conv3x3(x, ld, off, cin, wk, bias, cout, dims, stats=None):
-    """fd_conv2d, exact fp32: x channels [off, off + cin) of (B, H, W, ld); wk [cout][9 cin], K order (kh, kw, c)"""
-    B, H, W = dims
-    out = torch.empty(B, H, W, cout, device=x.device, dtype=torch.float32)
-    p = L.ConvParams()
-    p.dtype, p.out_f32 = L.FD_F32, 0
-    p.in0, p.c0, p.ld0, p.off0 = x.data_ptr() - 4 * off, cin, ld, off
-    p.B, p.H, p.W, p.OH, p.OW = B, H, W, H, W
-    p.KH, p.KW, p.stride, p.pad_h, p.pad_w, p.ndir = 3, 3, 1, 1, 1, 1
-    p.weight, p.bias = wk.data_ptr(), (None if bias is None else bias.data_ptr())
-    p.Cout, p.out, p.ldo, p.offo = cout, out.data_ptr(), cout, 0
-    p.epilogue, p.ld_res, p.gn_groups = L.EPI_NONE, cout, 1
-    p.stats_partial = None if stats is None else stats.data_ptr()
-    p.f32_split = 0
-    L.call("fd_conv2d", C.byref(p), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    return out
 
 
 class _BlockCore(torch.autograd.Function):
@@ -84,22 +67,22 @@ class _BlockCore(torch.autograd.Function):
         dims = B, H, W, cout = _check_core("block_core_fn", *args, groups)
         cin = x.shape[3]
         ctx.dtypes, ctx.dims, ctx.cin, ctx.groups = tuple(None if t is None else t.dtype for t in args), dims, cin, groups
-        x, ld, off = _strided(_f32(x), cin)
-        w = _f32(weight)
-        bias, gamma, beta = (_f32(t).contiguous() for t in (bias, gn_weight, gn_bias))
-        r = None if res is None else _f32(res).contiguous()
+        x, ld, off = _strided(f32(x), cin)
+        w = f32(weight)
+        bias, gamma, beta = (f32(t).contiguous() for t in (bias, gn_weight, gn_bias))
+        r = None if res is None else f32(res).contiguous()
         dev = x.device
         with torch.cuda.device(dev):
             wk = w.permute(0, 2, 3, 1).contiguous()                     # [Cout][kh][kw][c], as fd_conv2d takes it
             mt = int(L.lib().fd_conv_mtiles(H, W))
             part = torch.empty(B, mt, cout, 2, device=dev, dtype=torch.float32)
-            h = _conv3x3(x, ld, off, cin, wk, bias, cout, (B, H, W), stats=part)
+            h = conv2d_f32(x, ld, off, cin, wk, bias, cout, (B, H, W), stats=part)
             del wk
             mr = torch.empty(B, groups, 2, device=dev, dtype=torch.float32)
             out = torch.empty(B, H, W, cout, device=dev, dtype=torch.float32)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            L.call("fd_gn_finalize", _p(part), B, mt, cout, groups, H * W, float(eps), _p(mr), stream)
-            L.call("fd_gn_silu_apply", L.FD_F32, _p(h), _p(mr), _p(gamma), _p(beta), _p(r), _p(out), B, H * W, cout, groups, stream)
+            L.call("fd_gn_finalize", ptr(part), B, mt, cout, groups, H * W, float(eps), ptr(mr), stream(dev))
+            L.call("fd_gn_silu_apply", L.FD_F32, ptr(h), ptr(mr), ptr(gamma), ptr(beta), ptr(r), ptr(out), B, H * W, cout, groups,
+                   stream(dev))
         ctx.ld_off = (ld, off)
         ctx.save_for_backward(x, w, h, mr, gamma, beta)
         return out
@@ -110,25 +93,24 @@ class _BlockCore(torch.autograd.Function):
         B, H, W, cout = ctx.dims
         cin, groups = ctx.cin, ctx.groups
         ld, off = ctx.ld_off
-        dout = _dout("block_core_fn", dout, ctx.dims)
+        dout = grad_out("block_core_fn", dout, ctx.dims)
         dev = x.device
         with torch.cuda.device(dev):
-            new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            new = empty(dev)
             dh, dgamma, dbeta, dbias = new(B, H, W, cout), new(cout), new(cout), new(cout)
-            ws = _ws("fd_gn_silu_bwd_ws_floats", dev, B, H * W, cout, groups)
-            L.call("fd_gn_silu_bwd_f32", _p(dout), _p(h), _p(mr), _p(gamma), _p(beta), _p(dh), _p(dgamma), _p(dbeta), _p(dbias),
-                   _p(ws), B, H * W, cout, groups, stream)
+            ws = workspace("fd_gn_silu_bwd_ws_floats", dev, B, H * W, cout, groups)
+            L.call("fd_gn_silu_bwd_f32", ptr(dout), ptr(h), ptr(mr), ptr(gamma), ptr(beta), ptr(dh), ptr(dgamma), ptr(dbeta),
+                   ptr(dbias), ptr(ws), B, H * W, cout, groups, stream(dev))
             dwk = new(cout, 3, 3, cin)
-            ws = _ws("fd_conv3x3_wgrad_ws_floats", dev, B, H, W, cin, cout)
-            L.call("fd_conv3x3_wgrad_f32", C.c_void_p(x.data_ptr() - 4 * off), ld, off, _p(dh), _p(dwk), _p(ws), B, H, W, cin, cout,
-                   stream)
+            ws = workspace("fd_conv3x3_wgrad_ws_floats", dev, B, H, W, cin, cout)
+            L.call("fd_conv3x3_wgrad_f32", C.c_void_p(x.data_ptr() - 4 * off), ld, off, ptr(dh), ptr(dwk), ptr(ws), B, H, W, cin,
+                   cout, stream(dev))
             del ws
             wd = w.flip(2, 3).permute(1, 2, 3, 0).contiguous()          # wd[c][kh][kw][n] = w[n][c][2 - kh][2 - kw]
-            dx = _conv3x3(dh, cout, 0, cout, wd, None, cin, (B, H, W))
+            dx = conv2d_f32(dh, cout, 0, cout, wd, None, cin, (B, H, W))
             del dh, wd
         dres = dout if ctx.dtypes[5] is not None else None
-        return _cast((dx, dwk.permute(0, 3, 1, 2), dbias, dgamma, dbeta, dres), ctx.dtypes) + (None, None)
+        return cast_grads((dx, dwk.permute(0, 3, 1, 2), dbias, dgamma, dbeta, dres), ctx.dtypes) + (None, None)
 
 
 def block_core_fn(x, weight, bias, gn_weight, gn_bias, res=None, groups=8, eps=1e-5):
@@ -178,7 +160,7 @@ def _check_module(fn, self, x, channel_axis):
         raise RuntimeError(f"{fn}: unsupported shape Cin={cin} Cout={cout} groups={norm.num_groups} ({_SUPPORTED})")
     if not isinstance(x, torch.Tensor):
         raise RuntimeError(f"{fn}: x must be a tensor (got {type(x).__name__})")
-    if x.dtype not in (torch.float32,) + _HALF:
+    if x.dtype not in (torch.float32,) + HALF:
         raise RuntimeError(f"{fn}: x must be float32 / float16 / bfloat16 (got {x.dtype})")
     if x.dim() != 4 or x.shape[channel_axis] != cin or min(x.shape) < 1:
         want = f"(B, {cin}, H, W)" if channel_axis == 1 else f"(B, H, W, {cin})"

@@ -17,11 +17,10 @@ by accident; a training run binds this module under the extension's name instead
 `selective_scan_fn(u, delta, A, B, C, D=None, delta_bias=None, delta_softplus=False)` is the same pair as an autograd
 function, for code that does not import the reference.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib as L
+from ._train import HALF, cast_grads, check_devices, f32, ptr, stream, workspace
 from .selective_scan_cuda_core import fwd
 
 __all__ = ["fwd", "bwd", "selective_scan_fn"]
@@ -30,15 +29,13 @@ __all__ = ["fwd", "bwd", "selective_scan_fn"]
 def _chk(name, t, ndim):
     if not isinstance(t, torch.Tensor):
         raise RuntimeError(f"selective_scan_train.bwd: {name} must be a tensor (got {type(t).__name__})")
-    if t.dtype in (torch.float16, torch.bfloat16):
-        t = t.float()          # as fwd: the reference's wrapper runs the op in fp32
-    if t.dtype != torch.float32:
+    if t.dtype not in (torch.float32,) + HALF:
         raise RuntimeError(f"selective_scan_train.bwd: {name} must be float32 / float16 / bfloat16 (got {t.dtype})")
     if t.dim() != ndim:
         raise RuntimeError(f"selective_scan_train.bwd: {name} must be {ndim}-dimensional (got {tuple(t.shape)})")
     if not t.is_cuda:
         raise RuntimeError(f"selective_scan_train.bwd: {name} must live on the GPU (there is no CPU path)")
-    return t if t.is_contiguous() else t.contiguous()
+    return f32(t).contiguous()          # as fwd: the reference's wrapper runs the op in fp32
 
 
 def bwd(u, delta, A, B, C_, D, delta_bias, dout, x, delta_softplus=False, nrows=1):
@@ -65,22 +62,18 @@ def bwd(u, delta, A, B, C_, D, delta_bias, dout, x, delta_softplus=False, nrows=
         D = _chk("D", D, 1)
     if delta_bias is not None:
         delta_bias = _chk("delta_bias", delta_bias, 1)
-    for name, t in (("delta", delta), ("dout", dout), ("A", A), ("B", B), ("C", C_), ("D", D), ("delta_bias", delta_bias)):
-        if t is not None and t.device != u.device:
-            raise RuntimeError(f"selective_scan_train.bwd: {name} lives on {t.device}, u on {u.device}")
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    check_devices("selective_scan_train.bwd", (("u", u), ("delta", delta), ("dout", dout), ("A", A), ("B", B), ("C", C_), ("D", D),
+                                               ("delta_bias", delta_bias)))
     with torch.cuda.device(u.device):
         du, ddelta = torch.empty_like(u), torch.empty_like(u)
         dA = torch.empty_like(A)
         dB, dC = torch.empty_like(B), torch.empty_like(C_)
         dD = torch.empty_like(D) if D is not None else None
         dbias = torch.empty_like(delta_bias) if delta_bias is not None else None
-        nws = int(L.lib().fd_selective_scan_bwd_ws_floats(b, KD, K, N, Ln))
-        ws = torch.empty(max(nws, 4), device=u.device, dtype=torch.float32)      # the caching allocator's blocks are 512-byte aligned
-        stream = C.c_void_p(torch.cuda.current_stream(u.device).cuda_stream)
-        L.call("fd_selective_scan_bwd_f32", p(u), p(delta), p(A), p(B), p(C_), p(D), p(delta_bias), p(dout),
-               int(bool(delta_softplus)), int(nrows), b, KD, K, N, Ln, p(du), p(ddelta), p(dA), p(dB), p(dC), p(dD),
-               p(dbias), p(ws), stream)
+        ws = workspace("fd_selective_scan_bwd_ws_floats", u.device, b, KD, K, N, Ln)
+        L.call("fd_selective_scan_bwd_f32", ptr(u), ptr(delta), ptr(A), ptr(B), ptr(C_), ptr(D), ptr(delta_bias), ptr(dout),
+               int(bool(delta_softplus)), int(nrows), b, KD, K, N, Ln, ptr(du), ptr(ddelta), ptr(dA), ptr(dB), ptr(dC), ptr(dD),
+               ptr(dbias), ptr(ws), stream(u.device))
     if squeeze:
         dB, dC = dB.squeeze(1), dC.squeeze(1)
     return du, ddelta, dA, dB, dC, dD, dbias
@@ -99,8 +92,7 @@ class _SelectiveScan(torch.autograd.Function):
     def backward(ctx, dout):
         u, delta, A, B, C_, D, delta_bias, x = ctx.saved_tensors
         grads = bwd(u, delta, A, B, C_, D, delta_bias, dout, x, ctx.delta_softplus, 1)
-        grads = [g.to(dt) if g is not None and g.dtype != dt else g for g, dt in zip(grads, ctx.dtypes)]
-        return (*grads, None)
+        return cast_grads(grads, ctx.dtypes) + (None,)
 
 
 def selective_scan_fn(u, delta, A, B, C, D=None, delta_bias=None, delta_softplus=False):

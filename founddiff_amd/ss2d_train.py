@@ -20,12 +20,12 @@ Binding for a training run:
 `SS2D(d_model, d_state, dropout=0.0)` is a module with the reference's parameter names and shapes (its state dict loads with
 strict=True) for code that does not import the reference.
 """
-import ctypes as C
 import math
 
 import torch
 
 from . import _lib as L
+from ._train import cast_grads, check_devices, check_tensors, empty, f32, ptr, stream, workspace
 
 __all__ = ["ss2d_core_fn", "ss2d_forward", "SS2D"]
 
@@ -34,25 +34,11 @@ _NAMES = ("xz", "conv_weight", "conv_bias", "x_proj_weight", "dt_projs_weight", 
           "norm_bias", "local")
 
 
-def _f32(name, t):
-    if t.dtype in (torch.float16, torch.bfloat16):
-        t = t.float()            # as cross_scan_train: the op runs in fp32
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"ss2d_core_fn: {name} must be float32 / float16 / bfloat16 (got {t.dtype})")
-    return t.contiguous()
-
-
 def _check(xz, conv_weight, conv_bias, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds, norm_weight, norm_bias, local):
     """Types, shapes and devices, in that order, before anything is launched (or CUDA initialised)."""
     named = list(zip(_NAMES, (xz, conv_weight, conv_bias, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds, norm_weight,
                               norm_bias, local)))
-    for name, t in named:
-        if t is None and name in ("conv_bias", "local"):
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"ss2d_core_fn: {name} must be a tensor (got {type(t).__name__})")
-        if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise RuntimeError(f"ss2d_core_fn: {name} must be float32 / float16 / bfloat16 (got {t.dtype})")
+    check_tensors("ss2d_core_fn", named, optional=("conv_bias", "local"))
     shapes = " ".join(f"{n}{tuple(t.shape)}" for n, t in named if t is not None)
     if xz.dim() != 4 or xz.shape[-1] % 2 or dt_projs_weight.dim() != 3 or A_logs.dim() != 2:
         raise RuntimeError(f"ss2d_core_fn: inconsistent shapes {shapes} (xz is (B, H, W, 2 d_inner))")
@@ -71,23 +57,8 @@ def _check(xz, conv_weight, conv_bias, x_proj_weight, dt_projs_weight, dt_projs_
     if D % 64 or D > 1024 or N not in _N_OK or R not in _R_OK or B < 1 or H < 1 or W < 1:
         raise RuntimeError(f"ss2d_core_fn: unsupported shape d_inner={D} (multiple of 64, at most 1024), d_state={N} (one of "
                            f"{_N_OK}), dt_rank={R} (one of {_R_OK}), image {H}x{W}, batch {B}")
-    for name, t in named:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError(f"ss2d_core_fn: {name} must live on the GPU (there is no CPU path)")
-        if t.device != xz.device:
-            raise RuntimeError(f"ss2d_core_fn: {name} lives on {t.device}, xz on {xz.device}")
+    check_devices("ss2d_core_fn", named)
     return B, H, W, D, N, R
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _ws(name, dev, *args):
-    n = int(getattr(L.lib(), name)(*args))
-    return torch.empty(max(n, 4), device=dev, dtype=torch.float32)      # the caching allocator's blocks are 512-byte aligned
 
 
 class _SS2DCore(torch.autograd.Function):
@@ -98,23 +69,22 @@ class _SS2DCore(torch.autograd.Function):
         B, H, W, D, N, R = _check(*args)
         ctx.dtypes = tuple(None if t is None else t.dtype for t in args)
         ctx.shapes = (dt_projs_bias.shape, None if local is None else local.shape)
-        xz, cw, cb, xw, dtw, dtb, Al, Dv, gw, gb, loc = (None if t is None else _f32(n, t) for n, t in zip(_NAMES, args))
+        xz, cw, cb, xw, dtw, dtb, Al, Dv, gw, gb, loc = (None if t is None else f32(t).contiguous() for t in args)
         w9 = cw.reshape(D, 9).t().contiguous()               # [9][D] tap-major, as fd_dwconv3x3 takes it
         A = -torch.exp(Al)
         loc2 = None if loc is None else loc.reshape(B, D)
         dev = xz.device
         L2 = ((H + 1) // 2) * ((W + 1) // 2)
         with torch.cuda.device(dev):
-            new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+            new = empty(dev)
             xc, y, out = new(B, H, W, D), new(B, H, W, D), new(B, H, W, D)
             xdbl, stats = new(4, B, L2, R + 2 * N), new(B, H, W, 2)
-            ws = _ws("fd_scan_ws_floats", dev, B, H, W, D, N)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            L.call("fd_dwconv3x3", L.FD_F32, _p(xz), 2 * D, 0, _p(w9), _p(cb), 1, _p(xc), D, 0, B, H, W, D, stream)
-            L.call("fd_cross_scan_fwd_nhwc_f32", _p(xc), _p(xw), _p(dtw), _p(dtb), _p(A), _p(Dv), _p(xdbl), _p(y), _p(ws),
-                   B, H, W, D, N, R, stream)
-            L.call("fd_ln_silu_gate_fwd_f32", _p(y), _p(gw), _p(gb), float(eps), _p(xz), 2 * D, D, _p(loc2), D, _p(out), _p(stats),
-                   B, H * W, D, stream)
+            ws = workspace("fd_scan_ws_floats", dev, B, H, W, D, N)
+            L.call("fd_dwconv3x3", L.FD_F32, ptr(xz), 2 * D, 0, ptr(w9), ptr(cb), 1, ptr(xc), D, 0, B, H, W, D, stream(dev))
+            L.call("fd_cross_scan_fwd_nhwc_f32", ptr(xc), ptr(xw), ptr(dtw), ptr(dtb), ptr(A), ptr(Dv), ptr(xdbl), ptr(y), ptr(ws),
+                   B, H, W, D, N, R, stream(dev))
+            L.call("fd_ln_silu_gate_fwd_f32", ptr(y), ptr(gw), ptr(gb), float(eps), ptr(xz), 2 * D, D, ptr(loc2), D, ptr(out),
+                   ptr(stats), B, H * W, D, stream(dev))
         ctx.dims = (B, H, W, D, N, R)
         ctx.has = (cb is not None, loc is not None)
         ctx.save_for_backward(xz, xc, xdbl, y, stats, w9, cb, xw, dtw, dtb, A, Dv, gw, gb)
@@ -127,32 +97,31 @@ class _SS2DCore(torch.autograd.Function):
         has_bias, has_local = ctx.has
         if tuple(dout.shape) != (B, H, W, D):
             raise RuntimeError(f"ss2d_core_fn: the gradient of out must be {(B, H, W, D)} (got {tuple(dout.shape)})")
-        dout = _f32("the gradient of out", dout)
+        dout = f32(dout).contiguous()
         dev = xz.device
         with torch.cuda.device(dev):
-            new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            new = empty(dev)
             dxz, dy = new(B, H, W, 2 * D), new(B, H, W, D)
             dgw, dgb = new(D), new(D)
             dloc = new(B, D) if has_local else None
-            ws = _ws("fd_ln_silu_gate_bwd_ws_floats", dev, B, H * W, D)
-            L.call("fd_ln_silu_gate_bwd_f32", _p(dout), _p(y), _p(stats), _p(gw), _p(gb), _p(xz), 2 * D, D, _p(dy), _p(dxz), 2 * D, D,
-                   _p(dgw), _p(dgb), _p(dloc), _p(ws), B, H * W, D, stream)
+            ws = workspace("fd_ln_silu_gate_bwd_ws_floats", dev, B, H * W, D)
+            L.call("fd_ln_silu_gate_bwd_f32", ptr(dout), ptr(y), ptr(stats), ptr(gw), ptr(gb), ptr(xz), 2 * D, D, ptr(dy), ptr(dxz),
+                   2 * D, D, ptr(dgw), ptr(dgb), ptr(dloc), ptr(ws), B, H * W, D, stream(dev))
             dxc = new(B, H, W, D)
             dxw, ddtw, ddtb, dA, dDs = torch.empty_like(xw), torch.empty_like(dtw), new(4 * D), torch.empty_like(A), torch.empty_like(Dv)
-            ws = _ws("fd_cross_scan_bwd_ws_floats", dev, B, H, W, D, N, R)
-            L.call("fd_cross_scan_bwd_nhwc_f32", _p(xc), _p(xdbl), _p(xw), _p(dtw), _p(dtb), _p(A), _p(Dv), _p(dy), _p(dxc), _p(dxw),
-                   _p(ddtw), _p(ddtb), _p(dA), _p(dDs), _p(ws), B, H, W, D, N, R, stream)
+            ws = workspace("fd_cross_scan_bwd_ws_floats", dev, B, H, W, D, N, R)
+            L.call("fd_cross_scan_bwd_nhwc_f32", ptr(xc), ptr(xdbl), ptr(xw), ptr(dtw), ptr(dtb), ptr(A), ptr(Dv), ptr(dy), ptr(dxc),
+                   ptr(dxw), ptr(ddtw), ptr(ddtb), ptr(dA), ptr(dDs), ptr(ws), B, H, W, D, N, R, stream(dev))
             del dy
             dw9, dcb = new(9, D), (new(D) if has_bias else None)
-            ws = _ws("fd_dwconv3x3_silu_bwd_ws_floats", dev, B, H, W, D)
-            L.call("fd_dwconv3x3_silu_bwd_f32", _p(xz), 2 * D, 0, _p(w9), _p(cb), _p(dxc), _p(dxz), 2 * D, 0, _p(dw9), _p(dcb), _p(ws),
-                   B, H, W, D, stream)
+            ws = workspace("fd_dwconv3x3_silu_bwd_ws_floats", dev, B, H, W, D)
+            L.call("fd_dwconv3x3_silu_bwd_f32", ptr(xz), 2 * D, 0, ptr(w9), ptr(cb), ptr(dxc), ptr(dxz), 2 * D, 0, ptr(dw9), ptr(dcb),
+                   ptr(ws), B, H, W, D, stream(dev))
             del dxc, ws
         bias_shape, local_shape = ctx.shapes
         grads = (dxz, dw9.t().reshape(D, 1, 3, 3), dcb, dxw, ddtw, ddtb.view(bias_shape), dA * A, dDs, dgw, dgb,
                  None if dloc is None else dloc.view(local_shape))       # A = -exp(A_logs): dA_logs = dA * A
-        return tuple(None if g is None else (g.to(dt) if g.dtype != dt else g) for g, dt in zip(grads, ctx.dtypes)) + (None,)
+        return cast_grads(grads, ctx.dtypes) + (None,)
 
 
 def ss2d_core_fn(xz, conv_weight, conv_bias, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds, norm_weight, norm_bias,

@@ -29,46 +29,10 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
+from ._train import cast_grads, check_devices, check_tensors, empty, f32, grad_out, ptr, stream, workspace
+from ._train import strided as _strided
 
 __all__ = ["chan_attn_fn", "tattn_core_fn", "transposed_attention_forward", "transposed_attention_nhwc", "TransposedAttention"]
-
-_HALF = (torch.float16, torch.bfloat16)
-
-
-def _f32(t):
-    return t.float() if t.dtype in _HALF else t
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _ws(name, dev, *args):
-    n = int(getattr(L.lib(), name)(*args))
-    return torch.empty(max(n, 4), device=dev, dtype=torch.float32)      # the caching allocator's blocks are 512-byte aligned
-
-
-def _check(fn, named, optional=()):
-    """Types, then (by the caller) shapes, then devices: _check_types before, _check_devices after the shape tests."""
-    for name, t in named:
-        if t is None and name in optional:
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"{fn}: {name} must be a tensor (got {type(t).__name__})")
-        if t.dtype not in (torch.float32,) + _HALF:
-            raise RuntimeError(f"{fn}: {name} must be float32 / float16 / bfloat16 (got {t.dtype})")
-
-
-def _check_devices(fn, named):
-    first = named[0][1]
-    for name, t in named:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError(f"{fn}: {name} must live on the GPU (there is no CPU path)")
-        if t.device != first.device:
-            raise RuntimeError(f"{fn}: {name} lives on {t.device}, {named[0][0]} on {first.device}")
-
 
 def _check_dim(fn, C3, temperature, shapes):
     if C3 % 3:
@@ -84,18 +48,18 @@ def _check_dim(fn, C3, temperature, shapes):
 
 def _check_attn(fn, qkv, temperature):
     named = [("qkv", qkv), ("temperature", temperature)]
-    _check(fn, named)
+    check_tensors(fn, named)
     shapes = " ".join(f"{n}{tuple(t.shape)}" for n, t in named)
     if qkv.dim() != 4 or min(qkv.shape) < 1:
         raise RuntimeError(f"{fn}: inconsistent shapes {shapes} (qkv is (B, H, W, 3 dim))")
     dim = _check_dim(fn, qkv.shape[-1], temperature, shapes)
-    _check_devices(fn, named)
+    check_devices(fn, named)
     return qkv.shape[0], qkv.shape[1], qkv.shape[2], dim
 
 
 def _check_core(fn, qkv_pre, dw_weight, dw_bias, temperature):
     named = [("qkv_pre", qkv_pre), ("dw_weight", dw_weight), ("dw_bias", dw_bias), ("temperature", temperature)]
-    _check(fn, named, optional=("dw_bias",))
+    check_tensors(fn, named, optional=("dw_bias",))
     shapes = " ".join(f"{n}{tuple(t.shape)}" for n, t in named if t is not None)
     if qkv_pre.dim() != 4 or min(qkv_pre.shape) < 1:
         raise RuntimeError(f"{fn}: inconsistent shapes {shapes} (qkv_pre is (B, H, W, 3 dim))")
@@ -103,31 +67,19 @@ def _check_core(fn, qkv_pre, dw_weight, dw_bias, temperature):
     if tuple(dw_weight.shape) != (C3, 1, 3, 3) or (dw_bias is not None and tuple(dw_bias.shape) != (C3,)):
         raise RuntimeError(f"{fn}: inconsistent shapes {shapes} (dw_weight is (3 dim, 1, 3, 3), dw_bias (3 dim,) or None)")
     dim = _check_dim(fn, C3, temperature, shapes)
-    _check_devices(fn, named)
+    check_devices(fn, named)
     return qkv_pre.shape[0], qkv_pre.shape[1], qkv_pre.shape[2], dim
-
-
-def _strided(t, C3):
-    """(tensor, ld, off) for the kernels: t itself if it is a channel slice of a dense (B, H, W, ld) tensor, else a dense copy"""
-    B, H, W, _ = t.shape
-    ld = t.stride(2)
-    if t.stride() == (H * W * ld, W * ld, ld, 1) and ld >= C3 and ld % 4 == 0:
-        off = t.storage_offset() % ld
-        if off % 4 == 0 and off + C3 <= ld and (t.data_ptr() - 4 * off) % 16 == 0:
-            return t, ld, off
-    return t.contiguous(), C3, 0
 
 
 def _attn_fwd(qkv, ld, off, temp, dims):
     B, H, W, dim = dims
     dev = qkv.device
     heads = dim // 32
-    new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+    new = empty(dev)
     out, attn, ghat, nrm = new(B, H, W, dim), new(B, heads, 32, 32), new(B, heads, 32, 32), new(B, heads, 64)
-    ws = _ws("fd_chan_attn_fwd_ws_floats", dev, B, H * W, dim)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    L.call("fd_chan_attn_fwd_f32", C.c_void_p(qkv.data_ptr() - 4 * off), ld, off, _p(temp), _p(out), _p(attn), _p(ghat), _p(nrm),
-           _p(ws), B, H * W, dim, stream)
+    ws = workspace("fd_chan_attn_fwd_ws_floats", dev, B, H * W, dim)
+    L.call("fd_chan_attn_fwd_f32", C.c_void_p(qkv.data_ptr() - 4 * off), ld, off, ptr(temp), ptr(out), ptr(attn), ptr(ghat), ptr(nrm),
+           ptr(ws), B, H * W, dim, stream(dev))
     return out, attn, ghat, nrm
 
 
@@ -136,21 +88,10 @@ def _attn_bwd(qkv, ld, off, temp, attn, ghat, nrm, dout, dims):
     dev = qkv.device
     dqkv = torch.empty(B, H, W, 3 * dim, device=dev, dtype=torch.float32)
     dtemp = torch.empty(dim // 32, device=dev, dtype=torch.float32)
-    ws = _ws("fd_chan_attn_bwd_ws_floats", dev, B, H * W, dim)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    L.call("fd_chan_attn_bwd_f32", C.c_void_p(qkv.data_ptr() - 4 * off), ld, off, _p(temp), _p(attn), _p(ghat), _p(nrm), _p(dout),
-           _p(dqkv), 3 * dim, 0, _p(dtemp), _p(ws), B, H * W, dim, stream)
+    ws = workspace("fd_chan_attn_bwd_ws_floats", dev, B, H * W, dim)
+    L.call("fd_chan_attn_bwd_f32", C.c_void_p(qkv.data_ptr() - 4 * off), ld, off, ptr(temp), ptr(attn), ptr(ghat), ptr(nrm),
+           ptr(dout), ptr(dqkv), 3 * dim, 0, ptr(dtemp), ptr(ws), B, H * W, dim, stream(dev))
     return dqkv, dtemp
-
-
-def _dout(fn, dout, dims):
-    if tuple(dout.shape) != tuple(dims):
-        raise RuntimeError(f"{fn}: the gradient of the result must be {tuple(dims)} (got {tuple(dout.shape)})")
-    return _f32(dout).contiguous()
-
-
-def _cast(grads, dtypes):
-    return tuple(None if g is None else (g.to(dt) if g.dtype != dt else g) for g, dt in zip(grads, dtypes))
 
 
 class _ChanAttn(torch.autograd.Function):
@@ -158,8 +99,8 @@ class _ChanAttn(torch.autograd.Function):
     def forward(ctx, qkv, temperature):
         dims = _check_attn("chan_attn_fn", qkv, temperature)
         ctx.dtypes, ctx.tshape, ctx.dims = (qkv.dtype, temperature.dtype), temperature.shape, dims
-        qkv, ld, off = _strided(_f32(qkv), 3 * dims[3])
-        temp = _f32(temperature).reshape(-1).contiguous()
+        qkv, ld, off = _strided(f32(qkv), 3 * dims[3])
+        temp = f32(temperature).reshape(-1).contiguous()
         with torch.cuda.device(qkv.device):
             out, attn, ghat, nrm = _attn_fwd(qkv, ld, off, temp, dims)
         ctx.ld_off = (ld, off)
@@ -169,10 +110,10 @@ class _ChanAttn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         qkv, temp, attn, ghat, nrm = ctx.saved_tensors
-        dout = _dout("chan_attn_fn", dout, ctx.dims)
+        dout = grad_out("chan_attn_fn", dout, ctx.dims)
         with torch.cuda.device(qkv.device):
             dqkv, dtemp = _attn_bwd(qkv, *ctx.ld_off, temp, attn, ghat, nrm, dout, ctx.dims)
-        return _cast((dqkv, dtemp.view(ctx.tshape)), ctx.dtypes)
+        return cast_grads((dqkv, dtemp.view(ctx.tshape)), ctx.dtypes)
 
 
 class _TattnCore(torch.autograd.Function):
@@ -182,15 +123,14 @@ class _TattnCore(torch.autograd.Function):
         dims = B, H, W, dim = _check_core("tattn_core_fn", *args)
         ctx.dtypes, ctx.tshape, ctx.dims = tuple(None if t is None else t.dtype for t in args), temperature.shape, dims
         C3 = 3 * dim
-        x = _f32(qkv_pre).contiguous()
-        w9 = _f32(dw_weight).reshape(C3, 9).t().contiguous()             # [9][3 dim] tap-major, as fd_dwconv3x3 takes it
-        bias = None if dw_bias is None else _f32(dw_bias).contiguous()
-        temp = _f32(temperature).reshape(-1).contiguous()
+        x = f32(qkv_pre).contiguous()
+        w9 = f32(dw_weight).reshape(C3, 9).t().contiguous()             # [9][3 dim] tap-major, as fd_dwconv3x3 takes it
+        bias = None if dw_bias is None else f32(dw_bias).contiguous()
+        temp = f32(temperature).reshape(-1).contiguous()
         dev = x.device
         with torch.cuda.device(dev):
             qkv = torch.empty(B, H, W, C3, device=dev, dtype=torch.float32)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            L.call("fd_dwconv3x3", L.FD_F32, _p(x), C3, 0, _p(w9), _p(bias), 0, _p(qkv), C3, 0, B, H, W, C3, stream)
+            L.call("fd_dwconv3x3", L.FD_F32, ptr(x), C3, 0, ptr(w9), ptr(bias), 0, ptr(qkv), C3, 0, B, H, W, C3, stream(dev))
             out, attn, ghat, nrm = _attn_fwd(qkv, C3, 0, temp, dims)
         ctx.save_for_backward(x, qkv, w9, bias, temp, attn, ghat, nrm)
         return out
@@ -200,19 +140,18 @@ class _TattnCore(torch.autograd.Function):
         x, qkv, w9, bias, temp, attn, ghat, nrm = ctx.saved_tensors
         B, H, W, dim = ctx.dims
         C3 = 3 * dim
-        dout = _dout("tattn_core_fn", dout, ctx.dims)
+        dout = grad_out("tattn_core_fn", dout, ctx.dims)
         dev = x.device
         with torch.cuda.device(dev):
-            new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+            new = empty(dev)
             dqkv, dtemp = _attn_bwd(qkv, C3, 0, temp, attn, ghat, nrm, dout, ctx.dims)
             del dout
             dx, dw9, db = new(B, H, W, C3), new(9, C3), (None if bias is None else new(C3))
-            ws = _ws("fd_dwconv3x3_bwd_ws_floats", dev, B, H, W, C3)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            L.call("fd_dwconv3x3_bwd_f32", _p(x), C3, 0, _p(w9), _p(bias), _p(dqkv), _p(dx), C3, 0, _p(dw9), _p(db), _p(ws), B, H, W,
-                   C3, stream)
+            ws = workspace("fd_dwconv3x3_bwd_ws_floats", dev, B, H, W, C3)
+            L.call("fd_dwconv3x3_bwd_f32", ptr(x), C3, 0, ptr(w9), ptr(bias), ptr(dqkv), ptr(dx), C3, 0, ptr(dw9), ptr(db), ptr(ws),
+                   B, H, W, C3, stream(dev))
             del dqkv, ws
-        return _cast((dx, dw9.t().reshape(C3, 1, 3, 3), db, dtemp.view(ctx.tshape)), ctx.dtypes)
+        return cast_grads((dx, dw9.t().reshape(C3, 1, 3, 3), db, dtemp.view(ctx.tshape)), ctx.dtypes)
 
 
 def chan_attn_fn(qkv, temperature):

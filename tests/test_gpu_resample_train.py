@@ -217,13 +217,14 @@ def test_conv3x3_reads_a_channel_slice_in_place():
     """x = channels [32, 96) of a wider tensor (ld = 128), 64 -> 32, 15 x 13: the view reaches the kernels as it is, and its gradient
     lands in the slice of the wide tensor's gradient, zeros elsewhere"""
     from founddiff_amd import resample_train as rt
+    from founddiff_amd._train import strided
     inputs, dout = _inputs("conv3", 2, 15, 13, 64, 32, seed=77)
     ref = _grads(_ref_conv3, inputs, dout, torch.float64)
     wide = torch.full((2, 15, 13, 128), SENTINEL, device="cuda")
     wide[..., 32:96] = inputs["x"].cuda()
     wide.requires_grad_()
     view = wide[..., 32:96]
-    kept, ld, off = rt._strided(view, 64)
+    kept, ld, off = strided(view, 64)
     assert kept is view and (ld, off) == (128, 32)
     w, b = inputs["weight"].cuda().requires_grad_(), inputs["bias"].cuda().requires_grad_()
     out = rt.conv3x3_fn(view, w, b)

@@ -56,7 +56,7 @@ def test_new_kernels_use_no_scratch():
     if not shutil.which("/opt/rocm/bin/hipcc"):
         pytest.skip("no hipcc")
     from founddiff_amd import build
-    want = {"sub2x_kernel", "corr_kernel", "corr_reduce_kernel"}
+    want = {"sub2x_kernel", "tapcorr_kernelILi4ELi2ELi4ELi8ELi40E", "tapcorr_reduce_kernel"}
     for half in ("bf16", "fp16"):
         build.build(half=half)
         tab = build.resources(half).get("fd_resample_train.hip")

@@ -175,8 +175,8 @@ def test_new_kernels_use_no_scratch():
     if not shutil.which("/opt/rocm/bin/hipcc"):
         pytest.skip("no hipcc")
     from founddiff_amd import build
-    want = {"rb_sum_kernel", "gsb_sums_kernel", "gsb_coef_kernel", "gsb_param_kernel", "gsb_dh_kernel", "wgrad_kernel",
-            "wgrad_reduce_kernel"}
+    want = {"partial_sum_kernel", "gsb_sums_kernel", "gsb_coef_kernel", "gsb_param_kernel", "gsb_dh_kernel",
+            "tapcorr_kernelILi3ELi1ELi8ELi16ELi48E", "tapcorr_reduce_kernel"}
     for half in ("bf16", "fp16"):
         build.build(half=half)
         tab = build.resources(half).get("fd_resblock_train.hip")

@@ -139,10 +139,11 @@ def test_new_kernels_use_no_scratch():
         seen = set()
         for name, r in tab.items():
             assert r.get("scratch", 0) == 0, (half, name, r)
-            m = re.search(r"(sum_kernel|dwb_pre_kernel|dwb_flip_kernel|lsg_fwd_kernel|lsg_bwd_kernel|lsg_finish_kernel)", name)
+            m = re.search(r"(partial_sum_kernel|dwb_pre_kernel|dwb_flip_kernel|lsg_fwd_kernel|lsg_bwd_kernel|lsg_finish_kernel)", name)
             if m:
                 seen.add(m.group(1))
-        assert seen == {"sum_kernel", "dwb_pre_kernel", "dwb_flip_kernel", "lsg_fwd_kernel", "lsg_bwd_kernel", "lsg_finish_kernel"}, seen
+        assert seen == {"partial_sum_kernel", "dwb_pre_kernel", "dwb_flip_kernel", "lsg_fwd_kernel", "lsg_bwd_kernel",
+                        "lsg_finish_kernel"}, seen
         cs = {n: r for n, r in res["fd_cross_scan_bwd.hip"].items() if re.search(r"cs_scan_kernel|cs_xproj_kernel", n)}
         assert len(cs) == 100                       # 20 (N, R) pairs x (carry, main and x_proj in both dx layouts)
         for name, r in cs.items():
