@@ -116,6 +116,12 @@ SIGNATURES = {
     "fd_chan_attn_bwd_f32": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i64, i32, vp]),
     "fd_dwconv3x3_bwd_ws_floats": (i64, [i32, i32, i32, i32]),
     "fd_dwconv3x3_bwd_f32": (i32, [vp, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "fd_adaln_fwd_f32": (i32, [vp, vp, vp, f32, vp, vp, i32, vp, vp, i32, i64, i32, vp]),
+    "fd_adaln_bwd_ws_floats": (i64, [i32, i64, i32]),
+    "fd_adaln_bwd_f32": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i64, i32, vp]),
+    "fd_gate_res_fwd_f32": (i32, [vp, vp, vp, i32, vp, i32, i64, i32, vp]),
+    "fd_gate_res_bwd_ws_floats": (i64, [i32, i64, i32]),
+    "fd_gate_res_bwd_f32": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i64, i32, vp]),
     "fd_gn_silu_bwd_ws_floats": (i64, [i32, i64, i32, i32]),
     "fd_gn_silu_bwd_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, vp]),
     "fd_conv3x3_wgrad_ws_floats": (i64, [i32, i32, i32, i32, i32]),

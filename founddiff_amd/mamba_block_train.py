@@ -4,8 +4,13 @@
     x = x + gate_mlp * TransposedAttention(modulate(norm2(x), shift_mlp, scale_mlp))      tattn_train.transposed_attention_nhwc
 
 NCHW goes in as a permute view and comes out as a permute view, as in the reference; in between everything is (B, H, W, C).  The
-reference's two permute().contiguous() copies around its NCHW TransposedAttention do not exist here.  The two LayerNorms,
-modulate, the gates and the residual adds stay with torch.
+reference's two permute().contiguous() copies around its NCHW TransposedAttention do not exist here.  Each LayerNorm + modulate
+is one launch (adaln_train.adaln_skip_fn), each gate + residual add one launch (adaln_train.gate_residual_fn); in the backward
+the gradient that reaches x along the residual path is added inside the LayerNorm's backward pass.  Apart from the five GEMMs
+(in_proj, out_proj, qkv, project_out, adaLN_modulation) no torch op touches a full-size activation -- when x arrives as the
+permute view of a channel-last tensor, as it does from the block before it and from unet_train.  A dense NCHW x (the one-line
+binding inside the reference's own loop, the tests) costs one transposing copy on the way in, which the LayerNorm of the torch
+composition made as well.
 
 Binding for a training run:
 
@@ -17,14 +22,12 @@ state dict loads with strict=True) for code that does not import the reference.
 """
 import torch
 
+from ._train import check_tensors
+from .adaln_train import adaln_skip_fn, gate_residual_fn
 from .ss2d_train import SS2D, ss2d_forward
 from .tattn_train import TransposedAttention, transposed_attention_nhwc
 
 __all__ = ["mamba_block_forward", "MambaBlock"]
-
-
-def _modulate(x, shift, scale):
-    return x * (1 + scale[:, None, None, :]) + shift[:, None, None, :]
 
 
 def mamba_block_forward(self, x, c, t):
@@ -32,12 +35,15 @@ def mamba_block_forward(self, x, c, t):
     view of a channel-last tensor as in the reference.  Reads the reference's attribute names (norm1, mamba, norm2,
     adaLN_modulation, attn_blk, cross).  Raises RuntimeError, before anything is launched, for cross=True (a CrossAttention
     attn_blk), CPU tensors, inconsistent shapes and whatever ss2d_forward / transposed_attention_nhwc do not support (a
-    hidden_size that is not a multiple of 64 or is above 512 among them)."""
+    hidden_size that is not a multiple of 64 or is above 512 among them), and for tensors that are not float32 / float16 /
+    bfloat16 or a LayerNorm with a weight and no bias."""
     if getattr(self, "cross", False):
         raise RuntimeError("mamba_block_forward: cross=True (a CrossAttention attn_blk) is not supported")
-    for name, v in (("x", x), ("c", c), ("t", t)):
-        if not isinstance(v, torch.Tensor):
-            raise RuntimeError(f"mamba_block_forward: {name} must be a tensor (got {type(v).__name__})")
+    check_tensors("mamba_block_forward", (("x", x), ("c", c), ("t", t)))
+    for name in ("norm1", "norm2"):
+        norm = getattr(self, name)
+        if (norm.weight is None) != (norm.bias is None):
+            raise RuntimeError(f"mamba_block_forward: {name} must have both a weight and a bias or neither")
     C = self.norm1.normalized_shape[0]
     if x.dim() != 4 or x.shape[1] != C or t.dim() != 2 or t.shape[0] != x.shape[0]:
         raise RuntimeError(f"mamba_block_forward: inconsistent shapes x{tuple(x.shape)} t{tuple(t.shape)} (expected x (B, {C}, H, W), "
@@ -49,10 +55,14 @@ def mamba_block_forward(self, x, c, t):
     for name, v in (("x", x), ("c", c), ("t", t)):
         if not v.is_cuda:
             raise RuntimeError(f"mamba_block_forward: {name} must live on the GPU (there is no CPU path)")
-    x = x.permute(0, 2, 3, 1)
+    dtype = x.dtype
+    x = x.permute(0, 2, 3, 1).contiguous()
     shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp = self.adaLN_modulation(t).chunk(6, dim=1)
-    x = x + gate_msa[:, None, None, :] * ss2d_forward(self.mamba, _modulate(self.norm1(x), shift_msa, scale_msa), c)
-    x = x + gate_mlp[:, None, None, :] * transposed_attention_nhwc(self.attn_blk, _modulate(self.norm2(x), shift_mlp, scale_mlp))
+    branches = ((self.norm1, shift_msa, scale_msa, gate_msa, lambda m: ss2d_forward(self.mamba, m, c)),
+                (self.norm2, shift_mlp, scale_mlp, gate_mlp, lambda m: transposed_attention_nhwc(self.attn_blk, m)))
+    for norm, shift, scale, gate, branch in branches:
+        m, skip = adaln_skip_fn(x, norm.weight, norm.bias, shift, scale, norm.eps)
+        x = gate_residual_fn(skip, branch(m.to(dtype)), gate).to(dtype)
     return x.permute(0, 3, 1, 2)
 
 

@@ -460,6 +460,33 @@ int fd_dwconv3x3_bwd_f32(const float *x, int ld_in, int off_in, const float *wei
                          float *dx, int ld_dx, int off_dx, float *dweight, float *dbias, float *ws, int B, int H, int W, int C,
                          void *stream);
 
+/* ---- The element-wise frame of Mamba_block.forward (src/DADiff.py:477-488) for training, fp32, NHWC (fd_adaln_train.hip):
+ * LayerNorm + modulate in front of a branch, the gated residual add behind it.  x, y, out and the gradients [B,hw,C] dense;
+ * shift, scale, gate [B][ld_mod] (the chunks of adaLN_modulation's [B,6C] output, read in place: 16-byte aligned, ld_mod a
+ * multiple of 4); their gradients [B][ld_dmod], only the C columns written.  Deterministic (a workgroup owns a contiguous pixel
+ * range whose length depends on hw only, partials summed in a fixed order, no float atomics): every per-slice result is the
+ * same bits alone or in a batch; dgamma and dbeta add the slices in index order.  C % 64 == 0, C <= 512.
+ *
+ * fd_adaln_fwd_f32: out = LN(x) * (1 + scale[b]) + shift[b].  gamma, beta [C], both set or both NULL (no affine); stats
+ *   [B,hw,2] receives (mean, rstd) per pixel; centred statistics (the variance of x - mean).
+ * fd_adaln_bwd_f32: dout -> dx, dshift, dscale, dgamma, dbeta (NULL exactly when gamma is).  dres [B,hw,C] or NULL is added to
+ *   dx in the same pass: the gradient that reaches x along the residual path.  Reads dout, x, stats, dres once; dout and x are
+ *   not modified.  ws: fd_adaln_bwd_ws_floats(...) floats, 0 for an unsupported shape.
+ * fd_gate_res_fwd_f32: out = x + gate[b] * y.
+ * fd_gate_res_bwd_f32: dy = gate[b] * dout, dgate[b,c] = sum over the pixels of dout * y.  The gradient of x is dout itself and
+ *   is not written.  ws: fd_gate_res_bwd_ws_floats(...) floats, 0 for an unsupported shape.                                    */
+int fd_adaln_fwd_f32(const float *x, const float *gamma, const float *beta, float eps, const float *shift, const float *scale,
+                     int ld_mod, float *out, float *stats, int B, int64_t hw, int C, void *stream);
+int64_t fd_adaln_bwd_ws_floats(int B, int64_t hw, int C);
+int fd_adaln_bwd_f32(const float *dout, const float *x, const float *stats, const float *gamma, const float *beta,
+                     const float *scale, int ld_mod, const float *dres, float *dx, float *dshift, float *dscale, int ld_dmod,
+                     float *dgamma, float *dbeta, float *ws, int B, int64_t hw, int C, void *stream);
+int fd_gate_res_fwd_f32(const float *x, const float *y, const float *gate, int ld_mod, float *out, int B, int64_t hw, int C,
+                        void *stream);
+int64_t fd_gate_res_bwd_ws_floats(int B, int64_t hw, int C);
+int fd_gate_res_bwd_f32(const float *dout, const float *y, const float *gate, int ld_mod, float *dy, float *dgate, int ld_dmod,
+                        float *ws, int B, int64_t hw, int C, void *stream);
+
 /* ---- The backward of the reference's ResnetBlock (src/DADiff.py:139-154, 213-229, 397-430) for training, fp32, NHWC
  * (fd_resblock_train.hip): out = SiLU(GroupNorm(h)) (+ res) with h = conv3x3(x, w) + bias.  The forward is fd_conv2d(FD_F32) with
  * stats_partial, fd_gn_finalize and fd_gn_silu_apply; the gradient of res is dout itself; the gradient of x is fd_conv2d(FD_F32)
