@@ -132,11 +132,19 @@ class DAEngine:
     _GEN = 0        # every engine gets a unique generation number: captured HIP graphs are keyed on it
     probe = None    # development hook: probe(tag, tensor) after each stage (tools/drift_table.py, stage_times.py)
     hip = L.BF16    # the build of the C ABI an engine calls: the default one, or L.F16 for mode 'fp16' (__init__)
+    # The switches at the oldest dataflow's values, for a weight-less engine that skips __init__ (the kernel tests' stubs); see __init__
+    fp8, f32_split, low_latency, z_recompute, v_recompute, down_fuse = False, 0, False, 0, False, False
+    _tab_S = _mod_tab_shape = None      # the adaLN table of a sampling loop (time_table_prepare, time_cond_table)
 
     @property
     def half(self):
         """16-bit storage (bfloat16, or binary16 on the second build): the fused kernel set"""
         return self.tdt in _HALF
+
+    @property
+    def scan_dt(self):
+        """`dt` with the FD_OPT_* bits of this engine: the dtype argument of the kernels whose plan depends on them"""
+        return self.dt | (L.FD_OPT_LOW_LATENCY if self.low_latency else 0) | (L.FD_OPT_F32_SPLIT if self.f32_split else 0)
 
     def __init__(self, state_dict, prefix="", device="cuda", mode="bf16", low_latency=False):
         self.hip = L.F16 if mode == "fp16" else L.BF16    # which build of the C ABI this engine calls (founddiff_amd/_lib.py)
@@ -147,16 +155,14 @@ class DAEngine:
             raise ValueError(f"mode must be 'fp32', 'fp32s', 'bf16', 'fp16' or 'fp8', got {mode!r}")
         self.mode = mode
         self.dt, self.tdt = _T[mode]
-        self.fp8 = mode == "fp8"
-        self.f32_split = int(mode == "fp32s")
+        self.fp8, self.f32_split = mode == "fp8", int(mode == "fp32s")
         # low_latency: the kernel set for ONE slice at a time (the reference's Trainer.test loop).  The default set is
         # chosen for throughput at a batch that fills the chip; both are functions of the image size only.
         self.low_latency = bool(low_latency)
-        self.scan_dt = self.dt | (L.FD_OPT_LOW_LATENCY if low_latency else 0) | (L.FD_OPT_F32_SPLIT if mode == "fp32s" else 0)
-        # z gate of SS2D recomputed inside out_proj instead of written by in_proj and read back (mamba_block); 0 = round-3 dataflow
+        # z gate of SS2D recomputed inside out_proj instead of written by in_proj and read back (_ss2d); 0 = round-3 dataflow
         # (development: 64 = only in the 64-channel blocks)
         self.z_recompute = int(_dev("FOUNDDIFF_Z_RECOMPUTE", "1"))
-        # v of the 64-channel TransposedAttention recomputed inside the kernel that applies Weff (mamba_block); 0 = stored v
+        # v of the 64-channel TransposedAttention recomputed inside the kernel that applies Weff (_chan_attn); 0 = stored v
         self.v_recompute = _dev("FOUNDDIFF_V_RECOMPUTE", "1") == "1"
         # GroupNorm apply of the down-path blocks fused with the 4x4 / stride-2 convolution behind them (_down); 0 = two passes
         self.down_fuse = _dev("FOUNDDIFF_DOWN_FUSE", "1") == "1"
@@ -173,7 +179,7 @@ class DAEngine:
         return t.detach().float().contiguous().to(self.dev)
 
     def _convw(self, w, b=None, cin_pad=None, up2x=False):
-        return ConvW(w, b, self.dev, self.tdt, cin_pad, fp8=getattr(self, "fp8", False), up2x=up2x, split=bool(getattr(self, "f32_split", 0)))
+        return ConvW(w, b, self.dev, self.tdt, cin_pad, fp8=self.fp8, up2x=up2x, split=bool(self.f32_split))
 
     def _pack_res(self, s):
         r = {"conv": self._convw(ws_standardize(s["block1.proj.weight"]), s["block1.proj.bias"]),
@@ -187,7 +193,7 @@ class DAEngine:
         """init_conv weight (Cout, C<=3, 7, 7) -> bf16 [Cout][7 kh][8 kw][4 c] (include/founddiff_hip.h:
         fd_init_conv7): one filter row = one K32 MFMA step."""
         co, c = w.shape[0], w.shape[1]
-        if getattr(self, "f32_split", 0) and c == 2 and tuple(w.shape[2:]) == (7, 7):
+        if self.f32_split and c == 2 and tuple(w.shape[2:]) == (7, 7):
             # fp32s engine (fd_init_conv7_f32s): bf16(w) in all four slots (planes + their rounding residuals) and the
             # weights' own residual bf16(w - bf16(w)) in slots 0, 1 -- the three terms of a split-bf16 product
             wf = w.detach().float().permute(0, 2, 3, 1)
@@ -428,30 +434,28 @@ class DAEngine:
         p.ln_gamma, p.ln_beta = ptr(ln_gamma), ptr(ln_beta)
         p.ln_shift, p.ln_scale, p.ln_ld = ptr(ln_shift), ptr(ln_scale), ln_ld
         p.ln_z, p.ln_ldz, p.ln_offz = ptr(ln_z), ln_ldz, ln_offz
-        p.f32_split = getattr(self, "f32_split", 0)
+        p.f32_split = self.f32_split
         if zre is not None:      # PRO_LN_GATE_ZRE: z = SiLU(w . LNmod(res)) recomputed in the operand load
             p.zre_w, p.zre_gamma, p.zre_beta = ptr(zre["w"]), ptr(zre.get("gamma")), ptr(zre.get("beta"))
             p.zre_shift, p.zre_scale, p.zre_ld, p.zre_eps = ptr(zre["shift"]), ptr(zre["scale"]), zre["ld"], zre["eps"]
         if fin is not None:      # EPI_GNSILU_ADD_FINAL: final_conv (+ DDIM update) in the epilogue
             p.fin_w, p.fin_b, p.fin_out = fin["w"].data_ptr(), float(fin["b"]), fin["out"].data_ptr()
             p.fin_mode, p.fin_last = int(fin.get("mode", 0)), int(fin.get("last", 0))
-            p.fin_img = fin["img"].data_ptr() if fin.get("img") is not None else None
-            p.fin_xin = fin["xin"].data_ptr() if fin.get("xin") is not None else None
+            p.fin_img, p.fin_xin = ptr(fin.get("img")), ptr(fin.get("xin"))
             p.fin_alpha = float(fin.get("alpha", 0.0))
-        if weight is None and cw is not None and getattr(cw, "w8", None) is not None:
-            p.weight_f8, p.w_scale, p.act_scale = cw.w8.data_ptr(), cw.ws.data_ptr(), FP8_ACT_SCALE
-        # (the one-slice kernel set asks for one workgroup per (tile, parity class) -- `upsample` = 2: a low-resolution tile grid
-        #  alone is 64..256 workgroups for a lone 512x512 slice, 150.8 against 146.3 ms per 50-step slice with the 9-tap form,
-        #  profiles/r05/latency_b1_sweep.txt; any split gives the same bits)
-        if weight is None and cw is not None and getattr(cw, "w_hi", None) is not None and KH == 3:
-            p.weight_split_hi, p.weight_split_lo = cw.w_hi.data_ptr(), cw.w_lo.data_ptr()
-        if upsample and weight is None and cw is not None and getattr(cw, "w_up_hi", None) is not None:
-            p.weight_up2x_split_hi, p.weight_up2x_split_lo = cw.w_up_hi.data_ptr(), cw.w_up_lo.data_ptr()
-            if getattr(self, "low_latency", False):
-                p.upsample = 2
-        if upsample and weight is None and cw is not None and getattr(cw, "w_up", None) is not None:
-            p.weight_up2x = cw.w_up.data_ptr()
-            if getattr(self, "low_latency", False):
+        if weight is None and cw is not None:        # the other forms ConvW packed this weight in
+            if cw.w8 is not None:
+                p.weight_f8, p.w_scale, p.act_scale = cw.w8.data_ptr(), cw.ws.data_ptr(), FP8_ACT_SCALE
+            if cw.w_hi is not None and KH == 3:
+                p.weight_split_hi, p.weight_split_lo = cw.w_hi.data_ptr(), cw.w_lo.data_ptr()
+            if upsample and cw.w_up_hi is not None:
+                p.weight_up2x_split_hi, p.weight_up2x_split_lo = cw.w_up_hi.data_ptr(), cw.w_up_lo.data_ptr()
+            if upsample and cw.w_up is not None:
+                p.weight_up2x = cw.w_up.data_ptr()
+            # (the one-slice kernel set asks for one workgroup per (tile, parity class) -- `upsample` = 2: a low-resolution tile grid
+            #  alone is 64..256 workgroups for a lone 512x512 slice, 150.8 against 146.3 ms per 50-step slice with the 9-tap form,
+            #  profiles/r05/latency_b1_sweep.txt; any split gives the same bits)
+            if upsample and self.low_latency and (cw.w_up_hi is not None or cw.w_up is not None):
                 p.upsample = 2
         if probe == "kid":          # which kernel would run (include/founddiff_hip.h: fd_conv_kernel_id)
             return int(self.hip.lib().fd_conv_kernel_id(C.byref(p)))
@@ -489,20 +493,26 @@ class DAEngine:
         return out
 
     # ------------------------------------------------------------------ blocks
-    def res_block(self, r, in0, c0, in1, c1, B, H, W, tag, defer_apply=False):
-        """DADiff ResnetBlock: conv3x3(WS)+GN+SiLU, + res_conv(x) or x (src/DADiff.py:397-430).  defer_apply (identity
-        residual only): stop after the GroupNorm statistics and return (h, mean_rstd, out buffer) -- the caller fuses the
-        apply pass into its consumer (_down: fd_gn_apply_down4x4)."""
-        cw = r["conv"]
+    def _conv3_gn(self, cw, in0, B, H, W, tag, launch=True, **kw):
+        """3x3 convolution with GroupNorm partial sums -> fd_gn_finalize: (raw convolution output, mean / rstd of the 8 groups).
+        launch=False: the two buffers only, for a caller that probes their consumer before it commits to them (_tail)."""
         Co = cw.Cout
-        hw = H * W
         mt = self.hip.lib().fd_conv_mtiles(H, W)
         hraw = self._b("res_h", (B, H, W, Co))
         part = self._b("gn_part", (B, mt, Co, 2), torch.float32)
         mr = self._b("gn_mr", (B, 8, 2), torch.float32)
-        self.conv(cw, in0, B, H, W, hraw, c0=c0, in1=in1, c1=c1, stats=part)
-        self._pr(tag + ".conv3", hraw)
-        self.hip.call("fd_gn_finalize", _p(part), B, mt, Co, 8, hw, 1e-5, _p(mr), self.stream)
+        if launch:
+            self.conv(cw, in0, B, H, W, hraw, stats=part, **kw)
+            self._pr(tag + ".conv3", hraw)
+            self.hip.call("fd_gn_finalize", _p(part), B, mt, Co, 8, H * W, 1e-5, _p(mr), self.stream)
+        return hraw, mr
+
+    def res_block(self, r, in0, c0, in1, c1, B, H, W, tag, defer_apply=False):
+        """DADiff ResnetBlock: conv3x3(WS)+GN+SiLU, + res_conv(x) or x (src/DADiff.py:397-430).  defer_apply (identity
+        residual only): stop after the GroupNorm statistics and return (h, mean_rstd, out buffer) -- the caller fuses the
+        apply pass into its consumer (_down: fd_gn_apply_down4x4)."""
+        Co = r["conv"].Cout
+        hraw, mr = self._conv3_gn(r["conv"], in0, B, H, W, tag, c0=c0, in1=in1, c1=c1)
         out = self._b(tag, (B, H, W, Co))
         if defer_apply:
             assert r["res"] is None and in1 is None
@@ -513,198 +523,190 @@ class DAEngine:
         else:
             assert in1 is None
             self.hip.call("fd_gn_silu_apply", self.dt, _p(hraw), _p(mr), _p(r["gamma"]), _p(r["beta"]), _p(in0), _p(out),
-                   B, hw, Co, 8, self.stream)
+                   B, H * W, Co, 8, self.stream)
         self._pr(tag, out)
         return out
 
     def mamba_block(self, m, x, B, H, W, tag):
         """adaLN-gated SS2D + channel attention (src/DADiff.py:477-488)."""
-        Cc, D, N, R, CD = m["C"], m["D"], m["N"], m["R"], m["CD"]
-        hw = H * W
-        s = self.stream
-        mod = self.mod_all
-        ml = self.mod_total
-        mo = m["mod_off"]
-        f4 = 4  # bytes per float
-        mp = lambda k: C.c_void_p(mod.data_ptr() + (mo + k * Cc) * f4)
-        # --- SS2D branch.  Where the library's streaming row-GEMM can run the projection (bf16,
-        # high-resolution levels) the LayerNorm+modulate / out_norm*z+local producers are fused into
-        # its operand load; otherwise they run as separate row kernels.
-        xz = self._b("xz", (B, H, W, 2 * D))
-        ln1 = dict(prologue=L.PRO_LN_MOD, ln_gamma=m["n1w"], ln_beta=m["n1b"], ln_eps=1e-5, ln_shift=mp(0),
-                   ln_scale=mp(1), ln_ld=ml)
-        xc = self._b("xc", (B, H, W, D))
-        fused = bool(self.hip.lib().fd_pw_dw3x3_ok(getattr(self, 'scan_dt', self.dt), Cc, D, D, H, W))      # (low latency: C = 128 unfused)
-        # out_proj's operands (decided here: whether in_proj has to write z at all depends on them)
-        y = self._b("scan_y", (B, H, W, D))
-        x1 = self._b(tag + ".x1", (B, H, W, Cc))
-        loc = C.c_void_p(self.local_all.data_ptr() + m["loc_off"] * f4)
+        s, mod0, c4 = self.stream, self.mod_all.data_ptr() + 4 * m["mod_off"], 4 * m["C"]
+        mp = lambda k: C.c_void_p(mod0 + k * c4)         # adaLN vector k of this block (shift, scale, gate of either branch) in mod_all's rows
+        x1 = self._ss2d(m, x, B, H, W, tag, s, mp)
+        return self._chan_attn(m, x1, B, H, W, tag, s, mp)
+
+    def _ss2d(self, m, x, B, H, W, tag, s, mp):
+        """x1 = x + gate * SS2D(LN-modulate(x)) (src/emamba2.py:713).  Three stages -- in_proj + conv2d, the scan, out_proj -- each
+        with one choice, all made from the library's plan queries before the first launch."""
+        Cc, D, N, R, CD, ip, op = m["C"], m["D"], m["N"], m["R"], m["CD"], m["in_proj"], m["out_proj"]
+        hw, ml, lib, sdt = H * W, self.mod_total, self.hip.lib(), self.scan_dt
+        xz, xc = self._b("xz", (B, H, W, 2 * D)), self._b("xc", (B, H, W, D))
+        y, x1 = self._b("scan_y", (B, H, W, D)), self._b(tag + ".x1", (B, H, W, Cc))
+        loc = C.c_void_p(self.local_all.data_ptr() + m["loc_off"] * 4)
+        # Where the library's streaming row-GEMM can run a projection (bf16, high-resolution levels) the LayerNorm+modulate /
+        # out_norm*z+local producers are fused into its operand load; otherwise they run as separate row kernels.
+        ln1 = dict(prologue=L.PRO_LN_MOD, ln_gamma=m["n1w"], ln_beta=m["n1b"], ln_eps=1e-5, ln_shift=mp(0), ln_scale=mp(1), ln_ld=ml)
+        xonly = dict(epi=L.EPI_SILU_SPLIT, split=D, Cout=D, ldo=2 * D)    # in_proj restricted to its x half (rows 0 .. D-1), z columns of xz untouched
         ep1 = dict(epi=L.EPI_GATE_RES, res=x, gate=mp(2), gate_ld=ml)
-        lng = dict(prologue=L.PRO_LN_GATE, ln_gamma=m["onw"], ln_beta=m["onb"], ln_eps=1e-5, ln_shift=loc,
-                   ln_ld=self.loc_total, ln_z=xz, ln_ldz=2 * D, ln_offz=D)
+        onorm = dict(ln_gamma=m["onw"], ln_beta=m["onb"], ln_eps=1e-5, ln_shift=loc, ln_ld=self.loc_total)
+        lng = dict(prologue=L.PRO_LN_GATE, ln_z=xz, ln_ldz=2 * D, ln_offz=D, **onorm)
         # z recomputed inside out_proj from the block input it reads anyway as its residual (fd_gemm_rows.hip:
         # gemm_rows_zre_kernel): the fused in_proj then writes the depthwise half only and z never exists in HBM
-        lngz = dict(prologue=L.PRO_LN_GATE_ZRE, ln_gamma=m["onw"], ln_beta=m["onb"], ln_eps=1e-5, ln_shift=loc,
-                    ln_ld=self.loc_total,
-                    zre=dict(w=C.c_void_p(m["in_proj"].w.data_ptr() + D * Cc * m["in_proj"].w.element_size()),
+        lngz = dict(prologue=L.PRO_LN_GATE_ZRE, **onorm,
+                    zre=dict(w=C.c_void_p(ip.w.data_ptr() + D * Cc * ip.w.element_size()),
                              gamma=m["n1w"], beta=m["n1b"], shift=mp(0), scale=mp(1), ld=ml, eps=1e-5))
-        xonly = dict(Cout=D, ldo=2 * D)                  # in_proj restricted to its x half (rows 0 .. D-1), z columns of xz untouched
-        # fp32s engine (fp32 storage, split-bf16 contractions): its own fused LN -> in_proj -> conv2d kernel (fd_pwdw32.hip)
-        f32s = bool(getattr(self, "f32_split", 0))
-        fused32 = f32s and m["in_proj"].w_hi is not None and bool(self.hip.lib().fd_pw_dw3x3_f32_ok(self.dt, Cc, D, H, W))
-        zre = (getattr(self, "z_recompute", 0) in (1, Cc) and self.conv(m["out_proj"], y, B, H, W, x1, probe=True, **ep1, **lngz)
-               and (fused32 or (bool(self.hip.lib().fd_pw_dw3x3_ok(getattr(self, 'scan_dt', self.dt), Cc, D, 0, H, W)) if fused else
-                                self.conv(m["in_proj"], x, B, H, W, xz, epi=L.EPI_SILU_SPLIT, split=D, probe=True, **ln1, **xonly))))
-        fused32 = fused32 and zre            # (the fp32 kernel writes the depthwise half only: z has to be recomputed)
-        if fused32:
-            self.hip.call("fd_pw_dw3x3_f32", _p(x), Cc, 0, Cc, _p(m["n1w"]), _p(m["n1b"]), 1e-5, mp(0), mp(1), ml, _p(m["in_proj"].w_hi), _p(m["in_proj"].w_lo), D,
+
+        # --- decide.  LN+modulate -> in_proj -> conv2d+SiLU in one kernel: the bf16 one, or the fp32s engine's own (fp32 storage,
+        # split-bf16 contractions, fd_pwdw32.hip), which writes the depthwise half only
+        fused = bool(lib.fd_pw_dw3x3_ok(sdt, Cc, D, D, H, W))                   # (low latency: C = 128 unfused)
+        fused32 = bool(self.f32_split and ip.w_hi is not None and lib.fd_pw_dw3x3_f32_ok(self.dt, Cc, D, H, W))
+        # zre: out_proj must take the recompute prologue, and in_proj must be able to leave z unwritten
+        zre = self.z_recompute in (1, Cc) and self.conv(op, y, B, H, W, x1, probe=True, **ep1, **lngz)
+        if zre and not fused32:
+            zre = bool(lib.fd_pw_dw3x3_ok(sdt, Cc, D, 0, H, W)) if fused else self.conv(ip, x, B, H, W, xz, probe=True, **ln1, **xonly)
+        # ("rows_x": the row-GEMM on in_proj's x half alone; "unfused": _ln_conv1x1's three ways, then the depthwise by itself)
+        in_path = "fused32" if fused32 and zre else "fused" if fused else "rows_x" if zre else "unfused"
+        # x_proj inside the scan's first phase (one workgroup per chunk at d_inner <= 256): no separate pass over xc
+        xproj_in_scan = bool(lib.fd_selective_scan_plan(sdt, D, N, R, H, W))
+        out_path = "zre" if zre else "ln_gate" if self.conv(op, y, B, H, W, x1, probe=True, **ep1, **lng) else "ln_gate_gemm"
+
+        # --- in_proj + conv2d -> xc (and z in xz[..., D:] unless it is recomputed)
+        if in_path == "fused32":
+            self.hip.call("fd_pw_dw3x3_f32", _p(x), Cc, 0, Cc, _p(m["n1w"]), _p(m["n1b"]), 1e-5, mp(0), mp(1), ml, _p(ip.w_hi), _p(ip.w_lo), D,
                    _p(m["dw_w"]), _p(m["dw_b"]), 1, _p(xc), D, 0, B, H, W, s)
-        elif fused:
-            # LN+modulate -> in_proj -> conv2d+SiLU (x half) / SiLU (z half) in one pass: the x half of
-            # in_proj's output never exists in HBM (xz[..., :D] stays unwritten, z lands in xz[..., D:])
-            self.hip.call("fd_pw_dw3x3", self.dt, _p(x), Cc, 0, Cc, _p(m["n1w"]), _p(m["n1b"]), 1e-5, mp(0), mp(1), ml,
-                   _p(m["in_proj"].w), D, _p(m["dw_wm"]), _p(m["dw_b"]), 1, _p(xc), D, 0,
-                   0 if zre else D, None if zre else _p(xz), 2 * D, D, B, H, W, s)
-        elif zre:
-            self.conv(m["in_proj"], x, B, H, W, xz, epi=L.EPI_SILU_SPLIT, split=D, **ln1, **xonly)
-        elif self.conv(m["in_proj"], x, B, H, W, xz, epi=L.EPI_SILU_SPLIT, split=D, probe=True, **ln1):
-            self.conv(m["in_proj"], x, B, H, W, xz, epi=L.EPI_SILU_SPLIT, split=D, **ln1)
-        elif getattr(self, "f32_split", 0) and self.conv_cols(m["in_proj"], x, B, H, W, xz, 2 * D, 2, split=D, **ln1):
-            pass                                          # fp32s, C = 128: the x half and the z half as two row-GEMM launches
+        elif in_path == "fused":
+            # conv2d+SiLU (x half) / SiLU (z half) in one pass: the x half of in_proj's output never exists in HBM
+            # (xz[..., :D] stays unwritten, z lands in xz[..., D:])
+            self.hip.call("fd_pw_dw3x3", self.dt, _p(x), Cc, 0, Cc, _p(m["n1w"]), _p(m["n1b"]), 1e-5, mp(0), mp(1), ml, _p(ip.w), D,
+                   _p(m["dw_wm"]), _p(m["dw_b"]), 1, _p(xc), D, 0, 0 if zre else D, None if zre else _p(xz), 2 * D, D, B, H, W, s)
+        elif in_path == "rows_x":
+            self.conv(ip, x, B, H, W, xz, **ln1, **xonly)
         else:
-            xm = self._b("xm", (B, H, W, Cc))
-            self.hip.call("fd_ln_modulate", self.dt, _p(x), _p(m["n1w"]), _p(m["n1b"]), 1e-5, mp(0), mp(1), ml, _p(xm),
-                   B, hw, Cc, s)
-            self.conv(m["in_proj"], xm, B, H, W, xz, epi=L.EPI_SILU_SPLIT, split=D)
-        if not fused and not fused32:
+            self._ln_conv1x1(ip, x, B, H, W, xz, 2, ln1, split=D)
+        if in_path not in ("fused32", "fused"):
             self.hip.call("fd_dwconv3x3", self.dt, _p(xz), 2 * D, 0, _p(m["dw_w"]), _p(m["dw_b"]), 1, _p(xc), D, 0,
                    B, H, W, D, s)
         self._pr(tag + ".xc", xc)
         if not zre:
             self._pr(tag + ".z", xz[..., D:])
-        # odd H / W: the four sub-grids are those of the image zero-padded to even sizes (src/emamba2.py:191-199);
-        # the x_proj gather zero-fills the positions outside the image, the scan treats them as padding
+
+        # --- x_proj + scan -> y.  Odd H / W: the four sub-grids are those of the image zero-padded to even sizes
+        # (src/emamba2.py:191-199); the x_proj gather zero-fills the positions outside the image, the scan treats them as padding
         H2, W2 = (H + 1) // 2, (W + 1) // 2
         Lq = H2 * W2
         xdbl = self._b("xdbl", (4, B, Lq, CD), torch.float32)
-        nws = self.hip.lib().fd_scan_ws_floats(B, H, W, D, N)
-        ws = self._b("scan_ws", (nws,), torch.float32)
-        if self.hip.lib().fd_selective_scan_plan(getattr(self, 'scan_dt', self.dt), D, N, R, H, W):
-            # x_proj inside the scan's first phase (one workgroup per chunk at d_inner <= 256): no separate pass over xc
-            self.hip.call("fd_selective_scan_xproj", getattr(self, "scan_dt", self.dt), _p(xc), _p(m["x_proj"]), _p(xdbl), _p(m["dtw"]), _p(m["dtb"]),
+        ws = self._b("scan_ws", (lib.fd_scan_ws_floats(B, H, W, D, N),), torch.float32)
+        if xproj_in_scan:
+            self.hip.call("fd_selective_scan_xproj", sdt, _p(xc), _p(m["x_proj"]), _p(xdbl), _p(m["dtw"]), _p(m["dtb"]),
                    _p(m["A"]), _p(m["Ds"]), _p(y), _p(ws), B, H, W, D, N, R, s)
             self._pr(tag + ".xdbl", xdbl)
         else:
-            self.conv(None, xc, B, H, W, xdbl, c0=D, weight=m["x_proj"], bias=None, Cout=CD, KH=1, KW=1, stride=2,
-                      pad=0, ndir=4, w_dir_stride=CD * D, out_dir_stride=B * Lq * CD, out_f32=True,
-                      OH=H2, OW=W2)
+            self.conv(None, xc, B, H, W, xdbl, c0=D, weight=m["x_proj"], bias=None, Cout=CD, KH=1, KW=1, stride=2, pad=0,
+                      ndir=4, w_dir_stride=CD * D, out_dir_stride=B * Lq * CD, out_f32=True, OH=H2, OW=W2)
             self._pr(tag + ".xdbl", xdbl)
-            self.hip.call("fd_selective_scan", getattr(self, "scan_dt", self.dt), _p(xc), _p(xdbl), _p(m["dtw"]), _p(m["dtb"]), _p(m["A"]),
+            self.hip.call("fd_selective_scan", sdt, _p(xc), _p(xdbl), _p(m["dtw"]), _p(m["dtb"]), _p(m["A"]),
                    _p(m["Ds"]), _p(y), _p(ws), B, H, W, D, N, R, s)
         self._pr(tag + ".y", y)
-        if zre:
-            self.conv(m["out_proj"], y, B, H, W, x1, **ep1, **lngz)
-        elif self.conv(m["out_proj"], y, B, H, W, x1, probe=True, **ep1, **lng):
-            self.conv(m["out_proj"], y, B, H, W, x1, **ep1, **lng)
+
+        # --- out_norm * z + local -> out_proj -> gated residual -> x1
+        if out_path != "ln_gate_gemm":
+            self.conv(op, y, B, H, W, x1, **ep1, **(lngz if out_path == "zre" else lng))
         else:
             yz = self._b("yz", (B, H, W, D))
             self.hip.call("fd_ln_gate", self.dt, _p(y), _p(m["onw"]), _p(m["onb"]), 1e-5, _p(xz), 2 * D, D, loc,
                    self.loc_total, _p(yz), B, hw, D, s)
-            self.conv(m["out_proj"], yz, B, H, W, x1, **ep1)
+            self.conv(op, yz, B, H, W, x1, **ep1)
         self._pr(tag + ".x1", x1)
-        # --- channel attention branch
+        return x1
+
+    def _chan_attn(self, m, x1, B, H, W, tag, s, mp):
+        """x2 = x1 + gate * TransposedAttention(LN-modulate(x1)) (src/DADiff.py:263-290).  One of five routes produces the Gram partials
+        of q k^T with the L2 norms and stores v or leaves it to be recomputed; one tail makes Weff of them and applies it to v."""
+        Cc, qw, hw, ml, lib, gdt = m["C"], m["qkv"], H * W, self.mod_total, self.hip.lib(), self.scan_dt
         ln2 = dict(prologue=L.PRO_LN_MOD, ln_eps=1e-6, ln_shift=mp(3), ln_scale=mp(4), ln_ld=ml)
-        if (f32s and m["qkv"].w_hi is not None and self.hip.lib().fd_pw_dw3x3_gram_f32_ok(self.dt, Cc, H, W)
-                and self.hip.lib().fd_pw_dw3x3_proj_f32_ok(self.dt, Cc, H, W)):
-            # fp32s: q, k -> depthwise -> Gram + norms in one pass over x1, then v -> depthwise -> Weff -> gated residual in
-            # another: q, k, v and the attention output never reach HBM (fd_pwdw32.hip)
-            nblk = self.hip.lib().fd_pw_dw3x3_gram_f32_nblk(H, W)
-            part = self._b("gram", (B, m["heads"], nblk, 1024 + 64), torch.float32)
-            self.hip.call("fd_pw_dw3x3_gram_f32", _p(x1), Cc, 0, Cc, None, None, 1e-6, mp(3), mp(4), ml, _p(m["qkv"].w_hi), _p(m["qkv"].w_lo), _p(m["qdw_w"]),
-                   3 * Cc, _p(part), B, H, W, s)
-            weff = self._b("weff", (B, Cc, Cc))
-            self.hip.call("fd_chan_attn_weff", self.dt, _p(part), nblk, _p(m["temp"]), _p(m["wproj"]), _p(weff), B, Cc, s)
-            self._pr(tag + ".weff", weff)
-            x2 = self._b(tag + ".x2", (B, H, W, Cc))
-            wvh, wvl = (C.c_void_p(t.data_ptr() + 2 * Cc * Cc * t.element_size()) for t in (m["qkv"].w_hi, m["qkv"].w_lo))
-            self.hip.call("fd_pw_dw3x3_proj_f32", _p(x1), Cc, 0, Cc, None, None, 1e-6, mp(3), mp(4), ml, wvh, wvl, _p(m["qdw_w_v"]), Cc,
-                   _p(weff), mp(5), ml, _p(x2), Cc, 0, B, H, W, s)
-            self._pr(tag, x2)
-            return x2
-        if self.hip.lib().fd_pw_dw3x3_gram_ok(self.dt, Cc, H, W):
-            # qkv -> qkv_dwconv -> L2 norms + q k^T in one pass: q and k never reach HBM, only v and one Gram
-            # partial per workgroup do (fd_pwdw.hip: pwdw_gram_kernel)
-            gdt = getattr(self, 'scan_dt', self.dt)          # carries FD_OPT_LOW_LATENCY: tiles per workgroup of the Gram kernel
-            nblk = self.hip.lib().fd_pw_dw3x3_gram_nblk_opts(gdt, H, W)
+
+        # --- decide the route, with the number of Gram partials per head its kernel writes; `v` = (tensor, row stride, channel
+        # offset) of the stored v, None = the tail recomputes it
+        if (self.f32_split and qw.w_hi is not None and lib.fd_pw_dw3x3_gram_f32_ok(self.dt, Cc, H, W)
+                and lib.fd_pw_dw3x3_proj_f32_ok(self.dt, Cc, H, W)):
+            route, nblk, v = "gram32", lib.fd_pw_dw3x3_gram_f32_nblk(H, W), None
+        elif lib.fd_pw_dw3x3_gram_ok(self.dt, Cc, H, W):
             # v recomputed where it is consumed (fd_pw_dw3x3_proj: LN -> W_v -> depthwise -> Weff -> gated residual in one
             # pass over x1): the Gram kernel then runs q and k only and v never reaches HBM
-            vre = getattr(self, "v_recompute", False) and bool(self.hip.lib().fd_pw_dw3x3_proj_ok(gdt, Cc, H, W))
-            vbuf = None if vre else self._b("attn_v", (B, H, W, Cc))
-            part = self._b("gram", (B, m["heads"], nblk, 1024 + 64), torch.float32)
-            self.hip.call("fd_pw_dw3x3_gram", gdt, _p(x1), Cc, 0, Cc, None, None, 1e-6, mp(3), mp(4), ml,
-                   _p(m["qkv"].w), _p(m["qdw_wm"]), _p(vbuf) if vbuf is not None else None, Cc, 0, _p(part), B, H, W, s)
-            if not vre:
-                self._pr(tag + ".qkv2", vbuf)
-            weff = self._b("weff", (B, Cc, Cc))
-            self.hip.call("fd_chan_attn_weff", self.dt, _p(part), nblk, _p(m["temp"]), _p(m["wproj"]), _p(weff), B, Cc, s)
-            self._pr(tag + ".weff", weff)
-            x2 = self._b(tag + ".x2", (B, H, W, Cc))
-            if vre:
-                wv = C.c_void_p(m["qkv"].w.data_ptr() + 2 * Cc * Cc * m["qkv"].w.element_size())
-                self.hip.call("fd_pw_dw3x3_proj", gdt, _p(x1), Cc, 0, Cc, None, None, 1e-6, mp(3), mp(4), ml, wv, _p(m["qdw_wm_v"]),
-                       _p(weff), mp(5), ml, _p(x2), Cc, 0, B, H, W, s)
-                self._pr(tag, x2)
-                return x2
-            self.conv(None, vbuf, B, H, W, x2, c0=Cc, ld0=Cc, off0=0, weight=weff, w_batch_stride=Cc * Cc,
-                      bias=None, Cout=Cc, KH=1, KW=1, epi=L.EPI_GATE_RES, res=x1, gate=mp(5), gate_ld=ml)
-            self._pr(tag, x2)
-            return x2
-        qkv2 = self._b("qkv2", (B, H, W, 3 * Cc))
-        if self.hip.lib().fd_pw_dw3x3_ok(self.dt, Cc, 3 * Cc, 0, H, W):
-            self.hip.call("fd_pw_dw3x3", self.dt, _p(x1), Cc, 0, Cc, None, None, 1e-6, mp(3), mp(4), ml,
-                   _p(m["qkv"].w), 3 * Cc, _p(m["qdw_wm"]), None, 0, _p(qkv2), 3 * Cc, 0,
-                   0, None, 0, 0, B, H, W, s)
+            vre = self.v_recompute and lib.fd_pw_dw3x3_proj_ok(gdt, Cc, H, W)
+            route, nblk, v = "gram", lib.fd_pw_dw3x3_gram_nblk_opts(gdt, H, W), None if vre else (self._b("attn_v", (B, H, W, Cc)), Cc, 0)
         else:
-            qkv = self._b("qkv", (B, H, W, 3 * Cc))
-            if self.conv(m["qkv"], x1, B, H, W, qkv, probe=True, **ln2):
-                self.conv(m["qkv"], x1, B, H, W, qkv, **ln2)
-            elif getattr(self, "f32_split", 0) and self.conv_cols(m["qkv"], x1, B, H, W, qkv, 3 * Cc, 3, **ln2):
-                pass                                      # fp32s, C = 128: q, k, v as three row-GEMM launches
+            qkv2 = self._b("qkv2", (B, H, W, 3 * Cc))     # (held on the "qkv_gram" route too, which never writes it)
+            if lib.fd_pw_dw3x3_ok(self.dt, Cc, 3 * Cc, 0, H, W):
+                route, nblk, v = "pwdw", lib.fd_chan_attn_nblk(hw), (qkv2, 3 * Cc, 2 * Cc)
+            elif lib.fd_dwconv_gram_ok(self.dt, Cc, H, W):
+                route, nblk, v = "qkv_gram", lib.fd_dwconv_gram_nblk(H, W), (self._b("attn_v", (B, H, W, Cc)), Cc, 0)
             else:
-                xm2 = self._b("xm", (B, H, W, Cc))
-                self.hip.call("fd_ln_modulate", self.dt, _p(x1), None, None, 1e-6, mp(3), mp(4), ml, _p(xm2), B, hw, Cc, s)
-                self.conv(m["qkv"], xm2, B, H, W, qkv)
-            if self.hip.lib().fd_dwconv_gram_ok(self.dt, Cc, H, W):
-                # qkv_dwconv of q and k straight into the Gram (fd_pwdw.hip: dwconv_gram_kernel): only v is written
-                nblk = self.hip.lib().fd_dwconv_gram_nblk(H, W)
-                vbuf = self._b("attn_v", (B, H, W, Cc))
-                part = self._b("gram", (B, m["heads"], nblk, 1024 + 64), torch.float32)
-                self.hip.call("fd_dwconv3x3", self.dt, _p(qkv), 3 * Cc, 2 * Cc, _p(m["qdw_w_v"]), None, 0, _p(vbuf), Cc, 0,
-                       B, H, W, Cc, s)
-                self.hip.call("fd_dwconv_gram", self.dt, _p(qkv), 3 * Cc, Cc, _p(m["qdw_wm"]), _p(part), B, H, W, s)
-                self._pr(tag + ".qkv2", vbuf)
-                weff = self._b("weff", (B, Cc, Cc))
-                self.hip.call("fd_chan_attn_weff", self.dt, _p(part), nblk, _p(m["temp"]), _p(m["wproj"]), _p(weff), B, Cc, s)
-                self._pr(tag + ".weff", weff)
-                x2 = self._b(tag + ".x2", (B, H, W, Cc))
-                self.conv(None, vbuf, B, H, W, x2, c0=Cc, ld0=Cc, off0=0, weight=weff, w_batch_stride=Cc * Cc,
-                          bias=None, Cout=Cc, KH=1, KW=1, epi=L.EPI_GATE_RES, res=x1, gate=mp(5), gate_ld=ml)
-                self._pr(tag, x2)
-                return x2
-            self.hip.call("fd_dwconv3x3", self.dt, _p(qkv), 3 * Cc, 0, _p(m["qdw_w"]), None, 0, _p(qkv2), 3 * Cc, 0,
-                   B, H, W, 3 * Cc, s)
-        self._pr(tag + ".qkv2", qkv2)
-        nblk = self.hip.lib().fd_chan_attn_nblk(hw)
+                route, nblk, v = "qkv_dw", lib.fd_chan_attn_nblk(hw), (qkv2, 3 * Cc, 2 * Cc)
         part = self._b("gram", (B, m["heads"], nblk, 1024 + 64), torch.float32)
-        self.hip.call("fd_chan_attn_gram", self.dt, _p(qkv2), B, hw, Cc, _p(part), s)
+        if route == "gram32":
+            # fp32s: q, k -> depthwise -> Gram + norms in one pass over x1, then (the tail) v -> depthwise -> Weff -> gated
+            # residual in another: q, k, v and the attention output never reach HBM (fd_pwdw32.hip)
+            self.hip.call("fd_pw_dw3x3_gram_f32", _p(x1), Cc, 0, Cc, None, None, 1e-6, mp(3), mp(4), ml, _p(qw.w_hi), _p(qw.w_lo), _p(m["qdw_w"]),
+                   3 * Cc, _p(part), B, H, W, s)
+        elif route == "gram":
+            # qkv -> qkv_dwconv -> L2 norms + q k^T in one pass: q and k never reach HBM, only v and one Gram partial per
+            # workgroup do (fd_pwdw.hip: pwdw_gram_kernel; gdt carries FD_OPT_LOW_LATENCY: its tiles per workgroup)
+            self.hip.call("fd_pw_dw3x3_gram", gdt, _p(x1), Cc, 0, Cc, None, None, 1e-6, mp(3), mp(4), ml,
+                   _p(qw.w), _p(m["qdw_wm"]), _p(v[0]) if v else None, Cc, 0, _p(part), B, H, W, s)
+            if v:
+                self._pr(tag + ".qkv2", v[0])
+        elif route == "qkv_gram":
+            # qkv_dwconv of q and k straight into the Gram (fd_pwdw.hip: dwconv_gram_kernel): only v is written
+            qkv = self._b("qkv", (B, H, W, 3 * Cc))
+            self._ln_conv1x1(qw, x1, B, H, W, qkv, 3, ln2)
+            self.hip.call("fd_dwconv3x3", self.dt, _p(qkv), 3 * Cc, 2 * Cc, _p(m["qdw_w_v"]), None, 0, _p(v[0]), Cc, 0,
+                   B, H, W, Cc, s)
+            self.hip.call("fd_dwconv_gram", self.dt, _p(qkv), 3 * Cc, Cc, _p(m["qdw_wm"]), _p(part), B, H, W, s)
+            self._pr(tag + ".qkv2", v[0])
+        else:
+            # q, k, v after the depthwise in one buffer (one fused kernel, or 1x1 then depthwise), the Gram by a kernel of its own
+            if route == "pwdw":
+                self.hip.call("fd_pw_dw3x3", self.dt, _p(x1), Cc, 0, Cc, None, None, 1e-6, mp(3), mp(4), ml, _p(qw.w), 3 * Cc,
+                       _p(m["qdw_wm"]), None, 0, _p(qkv2), 3 * Cc, 0, 0, None, 0, 0, B, H, W, s)
+            else:
+                qkv = self._b("qkv", (B, H, W, 3 * Cc))
+                self._ln_conv1x1(qw, x1, B, H, W, qkv, 3, ln2)
+                self.hip.call("fd_dwconv3x3", self.dt, _p(qkv), 3 * Cc, 0, _p(m["qdw_w"]), None, 0, _p(qkv2), 3 * Cc, 0,
+                       B, H, W, 3 * Cc, s)
+            self._pr(tag + ".qkv2", qkv2)
+            self.hip.call("fd_chan_attn_gram", self.dt, _p(qkv2), B, hw, Cc, _p(part), s)
+
+        # --- the tail: Weff, then x2 = x1 + gate * Weff . v
         weff = self._b("weff", (B, Cc, Cc))
         self.hip.call("fd_chan_attn_weff", self.dt, _p(part), nblk, _p(m["temp"]), _p(m["wproj"]), _p(weff), B, Cc, s)
         self._pr(tag + ".weff", weff)
         x2 = self._b(tag + ".x2", (B, H, W, Cc))
-        self.conv(None, qkv2, B, H, W, x2, c0=Cc, ld0=3 * Cc, off0=2 * Cc, weight=weff, w_batch_stride=Cc * Cc,
-                  bias=None, Cout=Cc, KH=1, KW=1, epi=L.EPI_GATE_RES, res=x1, gate=mp(5), gate_ld=ml)
+        if v is not None:
+            self.conv(None, v[0], B, H, W, x2, c0=Cc, ld0=v[1], off0=v[2], weight=weff, w_batch_stride=Cc * Cc,
+                      bias=None, Cout=Cc, KH=1, KW=1, epi=L.EPI_GATE_RES, res=x1, gate=mp(5), gate_ld=ml)
+        elif route == "gram32":         # the tail's fused variants: v recomputed from x1 in the kernel that applies Weff
+            wvh, wvl = (C.c_void_p(t.data_ptr() + 2 * Cc * Cc * t.element_size()) for t in (qw.w_hi, qw.w_lo))
+            self.hip.call("fd_pw_dw3x3_proj_f32", _p(x1), Cc, 0, Cc, None, None, 1e-6, mp(3), mp(4), ml, wvh, wvl, _p(m["qdw_w_v"]), Cc,
+                   _p(weff), mp(5), ml, _p(x2), Cc, 0, B, H, W, s)
+        else:
+            wv = C.c_void_p(qw.w.data_ptr() + 2 * Cc * Cc * qw.w.element_size())
+            self.hip.call("fd_pw_dw3x3_proj", gdt, _p(x1), Cc, 0, Cc, None, None, 1e-6, mp(3), mp(4), ml, wv, _p(m["qdw_wm_v"]),
+                   _p(weff), mp(5), ml, _p(x2), Cc, 0, B, H, W, s)
         self._pr(tag, x2)
         return x2
+
+    def _ln_conv1x1(self, cw, x, B, H, W, out, nchunks, ln, split=None):
+        """LayerNorm+modulate (`ln`: the PRO_LN_MOD keywords of conv) -> bias-free 1x1 convolution, SiLU on output channels >=
+        `split`, where no fused 1x1 -> depthwise kernel runs: on the row-GEMM with the LayerNorm in its operand load, as `nchunks`
+        column ranges of it (fp32s, C = 128: in_proj as x half and z half, qkv as q, k, v), else as a LayerNorm kernel and a GEMM."""
+        epi = dict(epi=L.EPI_SILU_SPLIT, split=split) if split is not None else {}
+        if self.conv(cw, x, B, H, W, out, probe=True, **epi, **ln):
+            self.conv(cw, x, B, H, W, out, **epi, **ln)
+        elif not (self.f32_split and self.conv_cols(cw, x, B, H, W, out, cw.Cout, nchunks, split=split, **ln)):
+            xm = self._b("xm", (B, H, W, cw.Cin))
+            self.hip.call("fd_ln_modulate", self.dt, _p(x), _p(ln.get("ln_gamma")), _p(ln.get("ln_beta")), ln["ln_eps"], ln["ln_shift"],
+                   ln["ln_scale"], ln["ln_ld"], _p(xm), B, H * W, cw.Cin, self.stream)
+            self.conv(cw, xm, B, H, W, out, **epi)
 
     # ------------------------------------------------------------------ conditioning (once per slice)
     def encode_condition(self, x_cond):
@@ -821,7 +823,7 @@ class DAEngine:
         linear; ~75 us of latency-bound work in front of every forward -- become five launches per LOOP on S * B rows.
         Every row is computed by itself (fd_linear: one wave per output feature, rows in turn): bit for bit the vectors
         time_cond produces.  forward(..., step=s) takes its vectors from the table."""
-        if getattr(self, "_tab_S", None) is None:
+        if self._tab_S is None:
             raise RuntimeError("time_cond_table(): call time_table_prepare(times, B) first (it owns the host -> device copy)")
         S, B = self._tab_S, self._tab_B
         if self.prompt_emb.shape[0] != B:
@@ -857,7 +859,7 @@ class DAEngine:
         if step is None:
             self.time_cond(time)
         else:                                   # vectors of loop step `step` from time_cond_table()
-            tab = getattr(self, "_mod_tab_shape", None)
+            tab = self._mod_tab_shape
             if tab is None:
                 raise RuntimeError("forward(step=...): no adaLN table -- call time_table_prepare() and time_cond_table() first")
             if tab[1] != B or not 0 <= int(step) < tab[0]:
@@ -941,9 +943,9 @@ class DAEngine:
         x = self.mamba_block(d["mamba"], x, B, h, w, f"d{i}m")
         cw = d["samp"]
         Cx = x.shape[-1]
-        if (d["stride"] == 2 and d["res"]["res"] is None and getattr(self, "down_fuse", False) and cw.KH == 4 and cw.KW == 4
-                and getattr(cw, "w8", None) is None
-                and self.hip.lib().fd_gn_apply_down4x4_ok(getattr(self, "scan_dt", self.dt), Cx, cw.Cout, h, w)):
+        if (d["stride"] == 2 and d["res"]["res"] is None and self.down_fuse and cw.KH == 4 and cw.KW == 4
+                and cw.w8 is None
+                and self.hip.lib().fd_gn_apply_down4x4_ok(self.scan_dt, Cx, cw.Cout, h, w)):
             # GroupNorm apply + SiLU + residual of the block AND the 4x4 / stride-2 convolution behind it in one pass: the
             # block output (the skip) is written once and read back by nothing (fd_downfuse.hip)
             hraw, mr, sk = self.res_block(d["res"], x, Cx, None, 0, B, h, w, f"d{i}r", defer_apply=True)
@@ -998,18 +1000,14 @@ class DAEngine:
         if sched is not None:
             fin.update(mode=1, alpha=sched[0], last=int(bool(sched[1])), img=x_t, xin=x_in)
         kw = dict(c0=c0, in1=r, c1=c1)
-        if (fr["res"] is not None and (self.tdt in _HALF or getattr(self, "f32_split", 0)) and not self.probe
+        if (fr["res"] is not None and (self.tdt in _HALF or self.f32_split) and not self.probe
                 and _dev("FOUNDDIFF_NO_FINAL_FOLD", "") == ""):
-            mt = self.hip.lib().fd_conv_mtiles(H, W)
-            hraw = self._b("res_h", (B, H, W, cw.Cout))
-            part = self._b("gn_part", (B, mt, cw.Cout, 2), torch.float32)
-            mr = self._b("gn_mr", (B, 8, 2), torch.float32)
+            hraw, mr = self._conv3_gn(cw, x, B, H, W, "finr", launch=False)
             ek = dict(epi=L.EPI_GNSILU_ADD_FINAL, h=hraw, gn=mr, gamma=fr["gamma"], beta=fr["beta"], groups=8, fin=fin)
             if self.conv(fr["res"], x, B, H, W, out, probe=True, **kw, **ek):
                 # res_conv + GroupNorm/SiLU of the 3x3 output + final_conv (+ DDIM update) in ONE epilogue: the block's
                 # 64-channel output, its read by final_conv and the separate update kernel never happen
-                self.conv(cw, x, B, H, W, hraw, stats=part, **kw)
-                self.hip.call("fd_gn_finalize", _p(part), B, mt, cw.Cout, 8, hw, 1e-5, _p(mr), self.stream)
+                self._conv3_gn(cw, x, B, H, W, "finr", **kw)
                 self.conv(fr["res"], x, B, H, W, out, **kw, **ek)
                 return out
         x = self.res_block(fr, x, c0, r, c1, B, H, W, "finr")
