@@ -16,7 +16,7 @@ EPI_NONE, EPI_SILU_SPLIT, EPI_RELU, EPI_GATE_RES, EPI_RES_RELU, EPI_GNSILU_ADD, 
 ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU = range(4)
 PRO_NONE, PRO_LN_MOD, PRO_LN_GATE, PRO_LN_GATE_ZRE = range(4)
 
-vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+vp, i32, i64, f32, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 
 
 class ConvParams(C.Structure):
@@ -163,6 +163,14 @@ SIGNATURES = {
     "fd_metrics": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
     "fd_affine_f32": (i32, [vp, f32, f32, vp, i64, vp]),
     "fd_axpy_f32": (i32, [vp, vp, f32, vp, i64, vp]),
+    "fd_res_qsample_f32": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, i32, i64, vp]),
+    "fd_res_loss_ws_floats": (i64, [i32, i64]),
+    "fd_res_loss_f32": (i32, [vp, vp, i32, f64, vp, vp, vp, i32, i64, vp]),
+    "fd_scale_dev_f32": (i32, [vp, vp, vp, i64, vp]),
+    "fd_opt_chunk_elems": (i32, []),
+    "fd_opt_sumsq_f32": (i32, [vp, vp, vp, i32, vp]),
+    "fd_opt_clip_coef": (i32, [vp, i32, vp, vp, i32, f32, i32, vp, vp]),
+    "fd_opt_adam_ema_f32": (i32, [vp, vp, vp, vp, i32, f64, f64, f64, f64, i32, f64, i32, i32, vp]),
     "fd_half_format": (i32, []),
 }
 

@@ -1,0 +1,507 @@
+"""One training step of the reference's residual diffusion around a trainable U-Net (founddiff_amd.unet_train), on HIP kernels
+(csrc/fd_train_step.hip): everything between a batch and the U-Net, and between the gradients and the next weights
+(src/DADiff.py:1382-1499 ResidualDiffusion.forward / q_sample / p_losses, 1689-1725 the loop body of Trainer.train).
+
+    q_sample(x_start, x_input, t, schedule, ...)   normalize, x_res, q_sample, the cat and the two time inputs: one launch; the noise
+                                                   is given, or keyed per slice as the samplers' (fd_keyed_normal's bits)
+    residual_loss(pred, target, loss_type, scale)  F.l1_loss / F.mse_loss(reduction='none') -> per-slice mean -> batch mean, with its
+                                                   gradient from the same pass (an autograd function)
+    p_losses_fn(model_fn, imgs, t, schedule, ...)  p_losses on a free function model_fn(x_in, [time0, time1]) -> list of (B, 1, H, W)
+    p_losses(self, imgs, t, ...)                   the same on the reference's attribute names
+    ClipAdamEMA(params, ema_params, ...)           clip_grad_norm_ + torch.optim.Adam + zero_grad + the EMA update: three launches
+    train_step(diffusion_or_fn, opt, batch, ...)   p_losses -> backward per loss -> opt.step()
+
+Binding for a training run:
+
+    import DADiff, founddiff_amd.diffusion_train as dt
+    DADiff.ResidualDiffusion.p_losses = dt.p_losses
+
+Deterministic: no float atomics, fixed summation orders that depend on a tensor's own size only, no host synchronisation (the clip
+coefficient, the non-finite flag and Adam's step counts stay on the device).  There is no CPU path.
+
+The EMA schedule (ema_schedule) restates ema-pytorch as the reference constructs it (src/DADiff.py:1607).  ema_pytorch is not
+available where this project is tested, so that parity is UNPINNED: no test compares it with the package itself.
+
+chunk_table, ema_schedule, adam_state_unpack and adam_state_pack are pure host code.
+"""
+import numpy as np
+import torch
+
+from . import _lib as L
+from ._train import empty, ptr, stream, workspace
+
+__all__ = ["q_sample", "residual_loss", "p_losses_fn", "p_losses", "ClipAdamEMA", "train_step", "chunk_table", "ema_schedule",
+           "adam_state_unpack", "adam_state_pack", "CHUNK"]
+
+CHUNK = 4096                      # elements of a parameter per workgroup (fd_opt_chunk_elems())
+_LOSS_TYPES = {"l1": 1, "l2": 2}
+_OBJECTIVES = {"pred_res": 1, "pred_noise": 1, "pred_res_noise": 2, "pred_x0_noise": 2}
+
+
+# ---- pure host code ----------------------------------------------------------------------------------------------------------------
+def chunk_table(numels):
+    """(nchunk, 3) int64 = (tensor index, offset, length): every tensor cut into chunks of CHUNK elements from its own start, in
+    tensor order.  A tensor's chunks depend on its numel alone."""
+    rows = []
+    for i, n in enumerate(numels):
+        n = int(n)
+        if n < 1:
+            raise RuntimeError(f"chunk_table: tensor {i} has no elements")
+        rows += [(i, off, min(CHUNK, n - off)) for off in range(0, n, CHUNK)]
+    return np.asarray(rows, dtype=np.int64).reshape(-1, 3)
+
+
+def ema_schedule(s0, copied, beta=0.995, update_every=10, update_after_step=100, inv_gamma=1.0, power=2 / 3, min_value=0.0):
+    """(mode, decay) of the EMA on the call whose counter value is s0 (0 on the first call); copied: whether the EMA has ever been
+    written.  mode 0: nothing; 1: ema = p; 2: ema -= (1 - decay)(ema - p)."""
+    if s0 % update_every != 0:
+        return 0, 0.0
+    if s0 <= update_after_step or not copied:        # a first copy followed by the decayed update of equal tensors is the copy
+        return 1, 0.0
+    epoch = max(s0 + 1 - update_after_step - 1, 0)
+    if epoch <= 0:
+        return 2, 0.0
+    return 2, min(max(1 - (1 + epoch / inv_gamma) ** -power, min_value), beta)
+
+
+def adam_state_unpack(sd, n):
+    """torch.optim.Adam's state_dict (one param group of n parameters) -> (steps, exp_avg, exp_avg_sq): three lists of length n,
+    step counts as ints; a parameter without state has step 0 and None twice."""
+    groups = sd["param_groups"]
+    if len(groups) != 1 or len(groups[0]["params"]) != n:
+        raise RuntimeError(f"load_state_dict: expected one param group of {n} parameters (got {len(groups)} group(s) of "
+                           f"{[len(g['params']) for g in groups]})")
+    steps, m, v = [0] * n, [None] * n, [None] * n
+    for i, key in enumerate(groups[0]["params"]):
+        st = sd["state"].get(key)
+        if st is None:
+            continue
+        steps[i], m[i], v[i] = int(round(float(st["step"]))), st["exp_avg"], st["exp_avg_sq"]
+    return steps, m, v
+
+
+def adam_state_pack(steps, exp_avg, exp_avg_sq, group):
+    """the inverse: torch.optim.Adam's layout, state[i] = {step, exp_avg, exp_avg_sq} for every parameter that has taken a step;
+    group: the hyperparameters of the one param group (its "params" is replaced)"""
+    state = {i: {"step": torch.tensor(float(s)), "exp_avg": exp_avg[i], "exp_avg_sq": exp_avg_sq[i]}
+             for i, s in enumerate(steps) if s > 0}
+    return {"state": state, "param_groups": [dict(group, params=list(range(len(steps))))]}
+
+
+# ---- argument checks: types and dtypes, then shapes, then devices, before anything launches ------------------------------------------
+def _check_f32(fn, named, optional=()):
+    for name, v in named:
+        if v is None and name in optional:
+            continue
+        if not isinstance(v, torch.Tensor):
+            raise RuntimeError(f"{fn}: {name} must be a tensor (got {type(v).__name__})")
+        if v.dtype != torch.float32:
+            raise RuntimeError(f"{fn}: {name} must be float32 (got {v.dtype})")
+
+
+def _check_i64(fn, name, v):
+    if not isinstance(v, torch.Tensor):
+        raise RuntimeError(f"{fn}: {name} must be a tensor (got {type(v).__name__})")
+    if v.dtype != torch.int64:
+        raise RuntimeError(f"{fn}: {name} must be int64 (got {v.dtype})")
+
+
+def _check_gpu(fn, named):
+    first = None
+    for name, v in named:
+        if v is None:
+            continue
+        if not v.is_cuda:
+            raise RuntimeError(f"{fn}: {name} must live on the GPU (there is no CPU path)")
+        if first is None:
+            first = (name, v.device)
+        elif v.device != first[1]:
+            raise RuntimeError(f"{fn}: {name} lives on {v.device}, {first[0]} on {first[1]}")
+
+
+_TABLES = {}      # (ids of the host tables, device) -> (the host tables, their copies on the device)
+
+
+def _schedule_tables(fn, schedule):
+    if not isinstance(schedule, dict) or "alphas_cumsum" not in schedule or "betas_cumsum" not in schedule:
+        raise RuntimeError(f"{fn}: schedule must be a dict with alphas_cumsum and betas_cumsum (DADiff.residual_schedule(T))")
+    ac, bc = schedule["alphas_cumsum"], schedule["betas_cumsum"]
+    _check_f32(fn, (("schedule['alphas_cumsum']", ac), ("schedule['betas_cumsum']", bc)))
+    if ac.dim() != 1 or ac.shape != bc.shape or ac.numel() < 1:
+        raise RuntimeError(f"{fn}: inconsistent shapes alphas_cumsum{tuple(ac.shape)} betas_cumsum{tuple(bc.shape)} (both (T,))")
+    return ac, bc
+
+
+def _upload_tables(ac, bc, dev):
+    """the two tables on dev, uploaded once per schedule"""
+    if ac.device == dev and bc.device == dev:
+        return ac.contiguous(), bc.contiguous()
+    key = (id(ac), id(bc), dev)
+    if key not in _TABLES:
+        _TABLES[key] = (ac, bc, ac.to(dev).contiguous(), bc.to(dev).contiguous())      # keeps ac, bc alive: the ids stay theirs
+    return _TABLES[key][2:]
+
+
+def _check_qsample(fn, x_start, x_input, t, schedule, noise, slice_seeds, dims=(2, 4)):
+    _check_f32(fn, (("x_start", x_start), ("x_input", x_input), ("noise", noise)), optional=("noise",))
+    _check_i64(fn, "t", t)
+    if slice_seeds is not None:
+        _check_i64(fn, "slice_seeds", slice_seeds)
+    if noise is not None and slice_seeds is not None:
+        raise RuntimeError(f"{fn}: give either noise or slice_seeds, not both")
+    ac, bc = _schedule_tables(fn, schedule)
+    shapes = " ".join(f"{n}{tuple(v.shape)}" for n, v in (("x_start", x_start), ("x_input", x_input), ("t", t), ("noise", noise),
+                                                         ("slice_seeds", slice_seeds)) if v is not None)
+    if x_start.dim() not in dims or x_start.numel() < 1 or (x_start.dim() == 4 and x_start.shape[1] != 1):
+        raise RuntimeError(f"{fn}: unsupported shape {shapes} (x_start is (B, 1, H, W)" + (" or (B, npix))" if 2 in dims else ")"))
+    B = x_start.shape[0]
+    if x_input.shape != x_start.shape or tuple(t.shape) != (B,) or (noise is not None and noise.shape != x_start.shape) or \
+            (slice_seeds is not None and tuple(slice_seeds.shape) != (B,)):
+        raise RuntimeError(f"{fn}: inconsistent shapes {shapes} (x_input and noise as x_start, t and slice_seeds (B,))")
+    if B > 65535:
+        raise RuntimeError(f"{fn}: unsupported shape {shapes} (at most 65535 slices)")
+    _check_gpu(fn, (("x_start", x_start), ("x_input", x_input), ("t", t), ("noise", noise), ("slice_seeds", slice_seeds)))
+    return ac, bc
+
+
+def q_sample(x_start, x_input, t, schedule, noise=None, slice_seeds=None, step=0, normalize=True):
+    """ResidualDiffusion.forward's normalize + p_losses' x_res, q_sample and cat (src/DADiff.py:1382-1388, 1412-1440, 1493-1497).
+    x_start, x_input (B, 1, H, W) or (B, npix) fp32, in [0, 1] with normalize=True (2x - 1 is applied to both); t (B,) int64;
+    schedule = DADiff.residual_schedule(T) (its alphas_cumsum and betas_cumsum are uploaded once).  noise as x_start, or
+    slice_seeds (B,) int64: the noise of slice b is then fd_keyed_normal's stream of (slice_seeds[b], step), whatever its batch or
+    rank.  With neither, the seeds are drawn from torch's generator of the device.
+    Returns x_in (B, 2, ...) = cat(x_t, x_input), x_res = x_input - x_start, the noise, times (2, B) = alphas_cumsum[t] T,
+    betas_cumsum[t] T.  Nothing is differentiable."""
+    fn = "q_sample"
+    ac, bc = _check_qsample(fn, x_start, x_input, t, schedule, noise, slice_seeds)
+    dev = x_start.device
+    B = x_start.shape[0]
+    npix = x_start.numel() // B
+    with torch.no_grad(), torch.cuda.device(dev):
+        ac, bc = _upload_tables(ac, bc, dev)
+        if noise is None and slice_seeds is None:
+            slice_seeds = torch.randint(0, 1 << 62, (B,), device=dev, dtype=torch.int64)
+        x0, xi, tt = x_start.detach().contiguous(), x_input.detach().contiguous(), t.contiguous()
+        new = empty(dev)
+        x_in, x_res, times = new((B, 2) + tuple(x_start.shape[2:] if x_start.dim() == 4 else (npix,))), new(x_start.shape), new(2, B)
+        if noise is None:
+            nz, out, seeds = None, new(x_start.shape), slice_seeds.contiguous()
+        else:
+            nz, out, seeds = noise.detach().contiguous(), None, None
+        L.call("fd_res_qsample_f32", ptr(x0), ptr(xi), ptr(tt), ptr(ac), ptr(bc), ac.numel(), ptr(nz), ptr(seeds), int(step) & 0x7FFFFFFF,
+               int(bool(normalize)), ptr(x_in), ptr(x_res), ptr(out), ptr(times), B, npix, stream(dev))
+    return x_in, x_res, (noise if out is None else out), times
+
+
+def _check_loss(fn, pred, target, loss_type, scale):
+    _check_f32(fn, (("pred", pred), ("target", target)))
+    if loss_type not in _LOSS_TYPES:
+        raise RuntimeError(f"{fn}: invalid loss type {loss_type!r} ('l1' or 'l2')")
+    if not isinstance(scale, (int, float)):
+        raise RuntimeError(f"{fn}: scale must be a number (got {type(scale).__name__})")
+    if pred.dim() < 1 or pred.numel() < 1 or pred.shape != target.shape:
+        raise RuntimeError(f"{fn}: inconsistent shapes pred{tuple(pred.shape)} target{tuple(target.shape)} (equal, (B, ...))")
+    if pred.shape[0] > 65535:
+        raise RuntimeError(f"{fn}: unsupported shape pred{tuple(pred.shape)} (at most 65535 slices)")
+    _check_gpu(fn, (("pred", pred), ("target", target)))
+
+
+class _Loss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, loss_type, scale):
+        _check_loss("residual_loss", pred, target, loss_type, scale)
+        dev = pred.device
+        B = pred.shape[0]
+        npix = pred.numel() // B
+        pf, tf = pred.contiguous(), target.contiguous()
+        with torch.cuda.device(dev):
+            new = empty(dev)
+            loss, dpred = new(1), new(pred.shape)
+            ws = workspace("fd_res_loss_ws_floats", dev, B, npix)
+            L.call("fd_res_loss_f32", ptr(pf), ptr(tf), _LOSS_TYPES[loss_type], float(scale), ptr(loss), ptr(dpred), ptr(ws), B, npix,
+                   stream(dev))
+        ctx.save_for_backward(dpred)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dpred, = ctx.saved_tensors
+        if tuple(dloss.shape) != ():
+            raise RuntimeError(f"residual_loss: the gradient of the result must be a scalar (got {tuple(dloss.shape)})")
+        dev = dpred.device
+        with torch.cuda.device(dev):
+            out = torch.empty_like(dpred)
+            L.call("fd_scale_dev_f32", ptr(dpred), ptr(dloss.float().contiguous()), ptr(out), dpred.numel(), stream(dev))
+        return out, None, None, None
+
+
+def residual_loss(pred, target, loss_type, scale=1.0):
+    """scale * reduce(loss_fn(pred, target, reduction='none'), 'b ... -> b (...)', 'mean').mean() (src/DADiff.py:1476-1481), a
+    scalar on the device.  pred, target (B, ...) fp32 of equal shapes; loss_type 'l1' or 'l2'.  Differentiable in pred: the
+    gradient comes from the forward pass (sign(0) = 0 for l1, as torch) and the backward multiplies it by the incoming scalar.
+    The target gets no gradient."""
+    _check_loss("residual_loss", pred, target, loss_type, scale)
+    return _Loss.apply(pred, target, loss_type, scale)
+
+
+def p_losses_fn(model_fn, imgs, t, schedule, objective="pred_res", loss_type="l1", noise=None, slice_seeds=None, step=0, scale=1.0,
+                normalize=False):
+    """p_losses (src/DADiff.py:1399-1482) for condition=True, input_condition=False on a free function:
+    model_fn(x_in (B, 2, H, W), [time0 (B,), time1 (B,)]) -> list of (B, 1, H, W), one per U-Net.  imgs = [x_start, x_input];
+    normalize=True takes them in [0, 1] as ResidualDiffusion.forward does.  Returns the list of losses, each times scale."""
+    fn = "p_losses"
+    if not callable(model_fn):
+        raise RuntimeError(f"{fn}: model_fn must be callable (got {type(model_fn).__name__})")
+    if objective not in _OBJECTIVES:
+        raise RuntimeError(f"{fn}: unknown objective {objective!r}")
+    if loss_type not in _LOSS_TYPES:
+        raise RuntimeError(f"{fn}: invalid loss type {loss_type!r} ('l1' or 'l2')")
+    if not isinstance(imgs, (list, tuple)) or len(imgs) != 2:
+        raise RuntimeError(f"{fn}: imgs must be [x_start, x_input] (condition=True without an input condition)")
+    x_start, x_input = imgs
+    _check_qsample(fn, x_start, x_input, t, schedule, noise, slice_seeds, dims=(4,))
+    x_in, x_res, noise, times = q_sample(x_start, x_input, t, schedule, noise, slice_seeds, step, normalize)
+    model_out = model_fn(x_in, [times[0], times[1]])
+    if objective == "pred_x0_noise":
+        x0 = x_start.detach()
+        if normalize:
+            x0 = torch.empty_like(x_res)
+            L.call("fd_affine_f32", ptr(x_start.detach().contiguous()), 2.0, -1.0, ptr(x0), x0.numel(), stream(x0.device))
+        target = [x0, noise]
+    else:
+        target = {"pred_res": [x_res], "pred_noise": [noise], "pred_res_noise": [x_res, noise]}[objective]
+    if not isinstance(model_out, (list, tuple)) or len(model_out) != len(target):
+        raise RuntimeError(f"{fn}: objective {objective!r} needs {len(target)} model output(s) (got "
+                           f"{len(model_out) if isinstance(model_out, (list, tuple)) else type(model_out).__name__})")
+    return [residual_loss(o, tg, loss_type, scale) for o, tg in zip(model_out, target)]
+
+
+def _diffusion_args(fn, self):
+    """the reference's attributes behind p_losses, checked"""
+    if getattr(self, "self_condition", False) or getattr(getattr(self, "model", None), "self_condition", False):
+        raise RuntimeError(f"{fn}: self_condition is not supported")
+    if getattr(self, "input_condition", False):
+        raise RuntimeError(f"{fn}: input_condition is not supported")
+    if not getattr(self, "condition", True):
+        raise RuntimeError(f"{fn}: condition=False (generation) is not supported")
+    schedule = dict(alphas_cumsum=self.alphas_cumsum, betas_cumsum=self.betas_cumsum)
+    if schedule["alphas_cumsum"].numel() != self.num_timesteps:
+        raise RuntimeError(f"{fn}: alphas_cumsum has {schedule['alphas_cumsum'].numel()} rows, num_timesteps is {self.num_timesteps}")
+    return (lambda x, times: self.model(x, times)), schedule, self.objective, self.loss_type
+
+
+def p_losses(self, imgs, t, noise=None, slice_seeds=None, step=0, scale=1.0):
+    """ResidualDiffusion.p_losses on the reference's attribute names (objective, loss_type, condition, num_timesteps, model, the
+    alphas_cumsum / betas_cumsum buffers): imgs = [x_start, x_input] already normalised, as ResidualDiffusion.forward hands them
+    over.  self_condition and input_condition raise before anything launches."""
+    model_fn, schedule, objective, loss_type = _diffusion_args("p_losses", self)
+    return p_losses_fn(model_fn, imgs, t, schedule, objective, loss_type, noise, slice_seeds, step, scale, normalize=False)
+
+
+# ---- the optimiser -----------------------------------------------------------------------------------------------------------------
+class ClipAdamEMA:
+    """clip_grad_norm_(params, max_norm) + torch.optim.Adam(params, lr, betas, eps).step() + zero_grad() + the EMA update of
+    ema_params (a parallel list, for example the parameters of a deep copy that samples), in three launches per step().
+
+    step() returns the device record (total_norm, coef, nonfinite flag, 0) without reading it: no .item(), no synchronisation, and
+    no allocation after the first call.  The gradients are taken from p.grad at every call; a parameter whose .grad is None is left
+    alone with its state, its own step count and its EMA entry (a deep copy already equals it), as torch.optim.Adam leaves it.
+    The per-tensor pointer table goes to the device from pinned memory on the current stream, whenever it differs from the one
+    already there (the gradients usually keep their addresses from step to step).  zero_grad is folded into step() by
+    default (g = 0 is written by the update; the .grad tensors stay allocated).  max_norm=None: no clipping (coef = 1).
+    skip_nonfinite: a step whose total norm is inf or NaN writes nothing at all -- the gradients included, so they keep their
+    values: call zero_grad() when the returned flag is up.
+
+    state_dict() / load_state_dict() use torch.optim.Adam's layout (the reference's `opt0` checkpoint entry), plus the EMA counter
+    under "ema_step" / "ema_copied"."""
+
+    def __init__(self, params, ema_params=None, lr=1e-4, betas=(0.9, 0.99), eps=1e-8, max_norm=1.0, ema_beta=0.995,
+                 ema_update_every=10, ema_update_after_step=100, ema_inv_gamma=1.0, ema_power=2 / 3, ema_min_value=0.0,
+                 skip_nonfinite=False):
+        fn = "ClipAdamEMA"
+        if isinstance(params, torch.Tensor):
+            raise RuntimeError(f"{fn}: params must be an iterable of tensors (got one tensor)")
+        params = list(params)
+        ema = None if ema_params is None else list(ema_params)
+        if not params:
+            raise RuntimeError(f"{fn}: params is empty")
+        _check_f32(fn, [(f"params[{i}]", p) for i, p in enumerate(params)])
+        if ema is not None:
+            _check_f32(fn, [(f"ema_params[{i}]", e) for i, e in enumerate(ema)])
+        ok = isinstance(lr, (int, float)) and lr >= 0 and len(betas) == 2 and all(0 <= b < 1 for b in betas) and eps >= 0 and \
+            (max_norm is None or max_norm >= 0) and 0 <= ema_beta <= 1 and ema_update_every >= 1
+        if not ok:
+            raise RuntimeError(f"{fn}: invalid hyperparameters lr={lr} betas={betas} eps={eps} max_norm={max_norm} ema_beta={ema_beta} "
+                               f"ema_update_every={ema_update_every}")
+        if ema is not None and (len(ema) != len(params) or any(e.shape != p.shape for e, p in zip(ema, params))):
+            raise RuntimeError(f"{fn}: inconsistent shapes: ema_params must be a parallel list of tensors shaped as params")
+        for name, lst in (("params", params), ("ema_params", ema or [])):
+            for i, p in enumerate(lst):
+                if p.numel() < 1 or not p.is_contiguous():
+                    raise RuntimeError(f"{fn}: unsupported shape {name}[{i}]{tuple(p.shape)} strides {p.stride()} (dense, not empty)")
+        _check_gpu(fn, [(f"params[{i}]", p) for i, p in enumerate(params)] + [(f"ema_params[{i}]", e) for i, e in enumerate(ema or [])])
+        self.params, self.ema_params = params, ema
+        self.lr, self.betas, self.eps, self.max_norm, self.skip_nonfinite = float(lr), tuple(map(float, betas)), float(eps), max_norm, \
+            bool(skip_nonfinite)
+        self.ema_args = dict(beta=ema_beta, update_every=ema_update_every, update_after_step=ema_update_after_step,
+                             inv_gamma=ema_inv_gamma, power=ema_power, min_value=ema_min_value)
+        self.ema_step, self.ema_copied = 0, False
+        dev = self.device = params[0].device
+        nt = self.nt = len(params)
+        chunks = chunk_table([p.numel() for p in params])
+        self.nchunk = len(chunks)
+        with torch.cuda.device(dev):
+            if L.lib().fd_opt_chunk_elems() != CHUNK:
+                raise RuntimeError(f"{fn}: the library cuts chunks of {L.lib().fd_opt_chunk_elems()} elements, this module of {CHUNK}")
+            self._chunks = torch.from_numpy(chunks).to(dev)
+            offs = np.cumsum([0] + [(p.numel() + 3) & ~3 for p in params])           # every state tensor starts 16-byte aligned
+            self._m, self._v = torch.zeros(int(offs[-1]), device=dev), torch.zeros(int(offs[-1]), device=dev)
+            self.exp_avg = [self._m[o:o + p.numel()].view(p.shape) for o, p in zip(offs, params)]
+            self.exp_avg_sq = [self._v[o:o + p.numel()].view(p.shape) for o, p in zip(offs, params)]
+            self._steps = torch.zeros(nt, device=dev, dtype=torch.int32)
+            self._part, self._rec = torch.empty(self.nchunk, device=dev), torch.zeros(4, device=dev)
+            self._table = torch.zeros(nt, 8, device=dev, dtype=torch.int64)
+            self._pinned = torch.zeros(nt, 8, dtype=torch.int64).pin_memory()
+            self._uploaded, self._event = None, torch.cuda.Event()
+        self._host = np.zeros((nt, 8), dtype=np.int64)
+        self._host[:, 2] = [m.data_ptr() for m in self.exp_avg]
+        self._host[:, 3] = [v.data_ptr() for v in self.exp_avg_sq]
+
+    def _upload_table(self):
+        fn, h = "ClipAdamEMA.step", self._host
+        grads = [p.grad for p in self.params]
+        for i, (p, g) in enumerate(zip(self.params, grads)):
+            if g is None:
+                continue
+            if g.dtype != torch.float32:
+                raise RuntimeError(f"{fn}: the gradient of params[{i}] must be float32 (got {g.dtype})")
+            if g.shape != p.shape or not g.is_contiguous():
+                raise RuntimeError(f"{fn}: inconsistent shapes: the gradient of params[{i}]{tuple(p.shape)} is {tuple(g.shape)} with "
+                                   f"strides {g.stride()} (dense, shaped as the parameter)")
+            if g.device != self.device:
+                raise RuntimeError(f"{fn}: the gradient of params[{i}] lives on {g.device}, the parameters on {self.device}")
+        h[:, 0] = [p.data_ptr() for p in self.params]
+        h[:, 1] = [0 if g is None else g.data_ptr() for g in grads]
+        h[:, 4] = 0 if self.ema_params is None else [e.data_ptr() for e in self.ema_params]
+        aligned = ((h[:, 0] | h[:, 1] | h[:, 4]) & 15) == 0
+        h[:, 5] = np.where(h[:, 1] != 0, 1 + 2 * aligned, 0)
+        if self._uploaded is None or not np.array_equal(h, self._uploaded):
+            if self._uploaded is not None:
+                self._event.synchronize()                # the pinned buffer's last copy has left it (a changed table is rare)
+            self._pinned.numpy()[:] = h
+            self._table.copy_(self._pinned, non_blocking=True)
+            self._event.record()
+            self._uploaded = h.copy()
+
+    def step(self, zero_grad=True, ema_mode=None, ema_decay=None):
+        """One update on the current stream.  ema_mode / ema_decay override the schedule for this call (0: leave the EMA alone, 1: copy,
+        2: decayed update).  Returns the device record (4 floats): total_norm, coef, nonfinite, 0."""
+        if ema_mode is not None and (ema_mode not in (0, 1, 2) or (ema_mode == 2 and ema_decay is None)):
+            raise RuntimeError(f"ClipAdamEMA.step: ema_mode must be 0, 1 or 2, with an ema_decay for 2 (got {ema_mode}, {ema_decay})")
+        with torch.cuda.device(self.device):
+            self._upload_table()
+            s0 = self.ema_step
+            self.ema_step += 1
+            if self.ema_params is None:
+                mode, decay = 0, 0.0
+            elif ema_mode is not None:
+                mode, decay = ema_mode, float(ema_decay or 0.0)
+            else:
+                mode, decay = ema_schedule(s0, self.ema_copied, **self.ema_args)
+            self.ema_copied = self.ema_copied or mode != 0
+            st, skip = stream(self.device), int(self.skip_nonfinite)
+            L.call("fd_opt_sumsq_f32", ptr(self._chunks), ptr(self._table), ptr(self._part), self.nchunk, st)
+            L.call("fd_opt_clip_coef", ptr(self._part), self.nchunk, ptr(self._table), ptr(self._steps), self.nt,
+                   -1.0 if self.max_norm is None else float(self.max_norm), skip, ptr(self._rec), st)
+            L.call("fd_opt_adam_ema_f32", ptr(self._chunks), ptr(self._table), ptr(self._steps), ptr(self._rec), self.nchunk, self.lr,
+                   self.betas[0], self.betas[1], self.eps, mode, decay, int(bool(zero_grad)), skip, st)
+        return self._rec
+
+    def zero_grad(self):
+        """the gradients to zero, kept allocated (step() does this itself unless called with zero_grad=False)"""
+        grads = [p.grad for p in self.params if p.grad is not None]
+        if grads:
+            torch._foreach_zero_(grads)
+
+    def steps(self):
+        """the Adam step count of every parameter (reads the device)"""
+        return self._steps.cpu().tolist()
+
+    def _group(self):
+        g = torch.optim.Adam([torch.zeros(1)], lr=self.lr, betas=self.betas, eps=self.eps).state_dict()["param_groups"][0]
+        return g
+
+    def state_dict(self):
+        sd = adam_state_pack(self.steps(), [m.clone() for m in self.exp_avg], [v.clone() for v in self.exp_avg_sq], self._group())
+        sd["ema_step"], sd["ema_copied"] = self.ema_step, self.ema_copied
+        return sd
+
+    def load_state_dict(self, sd):
+        steps, m, v = adam_state_unpack(sd, self.nt)
+        for i, p in enumerate(self.params):
+            for name, t in (("exp_avg", m[i]), ("exp_avg_sq", v[i])):
+                if t is not None and (not isinstance(t, torch.Tensor) or t.shape != p.shape):
+                    raise RuntimeError(f"ClipAdamEMA.load_state_dict: inconsistent shapes: {name} of parameter {i} is "
+                                       f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}, the parameter "
+                                       f"{tuple(p.shape)}")
+        with torch.no_grad():
+            for i in range(self.nt):
+                for dst, src in ((self.exp_avg[i], m[i]), (self.exp_avg_sq[i], v[i])):
+                    if src is None:
+                        dst.zero_()
+                    else:
+                        dst.copy_(src)
+            self._steps.copy_(torch.tensor(steps, dtype=torch.int32))
+        group = sd["param_groups"][0]
+        self.lr, self.betas, self.eps = float(group.get("lr", self.lr)), tuple(map(float, group.get("betas", self.betas))), \
+            float(group.get("eps", self.eps))
+        self.ema_step, self.ema_copied = int(sd.get("ema_step", self.ema_step)), bool(sd.get("ema_copied", self.ema_copied))
+
+
+# ---- the loop body -----------------------------------------------------------------------------------------------------------------
+def train_step(diffusion_or_fn, opt, batch, t=None, noise=None, slice_seeds=None, step=0, schedule=None, objective="pred_res",
+               loss_type="l1", normalize=True):
+    """The loop body of Trainer.train (src/DADiff.py:1689-1725) for one accumulation group: p_losses -> backward per loss ->
+    opt.step() (clip, Adam, zero_grad, EMA).  diffusion_or_fn: an object with the reference's ResidualDiffusion attributes, or a
+    free model_fn(x_in, [time0, time1]) -> list of (B, 1, H, W) together with schedule, objective and loss_type.  batch:
+    [x_start, x_input] in [0, 1] (normalize=True, as ResidualDiffusion.forward takes them), or a list of such pairs: the
+    micro-batches of gradient_accumulate_every, each loss scaled by one over their number.  t, noise and slice_seeds belong to the
+    micro-batch (lists of them for several); t defaults to torch.randint(0, T, (B,)) as the reference draws it.  `step` keys the
+    noise together with slice_seeds.  Returns the losses, one device tensor per U-Net, summed over the micro-batches."""
+    fn = "train_step"
+    if not isinstance(opt, ClipAdamEMA):
+        raise RuntimeError(f"{fn}: opt must be a ClipAdamEMA (got {type(opt).__name__})")
+    if not isinstance(batch, (list, tuple)) or not batch:
+        raise RuntimeError(f"{fn}: batch must be [x_start, x_input] or a list of such pairs (got {type(batch).__name__})")
+    many = isinstance(batch[0], (list, tuple))
+    groups = list(batch) if many else [batch]
+    if hasattr(diffusion_or_fn, "alphas_cumsum") and hasattr(diffusion_or_fn, "objective"):
+        model_fn, schedule, objective, loss_type = _diffusion_args(fn, diffusion_or_fn)
+    elif callable(diffusion_or_fn):
+        model_fn = diffusion_or_fn
+    else:
+        raise RuntimeError(f"{fn}: diffusion_or_fn must be a ResidualDiffusion or a callable (got {type(diffusion_or_fn).__name__})")
+    ac, _ = _schedule_tables(fn, schedule)
+
+    def pick(v, i):
+        if not many:
+            return v
+        if v is not None and (not isinstance(v, (list, tuple)) or len(v) != len(groups)):
+            raise RuntimeError(f"{fn}: with {len(groups)} micro-batches t, noise and slice_seeds are lists of {len(groups)}")
+        return None if v is None else v[i]
+
+    total = None
+    for i, imgs in enumerate(groups):
+        ti = pick(t, i)
+        if ti is None:
+            if not (isinstance(imgs, (list, tuple)) and len(imgs) == 2 and isinstance(imgs[0], torch.Tensor) and imgs[0].is_cuda):
+                raise RuntimeError(f"{fn}: a micro-batch must be [x_start, x_input] on the GPU (there is no CPU path)")
+            ti = torch.randint(0, ac.numel(), (imgs[0].shape[0],), device=imgs[0].device).long()
+        losses = p_losses_fn(model_fn, imgs, ti, schedule, objective, loss_type, pick(noise, i), pick(slice_seeds, i), step,
+                             1.0 / len(groups), normalize)
+        for loss in losses:
+            loss.backward()
+        det = [loss.detach() for loss in losses]
+        total = det if total is None else [a + b for a, b in zip(total, det)]
+    opt.step()
+    return total

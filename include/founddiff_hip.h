@@ -690,6 +690,42 @@ int fd_affine_f32(const float *x, float a, float b, float *out, int64_t n, void 
 /* out = x + s*noise   (x_T = x_input + sqrt(sum_scale) eps, src/DADiff.py:1294)              */
 int fd_axpy_f32(const float *x, const float *noise, float s, float *out, int64_t n, void *stream);
 
+/* ---- one training step around the U-Net (fd_train_step.hip; src/DADiff.py:1382-1499, 1689-1725) ---------------
+ * fp32, deterministic, no float atomics, no host synchronisation; every summation order depends on the tensor's own
+ * size only.  16-byte accesses where the pointers (and npix % 4) allow, the same elements per lane on the scalar path.
+ * fd_res_qsample_f32: ResidualDiffusion.forward's normalize (2x - 1, if `normalize`), x_res = x_input - x_start,
+ *   q_sample and the cat in one launch.  x_start, x_input, noise [B][npix]; t [B] int64 (clamped to [0, T)); alphas_cumsum,
+ *   betas_cumsum [T] on the device.  Give either noise, or seeds [B] int64: then noise = the keyed stream of
+ *   fd_keyed_normal(seeds, noise_step) and is written to noise_out.
+ *   x_in [B][2][npix] = (x_start + ac x_res + bc noise, x_input), x_res [B][npix], times [2][B] = ac T, bc T.
+ * fd_res_loss_f32: loss[0] = scale * mean_b(mean_i(|pred - target| or (pred - target)^2)) (loss_type 1 = l1, 2 = l2) and
+ *   dpred = its gradient (sign(0) = 0).  ws: fd_res_loss_ws_floats(B, npix) floats (0: unsupported shape).
+ * The optimiser: clip_grad_norm_(max_norm) + torch.optim.Adam (weight_decay 0, no amsgrad) + zero_grad + the EMA update in
+ *   three launches over two int64 tables on the device:
+ *     chunks  [nchunk][3] = tensor index, offset, length: every tensor cut into fd_opt_chunk_elems() elements from its start
+ *     tensors [nt][8]     = p, g, m, v, ema (addresses; ema may be 0), flags (1: has a gradient, 2: all five 16-byte aligned), 0, 0
+ *   fd_opt_sumsq_f32     part[chunk] = sum of g^2 (0 without a gradient)
+ *   fd_opt_clip_coef     rec[4] = total_norm, coef = min(1, max_norm / (total_norm + 1e-6)) (1 if max_norm < 0), nonfinite, 0;
+ *                        steps[i] += 1 for every tensor with a gradient, unless skip_nonfinite and nonfinite
+ *   fd_opt_adam_ema_f32  g' = coef g; Adam with the bias corrections of steps[i]; ema_mode 0: none, 1: ema = p,
+ *                        2: ema -= (1 - ema_decay)(ema - p); zero_grad: g = 0; writes nothing if skip_nonfinite and nonfinite */
+int fd_res_qsample_f32(const float *x_start, const float *x_input, const int64_t *t, const float *alphas_cumsum,
+                       const float *betas_cumsum, int T, const float *noise, const int64_t *seeds, int noise_step,
+                       int normalize, float *x_in, float *x_res, float *noise_out, float *times, int B, int64_t npix,
+                       void *stream);
+int64_t fd_res_loss_ws_floats(int B, int64_t npix);
+int fd_res_loss_f32(const float *pred, const float *target, int loss_type, double scale, float *loss, float *dpred,
+                    float *ws, int B, int64_t npix, void *stream);
+/* out = s_dev[0] * x (the loss gradient times the scalar autograd hands back, read on the device) */
+int fd_scale_dev_f32(const float *x, const float *s_dev, float *out, int64_t n, void *stream);
+int fd_opt_chunk_elems(void);
+int fd_opt_sumsq_f32(const int64_t *chunks, const int64_t *tensors, float *part, int nchunk, void *stream);
+int fd_opt_clip_coef(const float *part, int nchunk, const int64_t *tensors, int *steps, int nt, float max_norm,
+                     int skip_nonfinite, float *rec, void *stream);
+int fd_opt_adam_ema_f32(const int64_t *chunks, const int64_t *tensors, const int *steps, const float *rec, int nchunk,
+                        double lr, double beta1, double beta2, double eps, int ema_mode, double ema_decay, int zero_grad,
+                        int skip_nonfinite, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
