@@ -6,9 +6,14 @@ Same class names, constructor kwargs, method names/signatures and state_dict key
 reference (`/root/reference/src/DADiff.py`; contract in SURVEY.md section 8b), so
 `checkpoints/<name>/sample/model-N.pt` loads unchanged.  The modules below hold parameters only:
 `forward` never runs a torch op on activations -- it hands device pointers to libfounddiff_hip.so
-through `founddiff_amd.engine.DAEngine`.  Training (`p_losses`, optimiser, EMA update) is out of
-scope (inference engine).
+through `founddiff_amd.engine.DAEngine`.
+
+Training runs on the same classes: `Unet.trainable()` is a `unet_train.UnetTrunk` over the very
+parameters of the tree, `Unet.train_forward` runs the frozen DA-CLIP tower on the fp32 engine and the trunk under autograd on the HIP
+training kernels, `ResidualDiffusion.forward` / `p_losses` are the reference's (diffusion_train), and `Trainer.train / save / load`
+are its loop and checkpoint around `diffusion_train.ClipAdamEMA`.  One U-Net only: the reference optimises two with RAdam.
 """
+import copy
 import ctypes as C
 import math
 import os
@@ -21,6 +26,7 @@ from torch import nn
 
 from . import _lib as L
 from . import arch
+from . import diffusion_train as dt
 from .engine import DAEngine, _p
 
 ModelResPrediction = namedtuple("ModelResPrediction", ["pred_res", "pred_noise", "pred_x_start"])
@@ -124,20 +130,83 @@ class Unet(_ParamTree):
         _build_tree(self, arch.da_unet_spec(dim, self.dim_mults, channels, "", self.clip_cfg, input_condition))
         self._engine = None
 
+    _trainable = None        # trainable()'s UnetTrunk; kept out of _modules, so state_dict() and .to() meet every parameter once
+    _train_engine = None     # the 'fp32' engine of train_forward: the frozen DA-CLIP tower alone (DAEngine(tower_only=True))
+
+    def _drop_engines(self):
+        """every packed copy of the weights, the frozen tower's included: the parameters were replaced or moved"""
+        self._engine = None
+        self._train_engine = None
+
     # --- checkpoint handling: accept-and-ignore the dead weight a real checkpoint carries
     def load_state_dict(self, state_dict, strict=True, assign=False):
         live = {k: v for k, v in state_dict.items() if not arch.is_dead_key("unet0." + k, "unet0.")}
-        self._engine = None
+        self._drop_engines()
+        if assign:                       # new Parameter objects: the view would keep the old ones
+            self.__dict__.pop("_trainable", None)
         return super().load_state_dict(live, strict=strict, assign=assign)
 
     def _load_from_state_dict(self, *a, **k):
-        self._engine = None
+        self._drop_engines()
         return super()._load_from_state_dict(*a, **k)
 
     def _apply(self, fn, *a, **k):
         # .to(device) / .cuda() / dtype casts move the parameters: the packed weights of the engine are stale
-        self._engine = None
+        self._drop_engines()
         return super()._apply(fn, *a, **k)
+
+    # --- training (INTEGRATION.md, section B.1a)
+    def weights_changed(self):
+        """Tell the model that its trunk parameters were written in place behind its back (ClipAdamEMA writes through raw pointers):
+        the packed engines and the graphs they captured are dropped, the next sampling call packs again.  The engine of
+        train_forward stays: it holds the frozen tower only."""
+        self._engine = None
+
+    def trainable(self):
+        """The trunk of this model as a unet_train.UnetTrunk, built once: its parameters ARE the nn.Parameter objects of this tree's
+        trunk entries (re-registered, not copied), so state_dict(), .to(), load_state_dict() and the engines' packing see the same
+        storage.  Trunk parameters get requires_grad=True; everything under dose_encoder. stays frozen.  From the first call on
+        UnetRes.forward routes to train_forward whenever gradients are enabled."""
+        if self._trainable is None:
+            if self.input_condition or self.self_condition:
+                raise RuntimeError("Unet.trainable: input_condition and self_condition are not supported in training")
+            from .unet_train import UnetTrunk
+            with torch.random.fork_rng(devices=[]):           # the view's own initialisation is thrown away: leave the generator alone
+                trunk = UnetTrunk(self.dim, self.dim_mults, channels=self.channels, input_channels=2 * self.channels)
+            mine = {k: p for k, p in self.named_parameters() if not k.startswith("dose_encoder.")}
+            theirs = [k for k, _ in trunk.named_parameters()]
+            if set(theirs) != set(mine) or any(trunk.get_parameter(k).shape != mine[k].shape for k in theirs):
+                odd = sorted(set(theirs) ^ set(mine)) or [k for k in theirs if trunk.get_parameter(k).shape != mine[k].shape]
+                raise RuntimeError(f"Unet.trainable: the trunk's layout differs from UnetTrunk's (e.g. {odd[:3]})")
+            for k in theirs:
+                parent, _, leaf = k.rpartition(".")
+                trunk.get_submodule(parent)._parameters[leaf] = mine[k].requires_grad_(True)
+            self.__dict__["_trainable"] = trunk
+        return self._trainable
+
+    def train_forward(self, x, time):
+        """x (B, 2, H, W) = cat(x_t, x_input), time (B,) -> (B, 1, H, W), differentiable in the trunk's parameters.  The frozen DA-CLIP
+        tower runs on this model's 'fp32' engine whatever its sampling precision (the reference trains in fp32); the trunk, the two
+        outer convolutions included, on the HIP training kernels (unet_train.unet_trunk_forward)."""
+        from .outer_conv_train import final_conv_fn, init_conv_fn
+        from .unet_train import unet_trunk_forward
+        fn = "Unet.train_forward"
+        trunk = self.trainable()
+        for name, v in (("x", x), ("time", time)):
+            if not isinstance(v, torch.Tensor):
+                raise RuntimeError(f"{fn}: {name} must be a tensor (got {type(v).__name__})")
+        if x.dim() != 4 or x.shape[1] != 2 * self.channels or time.dim() != 1 or time.shape[0] != x.shape[0]:
+            raise RuntimeError(f"{fn}: inconsistent shapes x{tuple(x.shape)} time{tuple(time.shape)} (expected (B, 2, H, W) and (B,))")
+        if not x.is_cuda or not time.is_cuda or next(self.parameters()).device != x.device:
+            raise RuntimeError(f"{fn}: x, time and the model must live on one GPU (there is no CPU path)")
+        x = x.detach().float().contiguous()
+        if self._train_engine is None:
+            tower = {k: v for k, v in self.state_dict().items() if k.startswith("dose_encoder.")}
+            self._train_engine = DAEngine(tower, "", x.device, "fp32", tower_only=True)      # no copy of the trunk: it would go stale
+        with torch.no_grad(), torch.cuda.device(x.device):
+            dose, ctx = self._train_engine.encode_dose(x[:, 1:2].contiguous())
+            dose, ctx = dose.clone(), ctx.clone()             # the engine's buffers belong to its next call
+        return unet_trunk_forward(trunk, x, time.float(), dose, ctx.unsqueeze(1), init_fn=init_conv_fn, final_fn=final_conv_fn)
 
     def load_dose_clip(self, path_or_state="Dose-CLIP.pth"):
         """The reference builds its dose encoder from a separate file at construction time:
@@ -155,7 +224,7 @@ class Unet(_ParamTree):
             raise RuntimeError(f"Dose-CLIP state_dict lacks {len(missing)} live keys, e.g. {[m[len('dose_encoder.'):] for m in missing[:3]]}")
         res = super().load_state_dict(live, strict=False)
         assert not res.unexpected_keys
-        self._engine = None
+        self._drop_engines()
         return res
 
     @property
@@ -237,7 +306,16 @@ class UnetRes(nn.Module):
                               input_condition=input_condition, precision=precision, clip_cfg=clip_cfg)
 
     def forward(self, x, time, x_self_cond=None, reuse_condition=False):
-        """src/DADiff.py:817-836.  time = [alphas_cumsum[t]*T, betas_cumsum[t]*T]."""
+        """src/DADiff.py:817-836.  time = [alphas_cumsum[t]*T, betas_cumsum[t]*T].  With gradients enabled on a model whose
+        trainable view exists (Unet.trainable(): ResidualDiffusion.forward and Trainer.train ask for it) the call is a training
+        forward, Unet.train_forward; under no_grad, and on a model that never trained, it is the engine as ever."""
+        if torch.is_grad_enabled() and self.unet0._trainable is not None:
+            if self.num_unet != 1:
+                raise NotImplementedError("training two U-Nets: the reference optimises them with RAdam, which is not built "
+                                          "(DESIGN.md section 8)")
+            if self.objective not in ("pred_res", "pred_noise"):
+                raise ValueError(f"objective {self.objective!r} needs num_unet=2 (src/DADiff.py:826-831)")
+            return [self.unet0.train_forward(x, time[1] if self.objective == "pred_noise" else time[0])]
         kw = dict(x_self_cond=x_self_cond, reuse_condition=reuse_condition)
         if self.num_unet == 2:
             if self.test_res_or_noise == "res_noise":
@@ -1032,8 +1110,55 @@ class ResidualDiffusion(nn.Module):
             res.append(torch.cat([o[j] for _, o in outs], 0))
         return res
 
-    def forward(self, *a, **k):
-        raise NotImplementedError("training (p_losses) is out of scope: founddiff_amd is a sampling engine")
+    # ---- training (src/DADiff.py:1382-1499)
+    def weights_changed(self):
+        """The parameters were written in place (ClipAdamEMA's raw pointers): forget the captured graphs and the packed engines."""
+        self._drop_graphs()
+        for name in ("unet0", "unet1"):
+            u = getattr(self.model, name, None)
+            if u is not None:
+                u.weights_changed()
+
+    def clone(self):
+        """A deep copy with its own parameters and no engines, graphs or streams (the EMA model of Trainer.train)."""
+        self.weights_changed()
+        unets = [u for u in (getattr(self.model, n, None) for n in ("unet0", "unet1")) if u is not None]
+        saved, self._side_streams = self._side_streams, {}
+        engines = [u._train_engine for u in unets]
+        for u in unets:
+            u._train_engine = None
+        try:
+            return copy.deepcopy(self)
+        finally:
+            self._side_streams = saved
+            for u, e in zip(unets, engines):
+                u._train_engine = e
+
+    def _train_ready(self, fn):
+        if getattr(self.model, "num_unet", 1) != 1:
+            raise NotImplementedError(f"{fn}: training two U-Nets: the reference optimises them with RAdam, which is not built "
+                                      "(DESIGN.md section 8); objectives 'pred_res' and 'pred_noise' train one")
+        self.model.unet0.trainable()
+
+    def p_losses(self, imgs, t, noise=None, slice_seeds=None, step=0, scale=1.0):
+        """diffusion_train.p_losses (src/DADiff.py:1399-1482) on this class: imgs = [x_start, x_input] already normalised.  Asks
+        for the trainable view first, so that a bare call on a fresh model is a training forward and not the no_grad engine."""
+        self._train_ready("ResidualDiffusion.p_losses")
+        return dt.p_losses(self, imgs, t, noise, slice_seeds, step, scale)
+
+    def forward(self, imgs, t=None, noise=None, slice_seeds=None, step=0):
+        """src/DADiff.py:1382-1397: imgs = [x_start, x_input], (B, 1, H, W) in [0, 1] -> the list of losses (one U-Net: one),
+        differentiable in the trunk's parameters.  t (B,) int64 is drawn as the reference draws it unless given; noise, or
+        slice_seeds (+ step) for the keyed per-slice stream, as diffusion_train.q_sample takes them.  RuntimeError for CPU tensors
+        (there is no CPU path), NotImplementedError for two U-Nets."""
+        fn = "ResidualDiffusion.forward"
+        self._train_ready(fn)
+        model_fn, schedule, objective, loss_type = dt._diffusion_args(fn, self)
+        if not isinstance(imgs, (list, tuple)) or len(imgs) != 2 or not all(isinstance(v, torch.Tensor) for v in imgs):
+            raise RuntimeError(f"{fn}: imgs must be [x_start, x_input] (condition=True without an input condition)")
+        if t is None:
+            t = torch.randint(0, self.num_timesteps, (imgs[0].shape[0],), device=imgs[0].device).long()
+        return dt.p_losses_fn(model_fn, imgs, t, schedule, objective, loss_type, noise, slice_seeds, step, 1.0, normalize=True)
 
 
 class _Accel:
@@ -1066,18 +1191,19 @@ class _EMAView:
 
 
 class Trainer(object):
-    """Sampling harness with the reference Trainer's surface (src/DADiff.py:1506-1966): `load`,
-    `sample`, `test`, `.accelerator.is_local_main_process`, `.results_folder`, `.train_logger`.
-    Training (`train`, `save`) is out of scope.  Unlike the reference (whose datasets glob
-    private paths inside the class), the evaluation dataset is passed in: any object with
-    `__len__`, `__getitem__ -> [ndct, ldct]` ((1,H,W) tensors in [0,1]) and `load_name(i)`."""
+    """The reference Trainer's surface (src/DADiff.py:1506-1966): `train`, `save`, `load`, `sample`, `test`,
+    `.accelerator.is_local_main_process`, `.results_folder`, `.train_logger`.  Unlike the reference (whose datasets glob
+    private paths inside the class), the datasets are passed in: `dataset` (evaluation) is any object with
+    `__len__`, `__getitem__ -> [ndct, ldct]` ((1,H,W) tensors in [0,1]) and `load_name(i)`; `train_dataset` needs the first two.
+    No augmentation is applied.  `seed` keys what train() draws (diffusion_train.train_batch_indices / train_t_and_seeds),
+    `log_every` is how often the loss is read back from the device.  One U-Net only (train() raises for two: RAdam)."""
 
     def __init__(self, opt, diffusion_model, folder=None, *, train_batch_size=16, gradient_accumulate_every=1,
                  augment_flip=True, train_lr=1e-4, train_num_steps=100000, ema_update_every=10, ema_decay=0.995,
                  adam_betas=(0.9, 0.99), save_and_sample_every=1000, num_samples=25, results_folder=".results/sample",
                  amp=False, fp16=False, split_batches=True, convert_image_to=None, condition=False, sub_dir=False,
                  equalizeHist=False, crop_patch=False, generation=False, num_unet=2, checkpoint_folder=None,
-                 is_train=True, train_logger=None, dataset=None, device=None):
+                 is_train=True, train_logger=None, dataset=None, device=None, train_dataset=None, seed=0, log_every=100):
         import logging
         import os as _os
         self.opt = opt
@@ -1097,18 +1223,45 @@ class Trainer(object):
         self.sample_dataset = dataset if dataset is not None else folder
         self.train_logger = train_logger or logging.getLogger("founddiff_amd")
         self.step = 0
+        self.train_dataset = train_dataset
+        self.batch_size, self.gradient_accumulate_every = int(train_batch_size), int(gradient_accumulate_every)
+        self.train_lr, self.adam_betas, self.train_num_steps = train_lr, tuple(adam_betas), int(train_num_steps)
+        self.ema_decay, self.ema_update_every = ema_decay, int(ema_update_every)
+        self.save_and_sample_every = int(save_and_sample_every)
+        self.seed, self.log_every = int(seed), int(log_every)
+        self.opt0 = None                     # ClipAdamEMA, made with the EMA copy at the first train() / save() / load(for_training=True)
+        self.losses = None                   # the last step's losses, on the device
+        self.batch_log = []                  # a debugging aid: the dataset indices train() drew, one list per micro-batch (the
+                                             # last 1024); diffusion_train.train_batch_indices gives the same without a run
+        self._stale = False                  # a step has written the weights since the engines were packed
         self.condition_type = 2
         self.test_running_psnr, self.test_running_ssim, self.test_running_rmse = [], [], []
 
-    def load(self, milestone):
+    def load(self, milestone, for_training=False):
         """Read `<ckpt>/sample/model-N.pt` = {'step','model','opt0','ema','scaler'}
         (src/DADiff.py:1648-1669).  The EMA weights win when present; a missing file is skipped
-        silently like the reference does."""
+        silently like the reference does.  for_training=True resumes instead: the online model takes 'model', the EMA copy
+        'ema', the optimiser 'opt0', and the step and EMA counters are restored, so that train() continues as the run that
+        saved would have."""
         from pathlib import Path
         path = Path(self.results_folder + "/" + f"model-{milestone}.pt")
         if not path.exists():
             return
         data = torch.load(str(path), map_location="cpu", weights_only=False)
+        if for_training:
+            index, n = self._setup_training()
+            step, model_sd, ema_sd, opt_sd = dt.checkpoint_unpack(data, index, n)
+            load_weights(self.model, model_sd, f"{path}['model']")
+            load_weights(self.ema.ema_model, ema_sd, f"{path}['ema']")
+            self.model.to(self.device)
+            self.ema.ema_model.to(self.device)
+            self.opt0.load_state_dict(opt_sd)
+            self.step = step
+            self._stale = False
+            self.model.weights_changed()
+            self.ema.ema_model.weights_changed()
+            print("load model - " + str(path))
+            return
         load_weights(self.model, data["model"], f"{path}['model']")
         self.step = data.get("step", 0)
         ema = data.get("ema")
@@ -1117,12 +1270,89 @@ class Trainer(object):
             if live:
                 load_weights(self.model, live, f"{path}['ema']")
         self.model.to(self.device)
+        getattr(self.model, "weights_changed", lambda: None)()
+        if self.ema.ema_model is not self.model:
+            # train() has made the EMA copy, and sample() / test() read it: it takes the same winning weights
+            self.ema.ema_model.load_state_dict(self.model.state_dict())
+            self.ema.ema_model.to(self.device)
+            self.ema.ema_model.weights_changed()
+            self._stale = False
         print("load model - " + str(path))
 
-    def train(self):
-        raise NotImplementedError("founddiff_amd is a sampling engine: training is out of scope")
+    # ---- training (src/DADiff.py:1626-1646, 1673-1763)
+    def _setup_training(self):
+        """The EMA copy and the optimiser, made once: (the places of the trainable parameters in diffusion.parameters(), their
+        number).  Until here self.ema.ema_model is self.model."""
+        dif = self.model
+        if getattr(dif.model, "num_unet", 1) != 1:
+            raise NotImplementedError("Trainer.train: two U-Nets are optimised with RAdam in the reference, which is not built "
+                                      "(DESIGN.md section 8)")
+        dif.model.unet0.trainable()
+        params = list(dif.parameters())
+        index = [i for i, p in enumerate(params) if p.requires_grad]
+        if self.opt0 is None:
+            if self.device.type != "cuda":
+                raise RuntimeError("Trainer.train: the model must live on the GPU (there is no CPU path)")
+            if self.ema.ema_model is dif:
+                self.ema = _EMAView(dif.clone())
+            eparams = list(self.ema.ema_model.parameters())
+            self.opt0 = dt.ClipAdamEMA([params[i] for i in index], [eparams[i] for i in index], lr=self.train_lr,
+                                       betas=self.adam_betas, max_norm=1.0, ema_beta=self.ema_decay,
+                                       ema_update_every=self.ema_update_every)
+        return index, len(params)
 
-    save = train
+    def _fresh_engines(self):
+        """before anything samples after a step has written the weights"""
+        if self._stale:
+            self.model.weights_changed()
+            if self.ema.ema_model is not self.model:
+                self.ema.ema_model.weights_changed()
+            self._stale = False
+
+    def train(self):
+        """The reference's loop (src/DADiff.py:1683-1732) from self.step to train_num_steps: gradient_accumulate_every micro-batches
+        through diffusion_train.train_step (clip 1.0, Adam, zero_grad, the EMA), a preview from the EMA model every
+        save_and_sample_every steps and save() on the reference's schedule (its FID run is not built).  Micro-batch m of step s,
+        its t and its noise are functions of (seed, s, m) alone; the losses stay on the device and are read every log_every
+        steps."""
+        self._setup_training()
+        ds = self.train_dataset
+        if ds is None or len(ds) < 1:
+            raise RuntimeError("Trainer.train: give the constructor a train_dataset (__len__, __getitem__ -> [ndct, ldct])")
+        if self.sample_dataset is None:
+            self.sample_dataset = ds
+        acc, every, T = self.gradient_accumulate_every, self.save_and_sample_every, self.model.num_timesteps
+        while self.step < self.train_num_steps:
+            batches, ts, seeds = [], [], []
+            for m in range(acc):
+                idx = dt.train_batch_indices(self.seed, self.step, m, self.batch_size, len(ds), acc)
+                self.batch_log.append(idx)
+                items = [ds[i] for i in idx]
+                batches.append([torch.stack([it[j] for it in items]).float().to(self.device) for j in range(2)])
+                t, sd = dt.train_t_and_seeds(self.seed, self.step, m, idx, T)
+                ts.append(torch.from_numpy(t).to(self.device))
+                seeds.append(torch.from_numpy(sd).to(self.device))
+            del self.batch_log[:-1024]
+            self.losses = dt.train_step(self.model, self.opt0, batches, t=ts, slice_seeds=seeds, step=self.step)
+            self._stale = True
+            self.step += 1
+            if self.log_every > 0 and self.step % self.log_every == 0:                 # the one synchronisation of these steps
+                self.train_logger.info("Iters: [%d/%d], loss_unet0: %.6f" % (self.step, self.train_num_steps, float(self.losses[0])))
+            if self.step % every == 0:
+                milestone = self.step // every
+                self.sample(milestone)
+                if self.step > every * 10 * 4 and self.step % (every * 10) == 0:
+                    self.save(milestone)
+        print("training complete")
+
+    def save(self, milestone):
+        """`<results>/model-N.pt` = {'step', 'model', 'opt0', 'ema', 'scaler': None} (src/DADiff.py:1626-1646;
+        diffusion_train.checkpoint_pack)."""
+        index, n = self._setup_training()
+        ema_sd = {k: v.detach().clone() for k, v in self.ema.ema_model.state_dict().items()}
+        model_sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        data = dt.checkpoint_pack(self.step, model_sd, ema_sd, self.opt0.state_dict(), index, n)
+        torch.save(data, self.results_folder + "/" + f"model-{milestone}.pt")
 
     # anatomy groups of the reference's 2020 test list, in item order: (name, slices per dose level); each holds
     # 4 dose levels back to back (src/DADiff.py:1918-1950).  "head" is taken from the END of the list, as there.
@@ -1136,7 +1366,8 @@ class Trainer(object):
         n = min(self.num_samples, len(self.sample_dataset))
         items = [self.sample_dataset[i] for i in range(n)]
         show = [torch.stack([it[j] for it in items]).to(self.device) for j in range(len(items[0]))]
-        outs = list(self.model.sample(show[1:], batch_size=n, last=last))
+        self._fresh_engines()
+        outs = list(self.ema.ema_model.sample(show[1:], batch_size=n, last=last))      # (the model itself until train() copies it)
         all_images_list = show + outs
         all_images = hu_window(torch.cat(all_images_list, dim=0))
         nrow = int(math.sqrt(self.num_samples)) if last else all_images.shape[0]
@@ -1196,7 +1427,8 @@ class Trainer(object):
         # summation order).  The switch is only ever turned ON here (FOUNDDIFF_LOW_LATENCY=1 stays in force for any batch
         # size) and is restored on the way out, so later sample() calls on the same model are not affected.  Cost: the
         # low-latency engine is a second DAEngine (its own weight copy, workspaces and graphs) next to the default one.
-        unets = [u for u in (getattr(getattr(self.model, "model", None), n, None) for n in ("unet0", "unet1"))
+        self._fresh_engines()
+        unets = [u for u in (getattr(getattr(self.ema.ema_model, "model", None), n, None) for n in ("unet0", "unet1"))
                  if u is not None and hasattr(u, "low_latency")]
         saved = [u.low_latency for u in unets]
         try:
@@ -1210,7 +1442,8 @@ class Trainer(object):
 
     def _test(self, sample, last, FID, batch_size):
         from .metrics import compute_metrics
-        self.model.init()
+        model = self.ema.ema_model                   # inference uses the EMA weights (src/DADiff.py:1818-1822)
+        model.init()
         print("test start")
         if not self.condition:
             if FID:
@@ -1235,10 +1468,10 @@ class Trainer(object):
             y = torch.stack([it[0] for it in items]).to(self.device)
             xs = [torch.stack([it[k] for it in items]).to(self.device) for k in range(1, len(items[0]))]
             if sample:
-                all_images_list = [y] + xs + list(self.model.sample(xs, batch_size=len(idx)))
+                all_images_list = [y] + xs + list(model.sample(xs, batch_size=len(idx)))
                 y_pred = all_images_list[-1]
             else:
-                y_pred = list(self.model.sample(xs, batch_size=len(idx), last=last))[-1]
+                y_pred = list(model.sample(xs, batch_size=len(idx), last=last))[-1]
                 # src/DADiff.py:1872-1886: the metrics use the UNCROPPED prediction; crop_patch only crops what is saved
                 m = compute_metrics(y_pred, y).cpu().numpy()
             y_save = y_pred

@@ -22,7 +22,12 @@ coefficient, the non-finite flag and Adam's step counts stay on the device).  Th
 The EMA schedule (ema_schedule) restates ema-pytorch as the reference constructs it (src/DADiff.py:1607).  ema_pytorch is not
 available where this project is tested, so that parity is UNPINNED: no test compares it with the package itself.
 
-chunk_table, ema_schedule, adam_state_unpack and adam_state_pack are pure host code.
+The checkpoint of DADiff.Trainer.save (checkpoint_pack / checkpoint_unpack) has the reference's five keys; whether its 'opt0' and
+'ema' entries load into torch.optim.Adam and ema-pytorch as the reference holds them, and theirs here, is UNPINNED for the same
+reason: no test reads a file written by either.
+
+chunk_table, ema_schedule, adam_state_unpack, adam_state_pack, train_batch_indices, train_t_and_seeds, checkpoint_pack and
+checkpoint_unpack are pure host code.
 """
 import numpy as np
 import torch
@@ -31,7 +36,8 @@ from . import _lib as L
 from ._train import empty, ptr, stream, workspace
 
 __all__ = ["q_sample", "residual_loss", "p_losses_fn", "p_losses", "ClipAdamEMA", "train_step", "chunk_table", "ema_schedule",
-           "adam_state_unpack", "adam_state_pack", "CHUNK"]
+           "adam_state_unpack", "adam_state_pack", "train_batch_indices", "train_t_and_seeds", "checkpoint_pack",
+           "checkpoint_unpack", "CHUNK"]
 
 CHUNK = 4096                      # elements of a parameter per workgroup (fd_opt_chunk_elems())
 _LOSS_TYPES = {"l1": 1, "l2": 2}
@@ -86,6 +92,85 @@ def adam_state_pack(steps, exp_avg, exp_avg_sq, group):
     state = {i: {"step": torch.tensor(float(s)), "exp_avg": exp_avg[i], "exp_avg_sq": exp_avg_sq[i]}
              for i, s in enumerate(steps) if s > 0}
     return {"state": state, "param_groups": [dict(group, params=list(range(len(steps))))]}
+
+
+# What Trainer.train draws is a pure function of (seed, step, micro-batch): no generator state lives in a checkpoint, and a run resumed
+# from one continues as the uninterrupted run would.
+_M64 = (1 << 64) - 1
+
+
+def _mix64(*words):
+    """splitmix64 folded over the words: a fixed 64-bit hash in plain integer arithmetic"""
+    h = 0x9E3779B97F4A7C15
+    for w in words:
+        h = (h ^ (int(w) & _M64)) & _M64
+        h = (h + 0x9E3779B97F4A7C15) & _M64
+        h = ((h ^ (h >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+        h = ((h ^ (h >> 27)) * 0x94D049BB133111EB) & _M64
+        h ^= h >> 31
+    return h
+
+
+def train_batch_indices(seed, step, micro, batch_size, n, accumulate=1):
+    """The dataset indices of micro-batch `micro` of step `step`: sample number k = (step accumulate + micro) batch_size + i is item
+    perm_e[k % n] of epoch e = k // n, perm_e a permutation of range(n) keyed by (seed, e).  Every epoch covers the dataset once,
+    wherever its ends fall in a batch."""
+    if batch_size < 1 or n < 1 or accumulate < 1 or not 0 <= micro < accumulate or step < 0:
+        raise RuntimeError(f"train_batch_indices: invalid arguments step={step} micro={micro} batch_size={batch_size} n={n} "
+                           f"accumulate={accumulate}")
+    k0 = (int(step) * accumulate + micro) * batch_size
+    out, perms = [], {}
+    for k in range(k0, k0 + batch_size):
+        e = k // n
+        if e not in perms:
+            perms[e] = np.random.default_rng([int(seed) & _M64, e]).permutation(n)
+        out.append(int(perms[e][k % n]))
+    return out
+
+
+def train_t_and_seeds(seed, step, micro, indices, num_timesteps):
+    """(t, slice_seeds), two int64 arrays, of the items `indices` of micro-batch `micro` of step `step`: t uniform in
+    [0, num_timesteps), keyed by (seed, step, micro); a slice's seed by (seed, step, micro, its dataset index), so that its noise
+    does not depend on what else is in its batch."""
+    t = np.random.default_rng([int(seed) & _M64, int(step), int(micro), 0x74]).integers(0, num_timesteps, len(indices), dtype=np.int64)
+    seeds = np.asarray([_mix64(seed, step, micro, i) >> 2 for i in indices], dtype=np.int64)        # 62 bits, as q_sample draws them
+    return t, seeds
+
+
+CHECKPOINT_KEYS = ("step", "model", "opt0", "ema", "scaler")
+
+
+def checkpoint_pack(step, model_sd, ema_model_sd, opt_sd, trainable_index, n_params):
+    """The dictionary of Trainer.save (src/DADiff.py:1626-1646): {'step', 'model', 'opt0', 'ema', 'scaler': None}.  opt_sd is
+    ClipAdamEMA.state_dict() over the trainable parameters; trainable_index[j] is the place of its parameter j in
+    diffusion.parameters(), n_params their number: 'opt0' has torch.optim.Adam's layout over ALL of them, the frozen ones (and
+    any that never took a step) without state.  'ema' holds ema_model.<key>, initted and step, as ema-pytorch names them."""
+    nt = len(trainable_index)
+    steps, m, v = adam_state_unpack(opt_sd, nt)
+    S, M, V = [0] * n_params, [None] * n_params, [None] * n_params
+    for j, i in enumerate(trainable_index):
+        S[i], M[i], V[i] = steps[j], m[j], v[j]
+    group = {k: val for k, val in opt_sd["param_groups"][0].items() if k != "params"}
+    ema = {"ema_model." + k: val for k, val in ema_model_sd.items()}
+    ema["initted"] = torch.tensor([bool(opt_sd.get("ema_copied", False))])
+    ema["step"] = torch.tensor([int(opt_sd.get("ema_step", 0))])
+    return {"step": int(step), "model": model_sd, "opt0": adam_state_pack(S, M, V, group), "ema": ema, "scaler": None}
+
+
+def checkpoint_unpack(data, trainable_index, n_params):
+    """the inverse: (step, model_sd, ema_model_sd, opt_sd) with opt_sd as ClipAdamEMA.load_state_dict takes it"""
+    if set(data) != set(CHECKPOINT_KEYS):
+        raise RuntimeError(f"checkpoint_unpack: expected the keys {CHECKPOINT_KEYS} (got {sorted(data)})")
+    S, M, V = adam_state_unpack(data["opt0"], n_params)
+    frozen = set(range(n_params)) - set(trainable_index)
+    if any(S[i] for i in frozen):
+        raise RuntimeError("checkpoint_unpack: 'opt0' holds state for a frozen parameter")
+    group = {k: val for k, val in data["opt0"]["param_groups"][0].items() if k != "params"}
+    opt_sd = adam_state_pack([S[i] for i in trainable_index], [M[i] for i in trainable_index], [V[i] for i in trainable_index], group)
+    ema = data["ema"]
+    opt_sd["ema_step"], opt_sd["ema_copied"] = int(ema["step"].reshape(-1)[0]), bool(ema["initted"].reshape(-1)[0])
+    ema_model_sd = {k[len("ema_model."):]: val for k, val in ema.items() if k.startswith("ema_model.")}
+    return int(data["step"]), data["model"], ema_model_sd, opt_sd
 
 
 # ---- argument checks: types and dtypes, then shapes, then devices, before anything launches ------------------------------------------

@@ -146,7 +146,9 @@ class DAEngine:
         """`dt` with the FD_OPT_* bits of this engine: the dtype argument of the kernels whose plan depends on them"""
         return self.dt | (L.FD_OPT_LOW_LATENCY if self.low_latency else 0) | (L.FD_OPT_F32_SPLIT if self.f32_split else 0)
 
-    def __init__(self, state_dict, prefix="", device="cuda", mode="bf16", low_latency=False):
+    def __init__(self, state_dict, prefix="", device="cuda", mode="bf16", low_latency=False, tower_only=False):
+        """tower_only: pack the frozen DA-CLIP encoder (dose_encoder.*) alone -- an engine for encode_dose, which is all that
+        training asks of it (DADiff.Unet.train_forward); forward() and encode_condition() need the whole model."""
         self.hip = L.F16 if mode == "fp16" else L.BF16    # which build of the C ABI this engine calls (founddiff_amd/_lib.py)
         self.hip.lib()  # fail loudly if the HIP library is missing
         DAEngine._GEN += 1
@@ -169,7 +171,10 @@ class DAEngine:
         self.dev = torch.device(device)
         self.f32 = dict(device=self.dev, dtype=torch.float32)
         sd = _Sub(state_dict, prefix)
-        self._pack(sd)
+        if tower_only:
+            self._pack_clip(sd.sub("dose_encoder."))
+        else:
+            self._pack(sd)
         self._plan_key = None
         self.buf = {}
         self.graphs, self.loop_graphs = {}, {}     # HIP graphs captured over this engine's buffers (ResidualDiffusion)
@@ -709,9 +714,10 @@ class DAEngine:
             self.conv(cw, xm, B, H, W, out, **epi)
 
     # ------------------------------------------------------------------ conditioning (once per slice)
-    def encode_condition(self, x_cond):
-        """DA-CLIP encoder + prompt path + per-block `local` vectors; t-independent (SURVEY Q6),
-        so it runs once per slice instead of once per step.  x_cond (B,1,H,W) fp32 in [-1,1]."""
+    def encode_dose(self, x_cond):
+        """The frozen DA-CLIP encoder alone: visual tower, the two heads and their L2 normalisations.  x_cond (B,1,H,W) fp32 in
+        [-1,1] -> dose (B, 1024), ctx (B, 256), fp32, in engine-owned buffers (the next call overwrites them).  Training
+        (DADiff.Unet.train_forward) stops here: the prompt path and the `local` vectors are trainable and run under autograd."""
         B, _, H, W = x_cond.shape
         s = self.stream
         cl = self.clip
@@ -768,6 +774,14 @@ class DAEngine:
         t2 = self.linear(t1, cl["h2"][2], cl["h2"][3], self._b("h2b", (B, cl["h2"][2].shape[0]), torch.float32))
         ctx = self._b("ctx_emb", t2.shape, torch.float32)
         self.hip.call("fd_l2norm_rows", _p(t2), _p(ctx), B, t2.shape[1], 1e-12, s)
+        return dose, ctx
+
+    def encode_condition(self, x_cond):
+        """DA-CLIP encoder + prompt path + per-block `local` vectors; t-independent (SURVEY Q6),
+        so it runs once per slice instead of once per step.  x_cond (B,1,H,W) fp32 in [-1,1]."""
+        B = x_cond.shape[0]
+        s = self.stream
+        dose, ctx = self.encode_dose(x_cond)
         # prompt path (src/DADiff.py:706-707)
         pr = self.prompt
         td = self.time_dim

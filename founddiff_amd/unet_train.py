@@ -8,7 +8,8 @@
 
 torch.cat runs on the last axis and there is no layout copy.  The frozen dose_encoder, the time / prompt MLPs and the two outer
 convolutions (init_conv 7x7 on 2 planes, final_conv 1x1 to 1 plane: weight gradients of 6 K and 64 elements) stay with torch, the
-latter two on channels-last memory.
+latter two on channels-last memory -- unless unet_trunk_forward is given init_fn / final_fn (outer_conv_train), as the project's
+own model does (DADiff.Unet.train_forward): then the whole step's activation work is on HIP kernels and deterministic.
 
 Binding for a training run:
 
@@ -34,10 +35,12 @@ def _nhwc(x):
     return x.permute(0, 2, 3, 1).contiguous()
 
 
-def unet_trunk_forward(self, x, time, dose_embedding, c):
+def unet_trunk_forward(self, x, time, dose_embedding, c, init_fn=None, final_fn=None):
     """Unet.forward after the dose encoder (src/DADiff.py:700-740) on the reference's attribute names: x (B, input_channels, H, W),
     time (B,), dose_embedding (B, context_dim), c (B, 1, 256) -> (B, out_dim, H, W).  H and W must be multiples of
-    2 ** (levels - 1), as in the reference (whose torch.cat fails otherwise)."""
+    2 ** (levels - 1), as in the reference (whose torch.cat fails otherwise).  init_fn(x, weight, bias) -> (B, H, W, dim) and
+    final_fn(x (B, H, W, dim), weight, bias) -> (B, 1, H, W) replace torch's two outer convolutions
+    (outer_conv_train.init_conv_fn / final_conv_fn); None: torch on channels-last memory."""
     named = (("x", x), ("time", time), ("dose_embedding", dose_embedding), ("c", c))
     for name, v in named:
         if not isinstance(v, torch.Tensor):
@@ -51,7 +54,10 @@ def unet_trunk_forward(self, x, time, dose_embedding, c):
     if x.shape[2] % (1 << (levels - 1)) or x.shape[3] % (1 << (levels - 1)):
         raise RuntimeError(f"unet_forward: unsupported shape H={x.shape[2]} W={x.shape[3]} (multiples of {1 << (levels - 1)}: every "
                            "Downsample needs an even size)")
-    x = _nhwc(self.init_conv(x.contiguous(memory_format=torch.channels_last)))
+    if init_fn is None:
+        x = _nhwc(self.init_conv(x.contiguous(memory_format=torch.channels_last)))
+    else:
+        x = init_fn(x.contiguous(), self.init_conv.weight, self.init_conv.bias)
     r = x
     t = self.time_mlp(time)
     prompt_embedding = torch.softmax(self.text_mlp(dose_embedding), dim=1) * self.prompt
@@ -75,7 +81,9 @@ def unet_trunk_forward(self, x, time, dose_embedding, c):
         x = resample_nhwc(upsample, x)
     x = torch.cat((x, r), dim=3)
     x = resnet_block_nhwc(self.final_res_block, x)
-    return self.final_conv(x.permute(0, 3, 1, 2))
+    if final_fn is None:
+        return self.final_conv(x.permute(0, 3, 1, 2))
+    return final_fn(x, self.final_conv.weight, self.final_conv.bias)
 
 
 def unet_forward(self, x, time, x_self_cond=None):

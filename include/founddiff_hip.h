@@ -726,6 +726,29 @@ int fd_opt_adam_ema_f32(const int64_t *chunks, const int64_t *tensors, const int
                         double lr, double beta1, double beta2, double eps, int ema_mode, double ema_decay, int zero_grad,
                         int skip_nonfinite, void *stream);
 
+/* ---- the two outer convolutions of the U-Net for training (fd_outer_train.hip; src/DADiff.py:553-555, 681) ----
+ * Exact fp32 on the VALU, deterministic, no float atomics, no host synchronisation; out and dx of a slice do not depend on its
+ * batch.  Byte bounds: DESIGN.md section 4.
+ * fd_init_conv7_fwd_f32: x [B][Cin][H][W] planes (Cin 2 or 3), weight [Cout][Cin][7][7], bias [Cout] -> out [B][H][W][Cout],
+ *   padding 3.  Cout a multiple of 32, at most 512.
+ * fd_init_conv7_wgrad_f32: g [49 Cin + 1][Cout]: g[(c 7 + kh) 7 + kw][co] = dweight[co][c][kh][kw], the last row dbias; one pass
+ *   over dout [B][H][W][Cout] (tiles of it and their halo of x in the LDS), split over at most 1024 ranges of tiles whose
+ *   partials two more launches add in order.  ws: fd_init_conv7_wgrad_ws_floats(...) floats (0: unsupported shape).
+ * fd_final_conv1_fwd_f32: out[p] = bias[0] + sum_c x[p][off + c] weight[c], x rows ld floats apart (a channel slice is read in
+ *   place; x points at the row start, ld and off multiples of 4).  C a multiple of 4, at most 1024; npix <= 2^30.
+ * fd_final_conv1_bwd_f32: dx [npix][C] = dout[p] weight[c]; dwb [C + 4] = dweight, dbias, 0, 0, 0; reads x and dout once.
+ *   ws: fd_final_conv1_bwd_ws_floats(npix, C) floats (0: unsupported shape). */
+int fd_init_conv7_fwd_f32(const float *x, const float *weight, const float *bias, float *out, int B, int Cin, int H, int W,
+                          int Cout, void *stream);
+int64_t fd_init_conv7_wgrad_ws_floats(int B, int Cin, int H, int W, int Cout);
+int fd_init_conv7_wgrad_f32(const float *x, const float *dout, float *g, float *ws, int B, int Cin, int H, int W, int Cout,
+                            void *stream);
+int fd_final_conv1_fwd_f32(const float *x, int ld, int off, const float *weight, const float *bias, float *out, int64_t npix,
+                           int C, void *stream);
+int64_t fd_final_conv1_bwd_ws_floats(int64_t npix, int C);
+int fd_final_conv1_bwd_f32(const float *x, int ld, int off, const float *weight, const float *dout, float *dx, float *dwb,
+                           float *ws, int64_t npix, int C, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
