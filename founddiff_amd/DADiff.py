@@ -1147,16 +1147,19 @@ class ResidualDiffusion(nn.Module):
         return dt.p_losses(self, imgs, t, noise, slice_seeds, step, scale)
 
     def forward(self, imgs, t=None, noise=None, slice_seeds=None, step=0):
-        """src/DADiff.py:1382-1397: imgs = [x_start, x_input], (B, 1, H, W) in [0, 1] -> the list of losses (one U-Net: one),
-        differentiable in the trunk's parameters.  t (B,) int64 is drawn as the reference draws it unless given; noise, or
+        """src/DADiff.py:1382-1397: imgs = [x_start, x_input], (B, 1, H, W) in [0, 1], or a diffusion_train.StoreBatch -> the list
+        of losses (one U-Net: one), differentiable in the trunk's parameters.  t (B,) int64 is drawn as the reference draws it unless given; noise, or
         slice_seeds (+ step) for the keyed per-slice stream, as diffusion_train.q_sample takes them.  RuntimeError for CPU tensors
         (there is no CPU path), NotImplementedError for two U-Nets."""
         fn = "ResidualDiffusion.forward"
         self._train_ready(fn)
         model_fn, schedule, objective, loss_type = dt._diffusion_args(fn, self)
-        if not isinstance(imgs, (list, tuple)) or len(imgs) != 2 or not all(isinstance(v, torch.Tensor) for v in imgs):
+        if isinstance(imgs, dt.StoreBatch):
+            if t is None:
+                t = torch.randint(0, self.num_timesteps, (len(imgs),), device=imgs.device).long()
+        elif not isinstance(imgs, (list, tuple)) or len(imgs) != 2 or not all(isinstance(v, torch.Tensor) for v in imgs):
             raise RuntimeError(f"{fn}: imgs must be [x_start, x_input] (condition=True without an input condition)")
-        if t is None:
+        elif t is None:
             t = torch.randint(0, self.num_timesteps, (imgs[0].shape[0],), device=imgs[0].device).long()
         return dt.p_losses_fn(model_fn, imgs, t, schedule, objective, loss_type, noise, slice_seeds, step, 1.0, normalize=True)
 
@@ -1195,7 +1198,10 @@ class Trainer(object):
     `.accelerator.is_local_main_process`, `.results_folder`, `.train_logger`.  Unlike the reference (whose datasets glob
     private paths inside the class), the datasets are passed in: `dataset` (evaluation) is any object with
     `__len__`, `__getitem__ -> [ndct, ldct]` ((1,H,W) tensors in [0,1]) and `load_name(i)`; `train_dataset` needs the first two.
-    No augmentation is applied.  `seed` keys what train() draws (diffusion_train.train_batch_indices / train_t_and_seeds),
+    `augment=True` applies the reference's RandomFlip + RandomRotate90 to every training pair (data/pdf_dataset.py:521-545), both
+    images under one transform, drawn per item by diffusion_train.train_augment; `augment_flip` is ignored, as before.
+    `train_dataset` may be a data.DeviceSliceStore: train() then gathers (and augments) every micro-batch on the device and
+    uploads no image.  `seed` keys what train() draws (diffusion_train.train_batch_indices / train_t_and_seeds / train_augment),
     `log_every` is how often the loss is read back from the device.  One U-Net only (train() raises for two: RAdam)."""
 
     def __init__(self, opt, diffusion_model, folder=None, *, train_batch_size=16, gradient_accumulate_every=1,
@@ -1203,7 +1209,8 @@ class Trainer(object):
                  adam_betas=(0.9, 0.99), save_and_sample_every=1000, num_samples=25, results_folder=".results/sample",
                  amp=False, fp16=False, split_batches=True, convert_image_to=None, condition=False, sub_dir=False,
                  equalizeHist=False, crop_patch=False, generation=False, num_unet=2, checkpoint_folder=None,
-                 is_train=True, train_logger=None, dataset=None, device=None, train_dataset=None, seed=0, log_every=100):
+                 is_train=True, train_logger=None, dataset=None, device=None, train_dataset=None, seed=0, log_every=100,
+                 augment=False):
         import logging
         import os as _os
         self.opt = opt
@@ -1229,6 +1236,7 @@ class Trainer(object):
         self.ema_decay, self.ema_update_every = ema_decay, int(ema_update_every)
         self.save_and_sample_every = int(save_and_sample_every)
         self.seed, self.log_every = int(seed), int(log_every)
+        self.augment = bool(augment)
         self.opt0 = None                     # ClipAdamEMA, made with the EMA copy at the first train() / save() / load(for_training=True)
         self.losses = None                   # the last step's losses, on the device
         self.batch_log = []                  # a debugging aid: the dataset indices train() drew, one list per micro-batch (the
@@ -1313,8 +1321,11 @@ class Trainer(object):
         """The reference's loop (src/DADiff.py:1683-1732) from self.step to train_num_steps: gradient_accumulate_every micro-batches
         through diffusion_train.train_step (clip 1.0, Adam, zero_grad, the EMA), a preview from the EMA model every
         save_and_sample_every steps and save() on the reference's schedule (its FID run is not built).  Micro-batch m of step s,
-        its t and its noise are functions of (seed, s, m) alone; the losses stay on the device and are read every log_every
-        steps."""
+        its t, its noise and (with augment) its flip / rot90 codes are functions of (seed, s, m) alone; the losses stay on the
+        device and are read every log_every steps.  From a data.DeviceSliceStore, or with augment, a micro-batch is a
+        diffusion_train.StoreBatch: its indices, codes, t and seeds go up as one table and nothing waits for the host; a host
+        dataset without augment is loaded, stacked and uploaded as before."""
+        from .data import DeviceSliceStore
         self._setup_training()
         ds = self.train_dataset
         if ds is None or len(ds) < 1:
@@ -1327,9 +1338,17 @@ class Trainer(object):
             for m in range(acc):
                 idx = dt.train_batch_indices(self.seed, self.step, m, self.batch_size, len(ds), acc)
                 self.batch_log.append(idx)
+                t, sd = dt.train_t_and_seeds(self.seed, self.step, m, idx, T)
+                if isinstance(ds, DeviceSliceStore) or self.augment:
+                    store, local = (ds, idx) if isinstance(ds, DeviceSliceStore) else \
+                        (DeviceSliceStore.from_items([ds[i] for i in idx], self.device), list(range(len(idx))))
+                    codes = dt.train_augment(self.seed, self.step, m, idx, store.H == store.W) if self.augment else None
+                    batches.append(dt.StoreBatch(store, local, codes))
+                    ts.append(t)
+                    seeds.append(sd)
+                    continue
                 items = [ds[i] for i in idx]
                 batches.append([torch.stack([it[j] for it in items]).float().to(self.device) for j in range(2)])
-                t, sd = dt.train_t_and_seeds(self.seed, self.step, m, idx, T)
                 ts.append(torch.from_numpy(t).to(self.device))
                 seeds.append(torch.from_numpy(sd).to(self.device))
             del self.batch_log[:-1024]

@@ -1,5 +1,5 @@
 // fd_train_common.h -- what the training kernels (fd_*_train.hip, fd_*_bwd.hip) share: the host-side size helpers, the sigmoid, the
-// fixed-order partial sum and the split-K tap correlation behind both convolution weight gradients.  Everything sits in an
+// four-element load / store, the fixed-order partial sum and the split-K tap correlation behind both convolution weight gradients.  Everything sits in an
 // anonymous namespace: each file that includes this header gets its own copy of the kernels it launches, and of no other.
 #pragma once
 #include <type_traits>
@@ -14,6 +14,29 @@ __device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rc
 int64_t round4(int64_t n) { return (n + 3) & ~(int64_t)3; }
 
 bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// n <= 4 floats at p: one 16-byte access when VEC (then n == 4), scalar otherwise; missing elements read as 0
+template <bool VEC>
+__device__ __forceinline__ void load4(const float *p, int n, float v[4]) {
+    if (VEC) {
+        const f32x4 q = *(const f32x4 *)p;
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = e < n ? p[e] : 0.f;
+    }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void store4(float *p, int n, const float v[4]) {
+    if (VEC) {
+        *(f32x4 *)p = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (e < n) p[e] = v[e];
+    }
+}
 
 // ---- the fixed-order partial sum -----------------------------------------------------------------------------------------------
 // out[b][j][q] = sum of p[b][m][q] over m in [j G, min((j + 1) G, M)) in order; p rows ldp floats apart, out rows ldo.  (This kernel,

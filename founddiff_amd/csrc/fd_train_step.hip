@@ -39,29 +39,6 @@ __device__ __forceinline__ float block_sum256(float v, float *red) {
     return red[0];
 }
 
-// n <= 4 floats at p: one 16-byte access when VEC (then n == 4), scalar otherwise; missing elements read as 0
-template <bool VEC>
-__device__ __forceinline__ void load4(const float *p, int n, float v[4]) {
-    if (VEC) {
-        const f32x4 q = *(const f32x4 *)p;
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = e < n ? p[e] : 0.f;
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store4(float *p, int n, const float v[4]) {
-    if (VEC) {
-        *(f32x4 *)p = f32x4{v[0], v[1], v[2], v[3]};
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (e < n) p[e] = v[e];
-    }
-}
-
 // ---- q_sample ------------------------------------------------------------------------------------------------------------------
 // grid (groups of four pixels / 256, b); one group per lane.  VEC: npix % 4 == 0 and every pointer 16-byte aligned.
 template <bool VEC, bool KEYED>

@@ -1,4 +1,5 @@
-"""CT slice I/O, the normalisation contract and the mixed-dose datasets on either side of the sampling path.
+"""CT slice I/O, the normalisation contract, the mixed-dose datasets on either side of the sampling path, and a paired dataset held
+on the GPU (DeviceSliceStore) whose batches a HIP kernel gathers and augments (csrc/fd_train_data.hip).
 
 Reference contract:
   * slices are `.npy` arrays in HU + 1024, stored (1, H, W) (`ToTensor(expand_dims=False)` asserts ndim 3,
@@ -20,6 +21,9 @@ import os
 
 import numpy as np
 import torch
+
+from . import _lib as L
+from ._train import empty, ptr, stream
 
 DOSE_LABELS = {0.5: 2, 0.33: 3, 0.25: 4, 0.20: 5, 0.17: 6, 0.12: 8, 0.10: 10, 0.05: 20}
 
@@ -207,3 +211,201 @@ class SyntheticCTDataset(torch.utils.data.Dataset):
 
     def load_name(self, index, sub_dir=False):
         return f"synthetic-quarter-{index:04d}.npy"
+
+
+def upload_table(rows, device):
+    """the int64 rows as one (len(rows), B) table on the device: one copy from pinned memory on the current stream, not waited
+    for (torch's pinned allocator keeps the block until the copy has left it)"""
+    tab = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(r, dtype=np.int64) for r in rows])))
+    return tab.pin_memory().to(device, non_blocking=True)
+
+
+def check_batch(fn, store, indices, codes):
+    """(indices, codes) of a batch from `store` as int64 arrays (codes None stays None): types, then shapes, then ranges"""
+    if not isinstance(store, DeviceSliceStore):
+        raise RuntimeError(f"{fn}: store must be a DeviceSliceStore (got {type(store).__name__})")
+    out = []
+    for name, v in (("indices", indices), ("codes", codes)):
+        if v is None and name == "codes":
+            out.append(None)
+            continue
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        try:
+            a = np.asarray(v)
+        except Exception:
+            a = None
+        if a is not None and a.size == 0:
+            a = a.astype(np.int64)                       # an empty list has no dtype of its own: its shape is what is wrong
+        if a is None or a.dtype.kind not in "iu":
+            raise RuntimeError(f"{fn}: {name} must be a sequence of integers (got {type(v).__name__}"
+                               f"{'' if a is None else ' of ' + str(a.dtype)})")
+        out.append(a.astype(np.int64))
+    idx, cd = out
+    if idx.ndim != 1 or idx.size < 1 or (cd is not None and cd.shape != idx.shape):
+        raise RuntimeError(f"{fn}: inconsistent shapes indices{idx.shape} codes{None if cd is None else cd.shape} (both (B,), B >= 1)")
+    if idx.size > 65535:
+        raise RuntimeError(f"{fn}: unsupported shape indices{idx.shape} (at most 65535 slices)")
+    if idx.min() < 0 or idx.max() >= len(store):
+        raise RuntimeError(f"{fn}: index {int(idx[(idx < 0) | (idx >= len(store))][0])} outside [0, {len(store)})")
+    if cd is not None:
+        if cd.min() < 0 or cd.max() >= 16:
+            raise RuntimeError(f"{fn}: code {int(cd[(cd < 0) | (cd >= 16)][0])} outside [0, 16)")
+        if store.H != store.W and (cd & 4).any():
+            raise RuntimeError(f"{fn}: code {int(cd[(cd & 4) != 0][0])} transposes (k odd), the store's slices are {store.H} x {store.W}")
+    return idx, cd
+
+
+class DeviceSliceStore:
+    """A paired dataset on the GPU in the form load_slice returns (fp32 in [0, 1], normalised on the host): nd (n_nd, H, W),
+    ld (n_ld, H, W) and nd_index (n_ld,) int64, on the host (nd_index) and on the device (nd_index_dev): item i is the pair
+    [nd[nd_index[i]], ld[i]], so several dose levels share one stored NDCT.  It has the dataset surface (__len__,
+    __getitem__ -> device views, load_name), so it also serves as `dataset=` of Trainer.sample / test; batch() gathers a batch
+    under the flip / rot90 codes of diffusion_train.train_augment in one launch (fd_store_gather_f32), and
+    diffusion_train.StoreBatch hands one to the training step without assembling it."""
+
+    def __init__(self, nd, ld, nd_index, names=None):
+        fn = "DeviceSliceStore"
+        for name, v in (("nd", nd), ("ld", ld)):
+            if not isinstance(v, torch.Tensor):
+                raise RuntimeError(f"{fn}: {name} must be a tensor (got {type(v).__name__})")
+            if v.dtype != torch.float32:
+                raise RuntimeError(f"{fn}: {name} must be float32 (got {v.dtype})")
+        idx = nd_index.detach().cpu().numpy() if isinstance(nd_index, torch.Tensor) else np.asarray(nd_index)
+        if idx.dtype.kind not in "iu":
+            raise RuntimeError(f"{fn}: nd_index must hold integers (got {idx.dtype})")
+        idx = idx.astype(np.int64)
+        if names is not None and not (isinstance(names, (list, tuple)) and all(isinstance(n, str) for n in names)):
+            raise RuntimeError(f"{fn}: names must be a list of strings")
+        shapes = f"nd{tuple(nd.shape)} ld{tuple(ld.shape)} nd_index{idx.shape}"
+        if nd.dim() != 3 or ld.dim() != 3 or nd.shape[1:] != ld.shape[1:] or idx.shape != (ld.shape[0],) or \
+                (names is not None and len(names) != ld.shape[0]):
+            raise RuntimeError(f"{fn}: inconsistent shapes {shapes} (nd (n_nd, H, W), ld (n_ld, H, W), nd_index and names (n_ld,))")
+        if nd.numel() < 1 or ld.numel() < 1:
+            raise RuntimeError(f"{fn}: the dataset is empty ({shapes})")
+        if nd.shape[1] > 32768 or nd.shape[2] > 32768:
+            raise RuntimeError(f"{fn}: unsupported shape {shapes} (H, W <= 32768)")
+        if idx.min() < 0 or idx.max() >= nd.shape[0]:
+            raise RuntimeError(f"{fn}: nd_index points outside nd ({shapes})")
+        for name, v in (("nd", nd), ("ld", ld)):
+            if not v.is_cuda:
+                raise RuntimeError(f"{fn}: {name} must live on the GPU (there is no CPU path)")
+        if ld.device != nd.device:
+            raise RuntimeError(f"{fn}: ld lives on {ld.device}, nd on {nd.device}")
+        self.nd, self.ld, self.nd_index = nd.contiguous(), ld.contiguous(), idx
+        self.nd_index_dev = torch.from_numpy(idx).to(nd.device)
+        self.names = None if names is None else list(names)
+        self.n_nd, self.n_ld, self.H, self.W = nd.shape[0], ld.shape[0], nd.shape[1], nd.shape[2]
+        self.device = nd.device
+
+    # ---- constructors: everything is checked on the host before the first upload
+    @staticmethod
+    def _device(fn, device):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError(f"{fn}: the store must live on the GPU (there is no CPU path; got device {dev})")
+        return dev
+
+    @staticmethod
+    def _slice(fn, v, what):
+        if isinstance(v, np.ndarray):
+            v = torch.from_numpy(v)
+        if not isinstance(v, torch.Tensor):
+            raise RuntimeError(f"{fn}: {what} must be a tensor (got {type(v).__name__})")
+        if v.dim() == 3 and v.shape[0] == 1:
+            v = v[0]
+        if v.dim() != 2 or v.numel() < 1:
+            raise RuntimeError(f"{fn}: unsupported shape {what}{tuple(v.shape)} (a slice is (1, H, W) or (H, W))")
+        return v.float()
+
+    @classmethod
+    def _from_slices(cls, fn, nd, ld, nd_index, names, device):
+        if not ld:
+            raise RuntimeError(f"{fn}: the dataset is empty")
+        shapes = {tuple(v.shape) for v in nd} | {tuple(v.shape) for v in ld}
+        if len(shapes) != 1:
+            raise RuntimeError(f"{fn}: mixed slice shapes {sorted(shapes)} (a store holds slices of one shape)")
+        dev = cls._device(fn, device)
+
+        def upload(rows, chunk=256):
+            out = torch.empty((len(rows),) + tuple(rows[0].shape), device=dev, dtype=torch.float32)
+            for s in range(0, len(rows), chunk):
+                out[s:s + chunk].copy_(torch.stack(rows[s:s + chunk]))
+            return out
+        return cls(upload(nd), upload(ld), np.asarray(nd_index, dtype=np.int64), names)
+
+    @classmethod
+    def from_items(cls, items, device):
+        """a list of [ndct, ldct] pairs ((1, H, W) or (H, W) each); one NDCT is stored per item"""
+        fn = "DeviceSliceStore.from_items"
+        if not isinstance(items, (list, tuple)):
+            raise RuntimeError(f"{fn}: items must be a list of [ndct, ldct] pairs (got {type(items).__name__})")
+        nd, ld = [], []
+        for k, it in enumerate(items):
+            if not isinstance(it, (list, tuple)) or len(it) != 2:
+                raise RuntimeError(f"{fn}: item {k} must be [ndct, ldct] (got {type(it).__name__})")
+            nd.append(cls._slice(fn, it[0], f"item {k}'s ndct"))
+            ld.append(cls._slice(fn, it[1], f"item {k}'s ldct"))
+        return cls._from_slices(fn, nd, ld, range(len(ld)), None, device)
+
+    @classmethod
+    def from_dataset(cls, ds, device):
+        """any object with __len__ and __getitem__ -> [ndct, ldct]; one NDCT is stored per item, load_name is kept if present"""
+        fn = "DeviceSliceStore.from_dataset"
+        if not hasattr(ds, "__len__") or not hasattr(ds, "__getitem__"):
+            raise RuntimeError(f"{fn}: ds must have __len__ and __getitem__ (got {type(ds).__name__})")
+        nd, ld = [], []
+        for k in range(len(ds)):
+            it = ds[k]
+            if not isinstance(it, (list, tuple)) or len(it) != 2:
+                raise RuntimeError(f"{fn}: item {k} must be [ndct, ldct] (got {type(it).__name__})")
+            nd.append(cls._slice(fn, it[0], f"item {k}'s ndct"))
+            ld.append(cls._slice(fn, it[1], f"item {k}'s ldct"))
+        names = [ds.load_name(k) for k in range(len(ds))] if hasattr(ds, "load_name") else None
+        return cls._from_slices(fn, nd, ld, range(len(ld)), names, device)
+
+    @classmethod
+    def from_mixed_dose(cls, ds, device):
+        """a MixedDoseTestDataset: every full-dose file is stored once, however many dose levels name it as their partner"""
+        fn = "DeviceSliceStore.from_mixed_dose"
+        if not isinstance(ds, MixedDoseTestDataset):
+            raise RuntimeError(f"{fn}: ds must be a MixedDoseTestDataset (got {type(ds).__name__})")
+        slots, nd, ld, nd_index = {}, [], [], []
+        for k in range(len(ds)):
+            f = ds.partner(k)
+            if f not in slots:
+                slots[f] = len(nd)
+                nd.append(cls._slice(fn, load_slice(f), f"the partner of item {k}"))
+            nd_index.append(slots[f])
+            ld.append(cls._slice(fn, load_slice(ds.q_path_list[k]), f"item {k}"))
+        return cls._from_slices(fn, nd, ld, nd_index, [ds.load_name(k) for k in range(len(ds))], device)
+
+    # ---- the dataset surface
+    def __len__(self):
+        return self.n_ld
+
+    def __getitem__(self, i):
+        i = int(i)
+        if not 0 <= i < self.n_ld:
+            raise IndexError(f"DeviceSliceStore: index {i} outside [0, {self.n_ld})")
+        return [self.nd[int(self.nd_index[i])][None], self.ld[i][None]]
+
+    def load_name(self, index, sub_dir=False):
+        return self.names[index] if self.names is not None else f"store-quarter-{int(index):06d}.npy"
+
+    @property
+    def nbytes(self):
+        return 4 * (self.nd.numel() + self.ld.numel()) + 8 * self.n_ld
+
+    def batch(self, indices, codes=None):
+        """(x_start, x_input), both (B, 1, H, W): items `indices` under the transform `codes` (diffusion_train.train_augment;
+        None: as stored), in one launch.  A transposing code (k odd) needs square slices."""
+        idx, cd = check_batch("DeviceSliceStore.batch", self, indices, codes)
+        B = len(idx)
+        with torch.no_grad(), torch.cuda.device(self.device):
+            tab = upload_table([self.nd_index[idx], idx] + ([] if cd is None else [cd]), self.device)
+            new = empty(self.device)
+            x_start, x_input = new(B, 1, self.H, self.W), new(B, 1, self.H, self.W)
+            L.call("fd_store_gather_f32", ptr(self.nd), ptr(self.ld), self.n_nd, self.n_ld, ptr(tab[0]), ptr(tab[1]),
+                   None if cd is None else ptr(tab[2]), ptr(x_start), ptr(x_input), B, self.H, self.W, stream(self.device))
+        return x_start, x_input

@@ -10,6 +10,9 @@
     p_losses(self, imgs, t, ...)                   the same on the reference's attribute names
     ClipAdamEMA(params, ema_params, ...)           clip_grad_norm_ + torch.optim.Adam + zero_grad + the EMA update: three launches
     train_step(diffusion_or_fn, opt, batch, ...)   p_losses -> backward per loss -> opt.step()
+    StoreBatch(store, indices, codes)              a micro-batch that stays in a data.DeviceSliceStore: accepted wherever
+                                                   [x_start, x_input] is; q_sample then gathers, flips / rotates and diffuses it in
+                                                   one launch (csrc/fd_train_data.hip), fed by one int64 table from pinned memory
 
 Binding for a training run:
 
@@ -26,18 +29,19 @@ The checkpoint of DADiff.Trainer.save (checkpoint_pack / checkpoint_unpack) has 
 'ema' entries load into torch.optim.Adam and ema-pytorch as the reference holds them, and theirs here, is UNPINNED for the same
 reason: no test reads a file written by either.
 
-chunk_table, ema_schedule, adam_state_unpack, adam_state_pack, train_batch_indices, train_t_and_seeds, checkpoint_pack and
-checkpoint_unpack are pure host code.
+chunk_table, ema_schedule, adam_state_unpack, adam_state_pack, train_batch_indices, train_t_and_seeds, train_augment,
+augment_source_index, checkpoint_pack and checkpoint_unpack are pure host code.
 """
 import numpy as np
 import torch
 
 from . import _lib as L
 from ._train import empty, ptr, stream, workspace
+from .data import check_batch, upload_table
 
 __all__ = ["q_sample", "residual_loss", "p_losses_fn", "p_losses", "ClipAdamEMA", "train_step", "chunk_table", "ema_schedule",
-           "adam_state_unpack", "adam_state_pack", "train_batch_indices", "train_t_and_seeds", "checkpoint_pack",
-           "checkpoint_unpack", "CHUNK"]
+           "adam_state_unpack", "adam_state_pack", "train_batch_indices", "train_t_and_seeds", "train_augment", "augment_source_index",
+           "StoreBatch", "checkpoint_pack", "checkpoint_unpack", "CHUNK"]
 
 CHUNK = 4096                      # elements of a parameter per workgroup (fd_opt_chunk_elems())
 _LOSS_TYPES = {"l1": 1, "l2": 2}
@@ -135,6 +139,33 @@ def train_t_and_seeds(seed, step, micro, indices, num_timesteps):
     t = np.random.default_rng([int(seed) & _M64, int(step), int(micro), 0x74]).integers(0, num_timesteps, len(indices), dtype=np.int64)
     seeds = np.asarray([_mix64(seed, step, micro, i) >> 2 for i in indices], dtype=np.int64)        # 62 bits, as q_sample draws them
     return t, seeds
+
+
+def train_augment(seed, step, micro, indices, square=True):
+    """The flip / rot90 code of every item of `indices` in micro-batch `micro` of step `step`, an int32 array: the low 4 bits of
+    _mix64(seed, step, micro, index, 0x61), keyed per item like the slice seeds, so an item's code does not depend on what else
+    is in its batch.  Bit 0 flips H, bit 1 flips W, bits 2-3 are k: the item becomes np.rot90(flip_W(flip_H(m)), k, (1, 2)), the
+    reference's RandomFlip + RandomRotate90 on a (1, H, W) slice (data/transforms.py:25-82; its flip over the axis of length 1
+    is the identity).  The 16 codes are uniform and reach the 8 elements of the dihedral group twice each.  square=False
+    clears bit 2: k is 0 or 2, the rotations a non-square slice keeps its shape under."""
+    codes = np.asarray([_mix64(seed, step, micro, i, 0x61) & 15 for i in indices], dtype=np.int32)
+    return codes if square else codes & ~np.int32(4)
+
+
+def augment_source_index(code, H, W):
+    """(i, j), two (Ho, Wo) integer arrays: output pixel (y, x) of the transform `code` is source pixel (i[y, x], j[y, x]) of the
+    (H, W) slice.  The formula the kernels of csrc/fd_train_data.hip implement, in numpy."""
+    code = int(code)
+    k = (code >> 2) & 3
+    if k & 1 and H != W:
+        raise RuntimeError(f"augment_source_index: code {code} transposes (k odd), the slice is {H} x {W}")
+    y, x = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    i, j = ((y, x), (x, W - 1 - y), (H - 1 - y, W - 1 - x), (H - 1 - x, y))[k]
+    if code & 2:
+        j = W - 1 - j
+    if code & 1:
+        i = H - 1 - i
+    return i, j
 
 
 CHECKPOINT_KEYS = ("step", "model", "opt0", "ema", "scaler")
@@ -249,15 +280,108 @@ def _check_qsample(fn, x_start, x_input, t, schedule, noise, slice_seeds, dims=(
     return ac, bc
 
 
-def q_sample(x_start, x_input, t, schedule, noise=None, slice_seeds=None, step=0, normalize=True):
+class StoreBatch:
+    """Items `indices` of a data.DeviceSliceStore under the transform `codes` (train_augment; None: as stored): a micro-batch
+    that is never assembled.  Accepted wherever [x_start, x_input] is (q_sample, p_losses_fn, p_losses, train_step,
+    ResidualDiffusion.forward / p_losses); the images are the store's, in [0, 1].  Everything is checked here: types, shapes,
+    then the ranges of the indices and the codes."""
+
+    def __init__(self, store, indices, codes=None):
+        self.indices, self.codes = check_batch("StoreBatch", store, indices, codes)
+        self.store = store
+
+    def __len__(self):
+        return len(self.indices)
+
+    @property
+    def device(self):
+        return self.store.device
+
+    @property
+    def shape(self):
+        return (len(self.indices), 1, self.store.H, self.store.W)
+
+
+def _check_qsample_store(fn, sb, t, schedule, noise, slice_seeds):
+    """t and slice_seeds may stay on the host (a sequence, an array or a CPU tensor of integers: they travel in the batch's table)
+    or be int64 tensors on the store's device.  Returns (ac, bc, t, slice_seeds), the host ones as int64 arrays."""
+    B = len(sb)
+
+    def ints(name, v):
+        if isinstance(v, torch.Tensor) and v.is_cuda:
+            _check_i64(fn, name, v)
+            return v
+        a = v.detach().numpy() if isinstance(v, torch.Tensor) else (np.asarray(v) if isinstance(v, (list, tuple, np.ndarray)) else None)
+        if a is None:
+            raise RuntimeError(f"{fn}: {name} must be a tensor or a sequence of integers (got {type(v).__name__})")
+        if a.dtype.kind not in "iu":
+            raise RuntimeError(f"{fn}: {name} must be int64 (got {a.dtype})")
+        return a.astype(np.int64)
+    _check_f32(fn, (("noise", noise),), optional=("noise",))
+    t = ints("t", t)
+    if slice_seeds is not None:
+        slice_seeds = ints("slice_seeds", slice_seeds)
+    if noise is not None and slice_seeds is not None:
+        raise RuntimeError(f"{fn}: give either noise or slice_seeds, not both")
+    ac, bc = _schedule_tables(fn, schedule)
+    shapes = " ".join(f"{n}{tuple(v.shape)}" for n, v in (("batch", sb), ("t", t), ("noise", noise), ("slice_seeds", slice_seeds))
+                      if v is not None)
+    if tuple(t.shape) != (B,) or (noise is not None and tuple(noise.shape) != sb.shape) or \
+            (slice_seeds is not None and tuple(slice_seeds.shape) != (B,)):
+        raise RuntimeError(f"{fn}: inconsistent shapes {shapes} (noise as the batch, t and slice_seeds (B,))")
+    for name, v in (("t", t), ("noise", noise), ("slice_seeds", slice_seeds)):
+        if isinstance(v, torch.Tensor) and v.device != sb.device:
+            raise RuntimeError(f"{fn}: {name} lives on {v.device}, the store on {sb.device}")
+    return ac, bc, t, slice_seeds
+
+
+def _q_sample_store(sb, t, schedule, noise, slice_seeds, step, normalize, x0_out):
+    fn = "q_sample"
+    ac, bc, t, slice_seeds = _check_qsample_store(fn, sb, t, schedule, noise, slice_seeds)
+    st, dev, B = sb.store, sb.device, len(sb)
+    with torch.no_grad(), torch.cuda.device(dev):
+        ac, bc = _upload_tables(ac, bc, dev)
+        if noise is None and slice_seeds is None:
+            slice_seeds = torch.randint(0, 1 << 62, (B,), device=dev, dtype=torch.int64)
+        # one table: the NDCT slots, the indices, then whichever of the codes, t and the seeds are on the host
+        rows, at = [st.nd_index[sb.indices], sb.indices], {}
+        for name, v in (("codes", sb.codes), ("t", t), ("seeds", slice_seeds)):
+            if isinstance(v, np.ndarray):
+                at[name] = len(rows)
+                rows.append(v)
+        tab = upload_table(rows, dev)
+        col = lambda name, v: tab[at[name]] if name in at else (None if v is None else v.contiguous())
+        codes, tt, seeds = col("codes", sb.codes), col("t", t), col("seeds", slice_seeds)
+        new = empty(dev)
+        x_in, x_res, times = new(B, 2, st.H, st.W), new(sb.shape), new(2, B)
+        x0 = new(sb.shape) if x0_out else None
+        if noise is None:
+            nz, out = None, new(sb.shape)
+        else:
+            nz, out = noise.detach().contiguous(), None
+        L.call("fd_res_qsample_store_f32", ptr(st.nd), ptr(st.ld), st.n_nd, st.n_ld, ptr(tab[0]), ptr(tab[1]), ptr(codes), ptr(tt),
+               ptr(ac), ptr(bc), ac.numel(), ptr(nz), ptr(seeds), int(step) & 0x7FFFFFFF, int(bool(normalize)), ptr(x_in), ptr(x_res),
+               ptr(out), ptr(times), ptr(x0), B, st.H, st.W, stream(dev))
+    res = (x_in, x_res, (noise if out is None else out), times)
+    return res + (x0,) if x0_out else res
+
+
+def q_sample(x_start, x_input, t, schedule, noise=None, slice_seeds=None, step=0, normalize=True, x0_out=False):
     """ResidualDiffusion.forward's normalize + p_losses' x_res, q_sample and cat (src/DADiff.py:1382-1388, 1412-1440, 1493-1497).
     x_start, x_input (B, 1, H, W) or (B, npix) fp32, in [0, 1] with normalize=True (2x - 1 is applied to both); t (B,) int64;
     schedule = DADiff.residual_schedule(T) (its alphas_cumsum and betas_cumsum are uploaded once).  noise as x_start, or
     slice_seeds (B,) int64: the noise of slice b is then fd_keyed_normal's stream of (slice_seeds[b], step), whatever its batch or
     rank.  With neither, the seeds are drawn from torch's generator of the device.
     Returns x_in (B, 2, ...) = cat(x_t, x_input), x_res = x_input - x_start, the noise, times (2, B) = alphas_cumsum[t] T,
-    betas_cumsum[t] T.  Nothing is differentiable."""
+    betas_cumsum[t] T; with x0_out a fifth result, the normalised x_start (pred_x0_noise's target).  Nothing is differentiable.
+    x_start may be a StoreBatch (x_input is then None): the gather, the flip / rot90 of its codes and all of the above are one
+    launch of fd_res_qsample_store_f32, bit for bit what store.batch() followed by this function gives; t and slice_seeds may
+    then stay on the host, and go up with the indices and the codes as one int64 table from pinned memory."""
     fn = "q_sample"
+    if isinstance(x_start, StoreBatch):
+        if x_input is not None:
+            raise RuntimeError(f"{fn}: with a StoreBatch x_input must be None (the batch holds both images)")
+        return _q_sample_store(x_start, t, schedule, noise, slice_seeds, step, normalize, x0_out)
     ac, bc = _check_qsample(fn, x_start, x_input, t, schedule, noise, slice_seeds)
     dev = x_start.device
     B = x_start.shape[0]
@@ -275,7 +399,14 @@ def q_sample(x_start, x_input, t, schedule, noise=None, slice_seeds=None, step=0
             nz, out, seeds = noise.detach().contiguous(), None, None
         L.call("fd_res_qsample_f32", ptr(x0), ptr(xi), ptr(tt), ptr(ac), ptr(bc), ac.numel(), ptr(nz), ptr(seeds), int(step) & 0x7FFFFFFF,
                int(bool(normalize)), ptr(x_in), ptr(x_res), ptr(out), ptr(times), B, npix, stream(dev))
-    return x_in, x_res, (noise if out is None else out), times
+        res = (x_in, x_res, (noise if out is None else out), times)
+        if x0_out:
+            xn = x0
+            if normalize:
+                xn = torch.empty_like(x_res)
+                L.call("fd_affine_f32", ptr(x0), 2.0, -1.0, ptr(xn), xn.numel(), stream(dev))
+            res += (xn,)
+    return res
 
 
 def _check_loss(fn, pred, target, loss_type, scale):
@@ -341,18 +472,19 @@ def p_losses_fn(model_fn, imgs, t, schedule, objective="pred_res", loss_type="l1
         raise RuntimeError(f"{fn}: unknown objective {objective!r}")
     if loss_type not in _LOSS_TYPES:
         raise RuntimeError(f"{fn}: invalid loss type {loss_type!r} ('l1' or 'l2')")
-    if not isinstance(imgs, (list, tuple)) or len(imgs) != 2:
-        raise RuntimeError(f"{fn}: imgs must be [x_start, x_input] (condition=True without an input condition)")
-    x_start, x_input = imgs
-    _check_qsample(fn, x_start, x_input, t, schedule, noise, slice_seeds, dims=(4,))
-    x_in, x_res, noise, times = q_sample(x_start, x_input, t, schedule, noise, slice_seeds, step, normalize)
+    want_x0 = objective == "pred_x0_noise"
+    if isinstance(imgs, StoreBatch):
+        _check_qsample_store(fn, imgs, t, schedule, noise, slice_seeds)
+        x_in, x_res, noise, times, *x0 = q_sample(imgs, None, t, schedule, noise, slice_seeds, step, normalize, x0_out=want_x0)
+    else:
+        if not isinstance(imgs, (list, tuple)) or len(imgs) != 2:
+            raise RuntimeError(f"{fn}: imgs must be [x_start, x_input] (condition=True without an input condition)")
+        x_start, x_input = imgs
+        _check_qsample(fn, x_start, x_input, t, schedule, noise, slice_seeds, dims=(4,))
+        x_in, x_res, noise, times, *x0 = q_sample(x_start, x_input, t, schedule, noise, slice_seeds, step, normalize, x0_out=want_x0)
     model_out = model_fn(x_in, [times[0], times[1]])
-    if objective == "pred_x0_noise":
-        x0 = x_start.detach()
-        if normalize:
-            x0 = torch.empty_like(x_res)
-            L.call("fd_affine_f32", ptr(x_start.detach().contiguous()), 2.0, -1.0, ptr(x0), x0.numel(), stream(x0.device))
-        target = [x0, noise]
+    if want_x0:
+        target = [x0[0], noise]
     else:
         target = {"pred_res": [x_res], "pred_noise": [noise], "pred_res_noise": [x_res, noise]}[objective]
     if not isinstance(model_out, (list, tuple)) or len(model_out) != len(target):
@@ -550,16 +682,20 @@ def train_step(diffusion_or_fn, opt, batch, t=None, noise=None, slice_seeds=None
     opt.step() (clip, Adam, zero_grad, EMA).  diffusion_or_fn: an object with the reference's ResidualDiffusion attributes, or a
     free model_fn(x_in, [time0, time1]) -> list of (B, 1, H, W) together with schedule, objective and loss_type.  batch:
     [x_start, x_input] in [0, 1] (normalize=True, as ResidualDiffusion.forward takes them), or a list of such pairs: the
-    micro-batches of gradient_accumulate_every, each loss scaled by one over their number.  t, noise and slice_seeds belong to the
+    micro-batches of gradient_accumulate_every, each loss scaled by one over their number.  A micro-batch may also be a StoreBatch
+    (one, or a list of them), whose t and slice_seeds may stay on the host.  t, noise and slice_seeds belong to the
     micro-batch (lists of them for several); t defaults to torch.randint(0, T, (B,)) as the reference draws it.  `step` keys the
     noise together with slice_seeds.  Returns the losses, one device tensor per U-Net, summed over the micro-batches."""
     fn = "train_step"
     if not isinstance(opt, ClipAdamEMA):
         raise RuntimeError(f"{fn}: opt must be a ClipAdamEMA (got {type(opt).__name__})")
+    single = isinstance(batch, StoreBatch)
+    if single:
+        batch = [batch]
     if not isinstance(batch, (list, tuple)) or not batch:
         raise RuntimeError(f"{fn}: batch must be [x_start, x_input] or a list of such pairs (got {type(batch).__name__})")
-    many = isinstance(batch[0], (list, tuple))
-    groups = list(batch) if many else [batch]
+    many = not single and isinstance(batch[0], (list, tuple, StoreBatch))
+    groups = list(batch) if many or single else [batch]
     if hasattr(diffusion_or_fn, "alphas_cumsum") and hasattr(diffusion_or_fn, "objective"):
         model_fn, schedule, objective, loss_type = _diffusion_args(fn, diffusion_or_fn)
     elif callable(diffusion_or_fn):
@@ -578,6 +714,8 @@ def train_step(diffusion_or_fn, opt, batch, t=None, noise=None, slice_seeds=None
     total = None
     for i, imgs in enumerate(groups):
         ti = pick(t, i)
+        if ti is None and isinstance(imgs, StoreBatch):
+            ti = torch.randint(0, ac.numel(), (len(imgs),), device=imgs.device).long()
         if ti is None:
             if not (isinstance(imgs, (list, tuple)) and len(imgs) == 2 and isinstance(imgs[0], torch.Tensor) and imgs[0].is_cuda):
                 raise RuntimeError(f"{fn}: a micro-batch must be [x_start, x_input] on the GPU (there is no CPU path)")

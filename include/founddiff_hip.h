@@ -726,6 +726,28 @@ int fd_opt_adam_ema_f32(const int64_t *chunks, const int64_t *tensors, const int
                         double lr, double beta1, double beta2, double eps, int ema_mode, double ema_decay, int zero_grad,
                         int skip_nonfinite, void *stream);
 
+/* ---- a training batch from a slice store on the device (fd_train_data.hip; data/pdf_dataset.py:521-545) -------
+ * nd [n_nd][H][W], ld [n_ld][H][W] fp32 in [0, 1].  Item b of the batch is the pair nd[nd_slot[b]], ld[ld_slot[b]] (int64 [B],
+ * clamped to the store), both under the transform codes[b] (int64 [B], low 4 bits; a null codes is all 0):
+ *   bit 0 flips H, bit 1 flips W, bits 2-3 = k: out = rot90(flip_W(flip_H(m)), k).  Source pixel (i, j) of output pixel (y, x):
+ *   k = 0 (y, x), 1 (x, W-1-y), 2 (H-1-y, W-1-x), 3 (H-1-x, y); then j = W-1-j if bit 1 and i = H-1-i if bit 0.  An odd k needs
+ *   H == W (it is dropped otherwise).  Even k: every lane owns 4 consecutive output pixels and reads 4 consecutive source
+ *   pixels; odd k: a workgroup owns a 64 x 64 output tile and turns it in the LDS (per pixel where W % 4 != 0 or a pointer
+ *   is not 16-byte aligned).  The form is chosen per slice.  B <= 65535, H, W <= 32768; no atomics, no host synchronisation.
+ * fd_store_gather_f32: x_start, x_input [B][H][W] = the two transformed images: a copy.
+ * fd_res_qsample_store_f32: fd_res_qsample_f32 on that batch without assembling it: the same arithmetic, and output pixel p
+ *   (row-major in the output) takes element p % 4 of the keyed stream's group p / 4, so every output has the bits of
+ *   fd_store_gather_f32 followed by fd_res_qsample_f32.  noise [B][H][W] is in output order.  x0 (nullable) [B][H][W] = the
+ *   normalised x_start (the target of pred_x0_noise). */
+int fd_store_gather_f32(const float *nd, const float *ld, int64_t n_nd, int64_t n_ld, const int64_t *nd_slot,
+                        const int64_t *ld_slot, const int64_t *codes, float *x_start, float *x_input, int B, int H, int W,
+                        void *stream);
+int fd_res_qsample_store_f32(const float *nd, const float *ld, int64_t n_nd, int64_t n_ld, const int64_t *nd_slot,
+                             const int64_t *ld_slot, const int64_t *codes, const int64_t *t, const float *alphas_cumsum,
+                             const float *betas_cumsum, int T, const float *noise, const int64_t *seeds, int noise_step,
+                             int normalize, float *x_in, float *x_res, float *noise_out, float *times, float *x0, int B,
+                             int H, int W, void *stream);
+
 /* ---- the two outer convolutions of the U-Net for training (fd_outer_train.hip; src/DADiff.py:553-555, 681) ----
  * Exact fp32 on the VALU, deterministic, no float atomics, no host synchronisation; out and dx of a slice do not depend on its
  * batch.  Byte bounds: DESIGN.md section 4.
