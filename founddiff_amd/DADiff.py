@@ -482,7 +482,6 @@ class ResidualDiffusion(nn.Module):
             u = getattr(self.model, name, None)
             for e in (getattr(u, "_engine", None) or {}).values():
                 e.graphs.clear()
-                e.loop_graphs.clear()
 
     def _hs(self):
         if self._host_sched is None:
@@ -696,36 +695,20 @@ class ResidualDiffusion(nn.Module):
         eng = eng or self._eng()
         run = (lambda: self._tail_forward(eng, tail_of, img, x_in, time_buf, mo)) if tail_of is not None else \
             (lambda: eng.forward(img, x_in, time_buf, out=mo))
-        key = (tuple(img.shape), eng.mode, eng.gen, tail_of.gen if tail_of is not None else 0, self.final_outer_levels, self.final_down_levels)
         if not self.use_graph:
             run()
             return
-        cache = eng.graphs                 # captured graphs live and die with the engine whose buffers they bake in
-        ent = cache.get(key)
-        if ent is None:
-            # warm-up (allocates every workspace buffer), then capture
-            run()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                run()
-            cache.clear()                                              # one step graph per engine
-            ent = cache[key] = (g, (x_in, img, time_buf, mo))
-        g, (gx, gi, gt, gm) = ent
-        if gx.data_ptr() != x_in.data_ptr():
-            gx.copy_(x_in)
-        if gi.data_ptr() != img.data_ptr():
-            gi.copy_(img)
-        if gt.data_ptr() != time_buf.data_ptr():
-            gt.copy_(time_buf)
+        # captured graphs live and die with the engine whose buffers they bake in
+        key = (tuple(img.shape), eng.mode, eng.gen, tail_of.gen if tail_of is not None else 0, self.final_outer_levels, self.final_down_levels)
+        bufs = (x_in, img, time_buf, mo)
+        g, baked = eng.captured("step", key, run, lambda capture: (capture(run), bufs))
+        if [t.data_ptr() for t in baked] != [t.data_ptr() for t in bufs]:
+            raise RuntimeError("_step_forward: the step graph of this engine was captured over other buffers than the ones passed "
+                               "(x_in, img, time_buf, mo must be the engine's loop buffers, _loop_buffers)")
         g.replay()
-        if gm.data_ptr() != mo.data_ptr():
-            mo.copy_(gm)
 
     def _loop_buffers(self, x_input, shape):
         eng = self._eng()
-        dev = x_input.device
-        f = dict(device=dev, dtype=torch.float32)
         x_in = eng._b("loop_xin", shape, torch.float32)
         x_in.copy_(x_input)
         img = eng._b("loop_img", shape, torch.float32)
@@ -750,6 +733,40 @@ class ResidualDiffusion(nn.Module):
         L.call("fd_keyed_normal", _p(seeds), int(t), _p(nz), shape[0], nz[0].numel(), _stream(nz))
         return nz
 
+    def _noise_and_seeds(self, path, size, dev, noise, slice_seeds, step_noise=None):
+        """The one rule for x_T and the per-slice seeds: (noise, seeds) as the sampler behind `path` takes them.  Paths of
+        _sample: "group" (the split into consecutive groups), "concurrent", "ddim", "ancestral"; "loop" is p_sample_loop itself.
+        Seeds that are not given are one torch.randint on the CPU generator (_slice_seeds), x_T without seeds one torch.randn
+        on the device; a None that is returned is drawn by the sampler it goes to."""
+        ddim = self.is_ddim_sampling and path != "loop"
+        seeds = lambda: self._slice_seeds(slice_seeds, size[0], dev)
+        keyed = lambda s: self._keyed_noise(s, self.X_T_STEP, size)
+        if path == "ancestral":                                   # p_sample_loop is an entry point of its own: it asks as "loop"
+            return noise, slice_seeds
+        if path == "group":
+            if noise is None:
+                noise = torch.randn(size, device=dev) if ddim and slice_seeds is None else keyed(seeds())
+            # known oddity: the ancestral sampler without slice_seeds draws them twice, once for x_T above and once for the steps
+            return noise, slice_seeds if ddim else seeds()
+        if ddim:
+            # known inconsistency (ADVICE.md, low): "concurrent" ignores slice_seeds while "ddim" and "group" key x_T on them, so a
+            # DDIM slice with seeds and no noise depends on its batch size
+            if path == "ddim" and noise is None and slice_seeds is not None:
+                noise = keyed(seeds())
+            return noise, None
+        s = seeds() if step_noise is None else None               # "loop", and "concurrent" ancestral (its step noise is keyed)
+        if noise is None:
+            noise = keyed(s) if s is not None else torch.randn(size, device=dev)
+        return noise, s
+
+    def _x_T(self, x_in, noise, img):
+        """img <- x_T = x_in + sqrt(sum_scale) * noise; returns a copy of it, the first image of what a loop returns"""
+        L.call("fd_axpy_f32", _p(x_in), _p(noise.contiguous()), math.sqrt(self.sum_scale), _p(img), img.numel(), _stream(img))
+        return img.clone()
+
+    def _finish(self, input_add_noise, img, img_list, last):
+        return unnormalize_to_zero_to_one([input_add_noise, img.clone()] if last else [input_add_noise] + img_list)
+
     @torch.no_grad()
     def p_sample_loop(self, x_input, shape, last=True, noise=None, step_noise=None, slice_seeds=None):
         """src/DADiff.py:1233-1273.  `noise`: the initial randn(shape); `step_noise`: callable t -> tensor (parity
@@ -765,14 +782,8 @@ class ResidualDiffusion(nn.Module):
         x_in, img, mo, time_buf = self._loop_buffers(x_input, shape)
         eng = self._eng()
         eng.encode_condition(x_in)
-        seeds = None
-        if step_noise is None:
-            seeds = self._slice_seeds(slice_seeds, shape[0], x_in.device)
-        if noise is None:
-            noise = self._keyed_noise(seeds, self.X_T_STEP, shape) if seeds is not None else torch.randn(shape, device=x_in.device)
-        L.call("fd_axpy_f32", _p(x_in), _p(noise.contiguous()), math.sqrt(self.sum_scale), _p(img), img.numel(),
-               _stream(img))
-        input_add_noise = img.clone()
+        noise, seeds = self._noise_and_seeds("loop", shape, x_in.device, noise, slice_seeds, step_noise)
+        input_add_noise = self._x_T(x_in, noise, img)
         hs = self._hs()
         T = self.num_timesteps
         B = shape[0]
@@ -796,11 +807,7 @@ class ResidualDiffusion(nn.Module):
                        img[0].numel(), _stream(img))
                 if not last:
                     img_list.append(img.clone())
-        if not last:
-            img_list = [input_add_noise] + img_list
-        else:
-            img_list = [input_add_noise, img.clone()]
-        return unnormalize_to_zero_to_one(img_list)
+        return self._finish(input_add_noise, img, img_list, last)
 
     def _ancestral_keyed(self, eng, e32, K, x_in, img, mo, time_buf, coefs, times, seeds, last, img_list):
         """The T ancestral steps with the timestep in a device counter: fd_ancestral_begin (t <- t - 1, UNet time
@@ -838,32 +845,22 @@ class ResidualDiffusion(nn.Module):
         # G steps per captured chunk: the largest divisor of n_main in [8, 64]; when there is none (n_main prime or
         # small) a fixed 40 with the n_main % 40 leftover steps run eagerly in front of the replays
         G = max([g for g in range(8, 65) if n_main > 0 and n_main % g == 0] or [40])
-        graphs = eng.__dict__.setdefault("anc_graphs", {})
         key = (tuple(img.shape), eng.mode, eng.gen, G, K, e32.gen if e32 else 0, self.final_outer_levels, self.final_down_levels, T)
         reps, rem = n_main // G, n_main % G
-        if key not in graphs:
-            start, t0 = img.clone(), t_dev.clone()
-            eng.forward(img, x_in, time_buf, out=mo)              # warm-up: every workspace buffer exists
+
+        def warm():
+            eng.forward(img, x_in, time_buf, out=mo)
             if e32 is not None:
                 self._tail_forward(e32, eng, img, x_in, time_buf, mo)
-            torch.cuda.synchronize()
-            gm = None
-            if reps > 0:
-                gm = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gm):
-                    for _ in range(G):
-                        one(eng)
-            gt = None
-            if K > 0:
-                gt = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gt):
-                    for _ in range(K):
-                        one(e32)
-            graphs.clear()
-            graphs[key] = (gm, gt)
-            img.copy_(start)
+
+        def record(capture):
+            start, t0 = img.clone(), t_dev.clone()
+            gm = capture(lambda: [one(eng) for _ in range(G)]) if reps > 0 else None
+            gt = capture(lambda: [one(e32) for _ in range(K)]) if K > 0 else None
+            img.copy_(start)                                      # capture does not execute: restore x_T and the step counter
             t_dev.copy_(t0)
-        gm, gt = graphs[key]
+            return gm, gt
+        gm, gt = eng.captured("anc", key, warm, record)
         lim = getattr(self, "_anc_max_chunks", None)          # bench.py's bounded leg: time a few chunks, not the volume
         if lim:
             reps, rem = min(reps, int(lim)), 0
@@ -900,9 +897,7 @@ class ResidualDiffusion(nn.Module):
         time_pairs = list(zip(times[:-1], times[1:]))
         if noise is None:
             noise = torch.randn(shape, device=x_in.device)
-        L.call("fd_axpy_f32", _p(x_in), _p(noise.contiguous()), math.sqrt(self.sum_scale), _p(img), img.numel(),
-               _stream(img))
-        input_add_noise = img.clone()
+        input_add_noise = self._x_T(x_in, noise, img)
         hs = self._hs()
         acs = hs["alphas_cumsum"]
         img_list = []
@@ -935,7 +930,7 @@ class ResidualDiffusion(nn.Module):
         if self.use_graph and last and os.environ.get("FOUNDDIFF_LOOP_GRAPH", "1") != "0":
             # the whole S-step loop as ONE HIP graph (S x (time fill + 141 kernels + DDIM update), every
             # scheduler constant baked into its node): replayed per sample() on the persistent loop buffers
-            key = ("ddim", tuple(shape), eng.mode, eng.gen, S, T, K, e32.gen if e32 else 0, self.final_outer_levels, self.final_down_levels,
+            key = (tuple(shape), eng.mode, eng.gen, S, T, K, e32.gen if e32 else 0, self.final_outer_levels, self.final_down_levels,
                    self.time_table)
 
             def fwd(e, sched=None, step=None):
@@ -943,30 +938,24 @@ class ResidualDiffusion(nn.Module):
                     e.forward(img, x_in, time_buf, out=mo, sched=sched, step=step)
                 else:
                     self._tail_forward(e, eng, img, x_in, time_buf, mo, sched=sched)
-            loops = eng.loop_graphs
-            if key not in loops:
-                start = img.clone()
+
+            def warm():
                 if self.time_table:                                # (host -> device copy and buffers: before the capture)
                     eng.time_table_prepare([acs[t] * T for t, _ in time_pairs], shape[0])
                     eng.time_cond_table()
                 for e in (eng, e32):
                     if e is not None:
-                        fwd(e)                                    # warm-up: every workspace buffer exists
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    run_steps(fwd, fold=True)
-                loops.clear()                                      # one loop graph per engine
-                loops[key] = g
+                        fwd(e)
+
+            def record(capture):
+                start = img.clone()
+                g = capture(lambda: run_steps(fwd, fold=True))
                 img.copy_(start)                                   # capture does not execute: restore x_T
-            loops[key].replay()
+                return g
+            eng.captured("ddim_loop", key, warm, record).replay()
         else:
             run_steps(lambda e: self._step_forward(x_in, img, time_buf, mo, e, tail_of=None if e is eng else eng))
-        if not last:
-            img_list = [input_add_noise] + img_list
-        else:
-            img_list = [input_add_noise, img.clone()]
-        return unnormalize_to_zero_to_one(img_list)
+        return self._finish(input_add_noise, img, img_list, last)
 
     def _generic_loop(self, x_in, shape, last, noise, step_noise, ddim):
         """p_sample_loop / ddim_sample for the objectives other than 'pred_res' and for the dual-UNet
@@ -976,9 +965,7 @@ class ResidualDiffusion(nn.Module):
         if noise is None:
             noise = torch.randn(shape, device=x_in.device)
         img = torch.empty_like(x_in)
-        L.call("fd_axpy_f32", _p(x_in), _p(noise.contiguous()), math.sqrt(self.sum_scale), _p(img), img.numel(),
-               _stream(img))
-        input_add_noise = img.clone()
+        input_add_noise = self._x_T(x_in, noise, img)
         hs = self._hs()
         T = self.num_timesteps
         img_list = []
@@ -1000,8 +987,7 @@ class ResidualDiffusion(nn.Module):
                 img, _ = self.p_sample(x_in, img, t, noise=nz, reuse_condition=True)
                 if not last:
                     img_list.append(img.clone())
-        img_list = [input_add_noise] + img_list if not last else [input_add_noise, img.clone()]
-        return unnormalize_to_zero_to_one(img_list)
+        return self._finish(input_add_noise, img, img_list, last)
 
     @torch.no_grad()
     def sample(self, x_input=0, batch_size=16, last=True, noise=None, step_noise=None, slice_seeds=None):
@@ -1039,11 +1025,7 @@ class ResidualDiffusion(nn.Module):
             dev = x_input[0].device
             batch_size = x_input[0].shape[0]
             size = tuple(x_input[0].shape)
-            if noise is None:
-                noise = (torch.randn(size, device=dev) if (self.is_ddim_sampling and slice_seeds is None) else
-                         self._keyed_noise(self._slice_seeds(slice_seeds, batch_size, dev), self.X_T_STEP, size))
-            if not self.is_ddim_sampling:
-                slice_seeds = self._slice_seeds(slice_seeds, batch_size, dev)
+            noise, slice_seeds = self._noise_and_seeds("group", size, dev, noise, slice_seeds)
             x01 = x_input[0]                             # (still the caller's [0, 1] tensor: the groups normalise their own slices)
             parts = []
             for g0 in range(0, batch_size, grp):
@@ -1060,18 +1042,13 @@ class ResidualDiffusion(nn.Module):
         # two concurrent sub-batches: DDIM, and the ancestral sampler when its step noise is the keyed stream
         nsl = self.streams if (self._is_shipped() and last and batch_size >= 8 and batch_size % self.streams == 0 and
                                (self.is_ddim_sampling or step_noise is None)) else 1
+        path = "concurrent" if nsl > 1 else "ddim" if self.is_ddim_sampling else "ancestral"
+        noise, seeds = self._noise_and_seeds(path, size, x_input[0].device, noise, slice_seeds)
         if nsl > 1:
-            seeds = None
-            if not self.is_ddim_sampling:
-                seeds = self._slice_seeds(slice_seeds, batch_size, x_input[0].device)
-                if noise is None:
-                    noise = self._keyed_noise(seeds, self.X_T_STEP, size)
             return self._sample_concurrent(x_input[0], size, noise, nsl, seeds)
         if self.is_ddim_sampling:
-            if noise is None and slice_seeds is not None:
-                noise = self._keyed_noise(self._slice_seeds(slice_seeds, batch_size, x_input[0].device), self.X_T_STEP, size)
             return self.ddim_sample(x_input, size, last=last, noise=noise)
-        return self.p_sample_loop(x_input, size, last=last, noise=noise, step_noise=step_noise, slice_seeds=slice_seeds)
+        return self.p_sample_loop(x_input, size, last=last, noise=noise, step_noise=step_noise, slice_seeds=seeds)
 
     def _sample_concurrent(self, x_in, size, noise, nsl, seeds=None):
         """Sampling of a batch (DDIM; ancestral with keyed step noise: `seeds`) as `nsl` independent sub-batches, each on its own HIP stream with its own engine
@@ -1101,14 +1078,11 @@ class ResidualDiffusion(nn.Module):
             finally:
                 self._slot = 0
             outs.append((st, o))
-        res = []
         for st, o in outs:
             main.wait_stream(st)
             for t in o:
                 t.record_stream(main)
-        for j in range(len(outs[0][1])):
-            res.append(torch.cat([o[j] for _, o in outs], 0))
-        return res
+        return [torch.cat([o[j] for _, o in outs], 0) for j in range(len(outs[0][1]))]
 
     # ---- training (src/DADiff.py:1382-1499)
     def weights_changed(self):

@@ -177,7 +177,27 @@ class DAEngine:
             self._pack(sd)
         self._plan_key = None
         self.buf = {}
-        self.graphs, self.loop_graphs = {}, {}     # HIP graphs captured over this engine's buffers (ResidualDiffusion)
+        self.graphs = {}     # kind ("step", "ddim_loop", "anc") -> (key, payload): HIP graphs over this engine's buffers (captured)
+
+    def captured(self, kind, key, warm, record):
+        """The payload of graphs[kind] if it was captured under `key`.  Otherwise warm() (eager forwards: every workspace buffer
+        exists), synchronize, payload = record(capture) with capture(fn) -> a CUDAGraph of fn's launches.  Capture does not execute:
+        record restores what its launches would have clobbered."""
+        ent = self.graphs.get(kind)
+        if ent is not None and ent[0] == key:
+            return ent[1]
+        warm()
+        torch.cuda.synchronize()
+
+        def capture(fn):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                fn()
+            return g
+        # ONE entry per kind: a new key replaces the kind's graph (and frees its nodes), another kind's stays.  Known cost: a batch
+        # that sample() splits into ragged groups (40 = 32 + 8) alternates two shapes, so every group re-captures its loop.
+        self.graphs[kind] = (key, record(capture))
+        return self.graphs[kind][1]
 
     # ------------------------------------------------------------------ packing
     def _f(self, t):

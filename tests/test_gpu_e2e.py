@@ -229,6 +229,45 @@ def test_ddim_tiny_bf16_drift(golden):
     assert l2rel(out, ref) < l2rel(pure, ref)
 
 
+def test_graph_cache_one_entry_per_kind(golden):
+    """DAEngine.graphs holds one (key, payload) per kind: a repeated sample() replays the same captured loop, the per-step graph
+    of a last=False run does not evict it, _drop_graphs empties the cache and the next call captures again -- same bits throughout."""
+    g, dif = _tiny_model(golden, "bf16")
+    x, nz = g["x_input"].cuda(), g["ddim.noise0"].cuda()
+    eng = dif._eng()
+    first = dif.sample([x], batch_size=2, last=True, noise=nz)[-1].clone()
+    assert set(eng.graphs) == {"ddim_loop"}
+    loop = eng.graphs["ddim_loop"][1]
+    dif.sample([x], batch_size=2, last=True, noise=nz)
+    assert eng.graphs["ddim_loop"][1] is loop
+    dif.sample([x], batch_size=2, last=False, noise=nz)
+    assert set(eng.graphs) == {"ddim_loop", "step"} and eng.graphs["ddim_loop"][1] is loop
+    third = dif.sample([x], batch_size=2, last=True, noise=nz)[-1]
+    assert eng.graphs["ddim_loop"][1] is loop and torch.equal(third, first)
+    dif._drop_graphs()
+    assert all(e.graphs == {} for e in dif.model.unet0._engine.values()) and len(dif.model.unet0._engine) >= 2
+    again = dif.sample([x], batch_size=2, last=True, noise=nz)[-1]
+    assert set(eng.graphs) == {"ddim_loop"} and eng.graphs["ddim_loop"][1] is not loop
+    assert torch.equal(again, first)
+
+
+def test_step_forward_refuses_other_buffers(golden):
+    """A step graph bakes in the four loop buffers it was captured over: _step_forward with another img raises on the host
+    (nothing is launched) instead of replaying over the old one."""
+    g, dif = _tiny_model(golden, "fp32")
+    x = g["x_input"].cuda()
+    dif.sample([x], batch_size=2, last=False, noise=g["ddim.noise0"].cuda())
+    eng = dif._eng()
+    entry = eng.graphs["step"]
+    x_in, img, mo, time_buf = dif._loop_buffers(x * 2 - 1, (2, 1, 64, 64))
+    assert [t.data_ptr() for t in entry[1][1]] == [t.data_ptr() for t in (x_in, img, time_buf, mo)]
+    before = mo.clone()
+    with pytest.raises(RuntimeError, match="captured over other buffers"):
+        dif._step_forward(x_in, img.clone(), time_buf, mo, eng)
+    torch.cuda.synchronize()
+    assert eng.graphs["step"] is entry and torch.equal(mo, before)
+
+
 def test_concurrent_half_batches_bitwise(golden):
     """ResidualDiffusion.sample runs a batch >= 8 as two half-batches on two HIP streams (own engines, own captured
     loop graphs): bit-identical to the single-stream run and to itself."""
@@ -555,8 +594,7 @@ def test_properties_512_bf16():
     eng = dif._eng()
     assert eng.z_recompute == 1 and eng.v_recompute and eng.down_fuse
     eng.z_recompute, eng.v_recompute, eng.down_fuse = 0, False, False
-    eng.loop_graphs.clear()
-    eng.graphs.clear()
+    dif._drop_graphs()
     c = dif.sample([x], batch_size=2, noise=nz)[-1]
     assert not torch.equal(a, c) and l2rel(a.float().cpu(), c.float().cpu()) < 2e-2
 
@@ -617,7 +655,7 @@ def test_ancestral_keyed_loop_properties(golden, prec):
     seeds = torch.arange(8, dtype=torch.int64) + 1000
     a = dif.sample([x8], batch_size=8, slice_seeds=seeds)[-1]               # two sub-batches of 4 on two streams
     assert torch.isfinite(a).all()
-    assert "anc_graphs" in dif._eng().__dict__
+    assert "anc" in dif._eng().graphs
     dif.streams = 1
     b = dif.sample([x8], batch_size=8, slice_seeds=seeds)[-1]               # one stream, graph chunks
     assert torch.equal(a, b)
