@@ -93,6 +93,7 @@ SIGNATURES = {
     "fd_selective_scan": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "fd_selective_scan_fuses_xproj": (i32, [i32, i32, i32, i32]),
     "fd_selective_scan_plan": (i32, [i32, i32, i32, i32, i32, i32]),
+    "fd_selective_scan_geom": (i32, [i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
     "fd_selective_scan_xproj": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "fd_selective_scan_fwd_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, vp, vp, vp]),
     "fd_selective_scan_bwd_ws_floats": (i64, [i32, i32, i32, i32, i64]),

@@ -933,37 +933,62 @@ static bool scan_cpl2_on() {
     return !off;
 }
 
+// Everything the launcher decides from the shape, in one place: launch_scan launches what this says and
+// fd_selective_scan_geom reports it, so the tests' coverage table (tests/scan_cases.py) cannot drift from the launcher.
+struct ScanPlan {
+    bool seq;       // the single-pass form; nothing below applies to it
+    bool two;       // two channels per lane
+    int cw, nw;     // channels per wave, waves per workgroup
+    int wgs;        // workgroups per chunk
+    int carry;      // scan_carry_kernel's PER (2, 8, 0), or -1: a single chunk, the carry-ins are a memset
+    size_t lds;     // dynamic LDS bytes of scan_chunk_kernel
+};
+
+// half: 16-bit storage; g.xw: the x_proj rows are computed inside phase A
+ScanPlan scan_plan(const ScanGeom &g, bool half) {
+    ScanPlan p = {};
+    p.seq = !g.xw && !g.low_latency && scan_seq_ok(g.H, g.W, g.D, g.N, g.R);
+    if (p.seq) return p;
+    // two channels per lane where the kernel is VALU-bound and the state is small (bf16, N <= 8); a function of the
+    // shape only
+    const int cpl = (half && g.N <= 4) ? 2 : 1;        // N = 8: measured slower (305 vs 293 us at 256x256, batch 8)
+    // (with the x_proj einsum inside phase A the two-channel form holds d_inner / 32 <= 4 pixel fragments per block)
+    // (not for ONE slice: a lone image has 2048 two-channel waves at level 0 for 1024 SIMDs; one channel per lane doubles
+    //  them: 155.7 -> 154.3 ms per 50-step slice at batch 1)
+    p.two = cpl == 2 && g.D % 128 == 0 && (!g.xw || g.D == 128) && scan_cpl2_on() && !g.low_latency;
+    p.cw = p.two ? 128 : 64;                           // channels per wave
+    p.nw = g.D >= 4 * p.cw ? 4 : g.D / p.cw;           // waves per workgroup
+    p.wgs = g.D / (p.cw * p.nw);
+    const size_t pad = fd_occ_pad(FD_DEV_PAD_SCAN);
+    // (+ 4 KB behind the rows: the u block of the two-channel phase A with the fused x_proj)
+    p.lds = (size_t)g.CL * ((g.CD + 3) & ~3) * sizeof(float) + (p.two && g.xw ? 4096 : 0) + pad;
+    const int per = (g.nch + SEG - 1) / SEG;           // chunks per segment of scan_carry_kernel
+    p.carry = g.nch <= 1 ? -1 : per <= 2 ? 2 : per <= 8 ? 8 : 0;
+    return p;
+}
+
 template <typename T, int N, int R, bool ODD>
 void launch_scan(const T *xc, const float *xdbl, const float *dtw, const float *dtb, const float *A,
                  const float *Ds, T *y, float *ws, const ScanGeom &g, hipStream_t s) {
-    if (!g.xw && !g.low_latency && scan_seq_ok(g.H, g.W, g.D, g.N, g.R)) {
+    const ScanPlan p = scan_plan(g, sizeof(T) == 2);
+    if (p.seq) {
         launch_scan_seq<T, N, R, ODD>(xc, xdbl, dtw, dtb, A, Ds, y, g, s);
         return;
     }
     const int64_t half = (int64_t)g.B * 4 * g.nch * g.N * g.D;
     float *wsH = ws, *wsP = ws + half;
-    // two channels per lane where the kernel is VALU-bound and the state is small (bf16, N <= 8); a function of the
-    // shape only
-    constexpr int CPL = (sizeof(T) == 2 && N <= 4) ? 2 : 1;     // N = 8: measured slower (305 vs 293 us at 256x256, batch 8)
-    // (with the x_proj einsum inside phase A the two-channel form holds d_inner / 32 <= 4 pixel fragments per block)
-    // (not for ONE slice: a lone image has 2048 two-channel waves at level 0 for 1024 SIMDs; one channel per lane doubles
-    //  them: 155.7 -> 154.3 ms per 50-step slice at batch 1)
-    const bool two = CPL == 2 && g.D % 128 == 0 && (!g.xw || g.D == 128) && scan_cpl2_on() && !g.low_latency;
-    const int cw = two ? 128 : 64;                     // channels per wave
-    const int nw = g.D >= 4 * cw ? 4 : g.D / cw;       // waves per workgroup
-    dim3 grid(g.nch * (g.D / (cw * nw)), g.B * 4), block(64 * nw);
-    const size_t pad = fd_occ_pad(FD_DEV_PAD_SCAN);
-    // (+ 4 KB behind the rows: the u block of the two-channel phase A with the fused x_proj)
-    const size_t lds = (size_t)g.CL * ((g.CD + 3) & ~3) * sizeof(float) + (two && g.xw ? 4096 : 0) + pad;
+    constexpr int CPL = (sizeof(T) == 2 && N <= 4) ? 2 : 1;     // the only instantiation scan_plan's `two` can ask for
+    const bool two = CPL == 2 && p.two;
+    dim3 grid(g.nch * p.wgs, g.B * 4), block(64 * p.nw);
+    const size_t lds = p.lds;
     if (two) hipLaunchKernelGGL((scan_chunk_kernel<T, N, R, false, ODD, CPL>), grid, block, lds, s, xc, xdbl, dtw, dtb, A, Ds, y, wsH, wsP, g);
     else hipLaunchKernelGGL((scan_chunk_kernel<T, N, R, false, ODD>), grid, block, lds, s, xc, xdbl, dtw, dtb, A, Ds, y, wsH, wsP, g);
-    if (g.nch > 1)
+    if (p.carry >= 0)
     {
-        const int per = (g.nch + SEG - 1) / SEG;
         const dim3 cgrid(g.B * 4 * g.N * (g.D / 64)), cblock(64 * SEG);
         const float asc = sizeof(T) == 2 ? 1.f : 1.4426950408889634f;
-        if (per <= 2) hipLaunchKernelGGL(scan_carry_kernel<2>, cgrid, cblock, 0, s, wsH, wsP, A, asc, g.nch, g.N, g.D);
-        else if (per <= 8) hipLaunchKernelGGL(scan_carry_kernel<8>, cgrid, cblock, 0, s, wsH, wsP, A, asc, g.nch, g.N, g.D);
+        if (p.carry == 2) hipLaunchKernelGGL(scan_carry_kernel<2>, cgrid, cblock, 0, s, wsH, wsP, A, asc, g.nch, g.N, g.D);
+        else if (p.carry == 8) hipLaunchKernelGGL(scan_carry_kernel<8>, cgrid, cblock, 0, s, wsH, wsP, A, asc, g.nch, g.N, g.D);
         else hipLaunchKernelGGL(scan_carry_kernel<0>, cgrid, cblock, 0, s, wsH, wsP, A, asc, g.nch, g.N, g.D);
     }
     else
@@ -1038,22 +1063,42 @@ extern "C" int64_t fd_scan_ws_floats(int B, int H, int W, int D, int N) {
     return 2 * (int64_t)B * 4 * g.nch * N * D;
 }
 
+// The shape checks of a scan call and its geometry: what scan_entry refuses, fd_selective_scan_geom refuses too.  g->xw is left
+// NULL (the caller's pointer, or a placeholder for the query, goes there when `fused`).
+static int scan_shape(int dtype_opts, bool fused, int B, int H, int W, int D, int N, int R, ScanGeom *g) {
+    FD_REQUIRE(B > 0 && H > 0 && W > 0, "fd_selective_scan: bad batch / image size %d x %d x %d", B, H, W);
+    FD_REQUIRE(D > 0 && D % 64 == 0, "fd_selective_scan: d_inner=%d must be a multiple of 64", D);
+    FD_REQUIRE((int64_t)H * W * D * 4 < (1ll << 31), "fd_selective_scan: one image must stay below 2^31 bytes");
+    FD_REQUIRE((N == 4 || N == 8 || N == 16 || N == 32) && (R == 2 || R == 4 || R == 8 || R == 16 || R == 32),
+               "fd_selective_scan: unsupported d_state=%d / dt_rank=%d (need N in {4,8,16,32}, R in {2,4,8,16,32})", N, R);
+    if (fused)
+        FD_REQUIRE(fd_selective_scan_fuses_xproj(dtype_opts & (0xff | FD_OPT_F32_SPLIT), D, N, R), "fd_selective_scan_xproj: not available for this shape "
+                   "(bf16 or fp32 | FD_OPT_F32_SPLIT, d_inner <= 256, (R + 2N) %% 4 == 0): D=%d N=%d R=%d", D, N, R);
+    *g = make_geom(B, H, W, D, N, R, (dtype_opts & FD_OPT_LOW_LATENCY) != 0);
+    return FD_OK;
+}
+
+// The chunk kernel's row buffer is held to 64 KiB.  Rows of N = 32 (68 floats with R <= 4, up to 96 with R = 32) in 256-step
+// chunks (d_inner * L >= 2^24: beyond every size the model runs at, never launched by a test) would need 68-96 KiB.
+static int scan_lds_ok(const ScanGeom &g, const ScanPlan &p) {
+    FD_REQUIRE(p.seq || p.lds <= 65536, "fd_selective_scan: %d-step chunks of %d-float rows need %zu bytes of LDS (limit 65536): "
+               "D=%d N=%d R=%d at %d x %d is not supported", g.CL, g.CD, p.lds, g.D, g.N, g.R, g.H, g.W);
+    return FD_OK;
+}
+
 static int scan_entry(int dtype_opts, const void *xc, const void *x_proj_w, float *xdbl, const float *dtw, const float *dtb,
                       const float *A, const float *Ds, void *y, float *ws, int B, int H, int W, int D, int N, int R,
                       void *stream) {
     const int dtype = dtype_opts & 0xff;
     FD_REQUIRE(xc && xdbl && dtw && dtb && A && Ds && y && ws, "fd_selective_scan: null pointer");
-    FD_REQUIRE(H > 0 && W > 0, "fd_selective_scan: bad image size %d x %d", H, W);
-    FD_REQUIRE(D % 64 == 0, "fd_selective_scan: d_inner=%d must be a multiple of 64", D);
-    FD_REQUIRE((int64_t)H * W * D * 4 < (1ll << 31), "fd_selective_scan: one image must stay below 2^31 bytes");
-    ScanGeom g = make_geom(B, H, W, D, N, R, (dtype_opts & FD_OPT_LOW_LATENCY) != 0);
+    ScanGeom g;
+    if (int rc = scan_shape(dtype_opts, x_proj_w != nullptr, B, H, W, D, N, R, &g)) return rc;
     if (x_proj_w) {
-        FD_REQUIRE(fd_selective_scan_fuses_xproj(dtype_opts & (0xff | FD_OPT_F32_SPLIT), D, N, R), "fd_selective_scan_xproj: not available for this shape "
-                   "(bf16 or fp32 | FD_OPT_F32_SPLIT, d_inner <= 256, (R + 2N) %% 4 == 0): D=%d N=%d R=%d", D, N, R);
         FD_REQUIRE(((uintptr_t)x_proj_w & 15) == 0 && ((uintptr_t)xc & 15) == 0, "fd_selective_scan_xproj: 16-byte alignment");
         g.xw = x_proj_w;
         g.xdbl_out = xdbl;
     }
+    if (int rc = scan_lds_ok(g, scan_plan(g, dtype == FD_BF16))) return rc;
     int rc = dtype == FD_BF16
                  ? dispatch_n<bf16>((const bf16 *)xc, xdbl, dtw, dtb, A, Ds, (bf16 *)y, ws, g, (hipStream_t)stream)
                  : dispatch_n<float>((const float *)xc, xdbl, dtw, dtb, A, Ds, (float *)y, ws, g, (hipStream_t)stream);
@@ -1087,6 +1132,27 @@ extern "C" int fd_selective_scan_fuses_xproj(int dtype_opts, int D, int N, int R
 extern "C" int fd_selective_scan_plan(int dtype_opts, int D, int N, int R, int H, int W) {
     const bool seq = !(dtype_opts & FD_OPT_LOW_LATENCY) && scan_seq_ok(H, W, D, N, R);
     return fd_selective_scan_fuses_xproj(dtype_opts & (0xff | FD_OPT_F32_SPLIT), D, N, R) && !seq;
+}
+
+// What a call of fd_selective_scan (fused = 0) / fd_selective_scan_xproj (fused = 1) with these arguments launches: scan_plan's
+// answer, host only.  out is filled whenever the shape itself is valid, also when the call is refused for its LDS size.
+extern "C" int fd_selective_scan_geom(int dtype_opts, int fused, int D, int N, int R, int H, int W, int32_t out[8]) {
+    FD_REQUIRE(out, "fd_selective_scan_geom: null pointer");
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    ScanGeom g;
+    if (int rc = scan_shape(dtype_opts, fused != 0, 1, H, W, D, N, R, &g)) return rc;
+    if (fused) g.xw = out;                              // any non-NULL value: only tested, never read
+    const ScanPlan p = scan_plan(g, (dtype_opts & 0xff) == FD_BF16);
+    if (p.seq) return FD_OK;
+    out[0] = 1;
+    out[1] = g.CL;
+    out[2] = g.nch;
+    out[3] = p.two ? 2 : 1;
+    out[4] = p.nw;
+    out[5] = p.wgs;
+    out[6] = p.carry;
+    out[7] = (int32_t)p.lds;
+    return scan_lds_ok(g, p);
 }
 
 extern "C" int fd_selective_scan_xproj(int dtype, const void *xc, const void *x_proj_w, float *xdbl, const float *dtw,

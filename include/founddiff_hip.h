@@ -341,6 +341,16 @@ int fd_selective_scan_xproj(int dtype, const void *xc, const void *x_proj_w, flo
 /* 1: call fd_selective_scan_xproj for this block; 0: run the x_proj launch, then fd_selective_scan (the single-pass
  * form takes its x_dbl rows from the workspace).                                                              */
 int fd_selective_scan_plan(int dtype, int D, int N, int R, int H, int W);
+/* Which device code a call of fd_selective_scan (fused = 0) or fd_selective_scan_xproj (fused = 1) with this dtype (options
+ * included) and shape runs -- the launcher's own decisions, host only, a function of the shape and never of B:
+ *   out[0] form: 0 single-pass, 1 chunked; for the single-pass form out[1..7] are 0
+ *   out[1] chunk length            out[2] number of chunks
+ *   out[3] channels per lane (1, 2) out[4] waves per workgroup      out[5] workgroups per chunk
+ *   out[6] carry kernel: -1 none (a single chunk), else chunks per segment held in registers (2, 8) or 0 (two passes)
+ *   out[7] dynamic LDS bytes of the chunk kernel
+ * Returns what the call itself would return for the shape: an error for an unsupported one, also where the chunk kernel
+ * would need more than 64 KiB of LDS (N = 32 in 256-step chunks, d_inner * L >= 2^24; out is filled all the same).     */
+int fd_selective_scan_geom(int dtype, int fused, int D, int N, int R, int H, int W, int32_t out[8]);
 
 /* ---- The reference's own native-op interface (the only one it has):
  *     out, x, *rest = selective_scan_cuda_core.fwd(u, delta, A, B, C, D, delta_bias, delta_softplus, nrows)

@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import HB, gate2x, rel_err, use_half_build
+from scan_cases import scan_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -383,15 +384,7 @@ def test_selective_scan(eng_factory, mode, tol, cfg):
     A = -torch.exp(torch.log(torch.arange(1, N + 1).float())[None].repeat(4 * D, 1) + 0.1 * torch.randn(4 * D, N))
     Ds = 1 + 0.1 * torch.randn(4 * D)
     # oracle on the explicitly gathered tensors
-    xs = nets.efficient_scan(xc)                                                    # (B,4,D,L) in scan order
-    xd = xdbl.permute(1, 0, 2, 3).reshape(B, 4, H2, W2, CD)
-    xd_scan = torch.stack([xd[:, 0].reshape(B, Lq, CD), xd[:, 1].transpose(1, 2).reshape(B, Lq, CD),
-                           xd[:, 2].reshape(B, Lq, CD), xd[:, 3].transpose(1, 2).reshape(B, Lq, CD)], 1)
-    dts = torch.einsum("bklr,kdr->bkdl", xd_scan[..., :R], dtw)
-    Bs = xd_scan[..., R:R + N].permute(0, 1, 3, 2).contiguous()
-    Cs = xd_scan[..., R + N:].permute(0, 1, 3, 2).contiguous()
-    ys = nets.selective_scan(xs.reshape(B, 4 * D, Lq), dts.reshape(B, 4 * D, Lq), A, Bs, Cs, Ds, dtb.reshape(-1))
-    ref = nets.efficient_merge(ys.view(B, 4, D, Lq), H, W).view(B, D, H, W)
+    ref, _ = scan_reference(xc, dtw, dtb, A, Ds, N, R, xdbl=xdbl, scan_fn=nets.selective_scan)
     nws = L.lib().fd_scan_ws_floats(B, H, W, D, N)
     ws = torch.empty(nws, device="cuda")
     y = torch.empty(B, H, W, D, device="cuda", dtype=e.tdt)
@@ -1120,16 +1113,8 @@ def test_selective_scan_fused_xproj(cfg):
     dtb = torch.randn(4, D) * 0.5 - 3
     A = -torch.exp(torch.log(torch.arange(1, N + 1).float())[None].repeat(4 * D, 1) + 0.1 * torch.randn(4 * D, N))
     Ds = 1 + 0.1 * torch.randn(4 * D)
-    xs = nets.efficient_scan(xc)                                   # (B,4,D,L) in scan order, zero-padded when odd
-    xd_scan = torch.einsum("bkdl,kcd->bklc", xs, xw)               # rows in scan order
-    dts = torch.einsum("bklr,kdr->bkdl", xd_scan[..., :R], dtw)
-    Bs = xd_scan[..., R:R + N].permute(0, 1, 3, 2).contiguous()
-    Cs = xd_scan[..., R + N:].permute(0, 1, 3, 2).contiguous()
-    ys = nets.selective_scan(xs.reshape(B, 4 * D, Lq), dts.reshape(B, 4 * D, Lq), A, Bs, Cs, Ds, dtb.reshape(-1))
-    ref = nets.efficient_merge(ys.view(B, 4, D, Lq), H, W).view(B, D, H, W)
-    # x_dbl rows are stored at row index h2 * W2 + w2 whatever the direction's scan order
-    xd_rows = torch.stack([xd_scan[:, 0], xd_scan[:, 1].reshape(B, W2, H2, CD).transpose(1, 2).reshape(B, Lq, CD),
-                           xd_scan[:, 2], xd_scan[:, 3].reshape(B, W2, H2, CD).transpose(1, 2).reshape(B, Lq, CD)], 0)
+    # the CPU einsum + sequential oracle; x_dbl rows at row index h2 * W2 + w2 whatever the direction's scan order
+    ref, xd_rows = scan_reference(xc, dtw, dtb, A, Ds, N, R, xw=xw, scan_fn=nets.selective_scan)
     ws = torch.empty(L.lib().fd_scan_ws_floats(B, H, W, D, N), device="cuda")
     y = torch.empty(B, H, W, D, device="cuda", dtype=HB.t)
     xdbl = torch.full((4, B, Lq, CD), float("nan"), device="cuda")
