@@ -99,6 +99,8 @@ SIGNATURES = {
     "fd_selective_scan_bwd_ws_floats": (i64, [i32, i32, i32, i32, i64]),
     "fd_selective_scan_bwd_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64,
                                         vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "fd_selective_scan_bwd_geom": (i32, [i32, i32, i32, i32, i64, C.POINTER(i32)]),
+    "fd_cross_scan_bwd_geom": (i32, [i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
     "fd_cross_scan_fwd_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "fd_cross_scan_bwd_ws_floats": (i64, [i32, i32, i32, i32, i32, i32]),
     "fd_cross_scan_bwd_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32,

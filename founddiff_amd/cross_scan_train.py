@@ -24,6 +24,7 @@ from ._train import HALF, cast_grads, check_devices, empty, f32, ptr, stream, wo
 __all__ = ["cross_selective_scan", "cross_scan_fn"]
 
 _N_OK, _R_OK = (4, 8, 16, 32), (2, 4, 8, 16, 32)
+_B_MAX = 16383                       # batch x direction is a grid.y of the backward: 4 B <= 65535 (cs_shape_ok)
 
 
 def _f32(name, t):
@@ -55,9 +56,9 @@ def _check(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds):
         raise RuntimeError(f"cross_selective_scan: inconsistent shapes x{tuple(x.shape)} x_proj_weight{tuple(x_proj_weight.shape)} "
                            f"dt_projs_weight{tuple(dt_projs_weight.shape)} dt_projs_bias{tuple(dt_projs_bias.shape)} "
                            f"A_logs{tuple(A_logs.shape)} Ds{tuple(Ds.shape)} (4 directions, d_inner = x.shape[1])")
-    if D % 64 or N not in _N_OK or R not in _R_OK or B < 1 or H < 1 or W < 1:
+    if D % 64 or N not in _N_OK or R not in _R_OK or not 1 <= B <= _B_MAX or H < 1 or W < 1:
         raise RuntimeError(f"cross_selective_scan: unsupported shape d_inner={D} (multiple of 64), d_state={N} (one of {_N_OK}), "
-                           f"dt_rank={R} (one of {_R_OK}), image {H}x{W}, batch {B}")
+                           f"dt_rank={R} (one of {_R_OK}), image {H}x{W}, batch {B} (at most {_B_MAX})")
     check_devices("cross_selective_scan", named)
     return B, D, H, W, N, R
 

@@ -466,15 +466,21 @@ __global__ __launch_bounds__(CS_T) void cs_nchw_nhwc_kernel(const float *__restr
 
 struct CsLayout {
     CsGeom g;
+    int tile;                                     // positions per tile of the scan kernels: 64 cs_e(CD)
     int64_t comp, part, dxd, dxp, wpart, total;   // floats: each composite array, parameter partials, dxdbl, its split partials,
 };                                                // the dx_proj_w partials
+
+// static LDS of cs_scan_kernel<N, R> (sT, sU, sY, sPix) and of cs_xproj_kernel<N, R> (sX, sW, sP), as declared there: host-side
+// restatements for fd_cross_scan_bwd_geom, held to the compiler's own figures by tests/test_scan_bwd_cases_cpu.py
+constexpr int cs_scan_lds(int CD) { return ((CD + 2 * CS_SLAB) * (64 * cs_e(CD) + 4) + 64 * cs_e(CD)) * 4; }
+constexpr int cs_xproj_lds(int CD) { return (XB * (CD + 1) + CD * 64 + XB) * 4; }
 
 CsLayout cs_layout(int B, int H, int W, int D, int N, int R) {
     CsLayout w;
     CsGeom &g = w.g;
     g.B = B; g.H = H; g.W = W; g.D = D; g.N = N; g.R = R; g.CD = R + 2 * N;
     g.H2 = (H + 1) / 2; g.W2 = (W + 1) / 2; g.L = g.H2 * g.W2;
-    const int tile = 64 * cs_e(g.CD);
+    const int tile = w.tile = 64 * cs_e(g.CD);
     g.ntiles = (g.L + tile - 1) / tile;
     // channel splits: enough workgroups for the chip from ONE slice (4 directions x tiles x splits >= 512), at least 64 channels
     // per split -- a function of the shape, never of the batch
@@ -492,7 +498,8 @@ CsLayout cs_layout(int B, int H, int W, int D, int N, int R) {
 }
 
 bool cs_shape_ok(int B, int H, int W, int D, int N, int R) {
-    return B > 0 && H > 0 && W > 0 && D > 0 && D % 64 == 0 && (N == 4 || N == 8 || N == 16 || N == 32) &&
+    // (B <= 16383: the scan and x_proj launches carry batch x direction in grid.y, 4 B <= 65535)
+    return B > 0 && B <= 16383 && H > 0 && W > 0 && D > 0 && D % 64 == 0 && (N == 4 || N == 8 || N == 16 || N == 32) &&
            (R == 2 || R == 4 || R == 8 || R == 16 || R == 32) && (int64_t)H * W * D * 4 < (1ll << 31);
 }
 
@@ -530,6 +537,26 @@ extern "C" int64_t fd_cross_scan_bwd_ws_floats(int B, int H, int W, int D, int N
     return cs_layout(B, H, W, D, N, R).total;
 }
 
+// What fd_cross_scan_bwd_f32 / _nhwc_f32 launch for this shape: cs_layout's own values, host only (tests/scan_bwd_cases.py).
+extern "C" int fd_cross_scan_bwd_geom(int B, int H, int W, int D, int N, int R, int32_t out[8]) {
+    FD_REQUIRE(out, "fd_cross_scan_bwd_geom: null pointer");
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    FD_REQUIRE(cs_shape_ok(B, H, W, D, N, R),
+               "fd_cross_scan_bwd_geom: unsupported shape B=%d H=%d W=%d d_inner=%d d_state=%d dt_rank=%d (d_inner %% 64 == 0, "
+               "N in {4,8,16,32}, R in {2,4,8,16,32}, B <= 16383)", B, H, W, D, N, R);
+    const CsLayout w = cs_layout(B, H, W, D, N, R);
+    const CsGeom &g = w.g;
+    out[0] = cs_e(g.CD);
+    out[1] = w.tile;
+    out[2] = g.L;
+    out[3] = g.ntiles;
+    out[4] = g.L - (g.ntiles - 1) * w.tile;
+    out[5] = g.S;
+    out[6] = g.nxb;
+    out[7] = cs_scan_lds(g.CD) > cs_xproj_lds(g.CD) ? cs_scan_lds(g.CD) : cs_xproj_lds(g.CD);
+    return FD_OK;
+}
+
 namespace {
 
 // the x_proj gather (src/emamba2.py:335) as the engine's fp32 parity mode runs it -- 4 stride-2 sub-grids, exact fp32, out-of-image
@@ -565,7 +592,7 @@ int cs_bwd(const char *name, int nhwc, const float *xc, const float *xdbl, const
                "%s: null pointer", name);
     FD_REQUIRE(cs_shape_ok(B, H, W, D, N, R),
                "%s: unsupported shape B=%d H=%d W=%d d_inner=%d d_state=%d dt_rank=%d (d_inner %% 64 == 0, "
-               "N in {4,8,16,32}, R in {2,4,8,16,32})", name, B, H, W, D, N, R);
+               "N in {4,8,16,32}, R in {2,4,8,16,32}, B <= 16383)", name, B, H, W, D, N, R);
     FD_REQUIRE((((uintptr_t)xc | (uintptr_t)dy | (uintptr_t)ws | (nhwc ? (uintptr_t)dx : 0)) & 15) == 0,
                "%s: tensors must be 16-byte aligned", name);
     const CsLayout w = cs_layout(B, H, W, D, N, R);
@@ -594,7 +621,7 @@ extern "C" int fd_cross_scan_fwd_f32(const float *x, const float *x_proj_w, cons
     FD_REQUIRE(x && x_proj_w && dtw && dtb && A && Ds && xc && xdbl && y && ws, "fd_cross_scan_fwd_f32: null pointer");
     FD_REQUIRE(cs_shape_ok(B, H, W, D, N, R),
                "fd_cross_scan_fwd_f32: unsupported shape B=%d H=%d W=%d d_inner=%d d_state=%d dt_rank=%d (d_inner %% 64 == 0, "
-               "N in {4,8,16,32}, R in {2,4,8,16,32})", B, H, W, D, N, R);
+               "N in {4,8,16,32}, R in {2,4,8,16,32}, B <= 16383)", B, H, W, D, N, R);
     FD_REQUIRE((((uintptr_t)x | (uintptr_t)xc | (uintptr_t)xdbl | (uintptr_t)y | (uintptr_t)x_proj_w) & 15) == 0,
                "fd_cross_scan_fwd_f32: tensors must be 16-byte aligned");
     const hipStream_t st = (hipStream_t)stream;
@@ -611,7 +638,7 @@ extern "C" int fd_cross_scan_fwd_nhwc_f32(const float *xc, const float *x_proj_w
     FD_REQUIRE(xc && x_proj_w && dtw && dtb && A && Ds && xdbl && y && ws, "fd_cross_scan_fwd_nhwc_f32: null pointer");
     FD_REQUIRE(cs_shape_ok(B, H, W, D, N, R),
                "fd_cross_scan_fwd_nhwc_f32: unsupported shape B=%d H=%d W=%d d_inner=%d d_state=%d dt_rank=%d (d_inner %% 64 == 0, "
-               "N in {4,8,16,32}, R in {2,4,8,16,32})", B, H, W, D, N, R);
+               "N in {4,8,16,32}, R in {2,4,8,16,32}, B <= 16383)", B, H, W, D, N, R);
     FD_REQUIRE((((uintptr_t)xc | (uintptr_t)xdbl | (uintptr_t)y | (uintptr_t)x_proj_w) & 15) == 0,
                "fd_cross_scan_fwd_nhwc_f32: tensors must be 16-byte aligned");
     return cs_fwd_from_xc(xc, x_proj_w, dtw, dtb, A, Ds, xdbl, y, ws, B, H, W, D, N, R, stream);

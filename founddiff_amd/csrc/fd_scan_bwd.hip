@@ -360,14 +360,16 @@ int sb_splits(int batch, int KD, int K, int64_t L) {
 }
 
 struct SbLayout {
-    int ntiles, S;
+    int ntiles, tgroups, S, NC;           // tiles, carry workgroups per row (SB_W tiles each), row splits, states per main-kernel chunk
     int64_t comp, part, bc, total;        // floats: each of the 3 composite arrays, the parameter partials, each dB / dC slab set
 };
 
 SbLayout sb_layout(int batch, int KD, int K, int N, int64_t L) {
     SbLayout w;
     w.ntiles = sb_ntiles(L);
+    w.tgroups = (w.ntiles + SB_W - 1) / SB_W;
     w.S = sb_splits(batch, KD, K, L);
+    w.NC = N <= 4 ? 4 : 8;
     w.comp = round4((int64_t)w.ntiles * batch * KD * N);
     w.part = round4((int64_t)(N + 2) * KD * batch * w.ntiles);
     w.bc = w.S > 1 ? round4((int64_t)w.S * batch * K * N * L) : 0;
@@ -375,11 +377,37 @@ SbLayout sb_layout(int batch, int KD, int K, int N, int64_t L) {
     return w;
 }
 
+// the shape checks of the call, shared with fd_selective_scan_bwd_geom
+int sb_shape(const char *name, int nrows, int batch, int KD, int K, int N, int64_t L) {
+    FD_REQUIRE(nrows >= 1 && nrows <= 4, "%s: nrows=%d not in 1..4", name, nrows);
+    FD_REQUIRE(batch > 0 && KD > 0 && K > 0 && L > 0 && KD % (K * nrows) == 0,
+               "%s: u.shape[1]=%d must be a multiple of B.shape[1]*nrows=%d*%d", name, KD, K, nrows);
+    FD_REQUIRE(N >= 1 && N <= 256, "%s: d_state=%d not in 1..256", name, N);
+    return FD_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t fd_selective_scan_bwd_ws_floats(int batch, int KD, int K, int N, int64_t L) {
     if (batch <= 0 || KD <= 0 || K <= 0 || N <= 0 || L <= 0 || KD % K) return 0;
     return sb_layout(batch, KD, K, N, L).total;
+}
+
+// What fd_selective_scan_bwd_f32 launches for this shape: sb_layout's own values, host only (tests/scan_bwd_cases.py).
+extern "C" int fd_selective_scan_bwd_geom(int batch, int KD, int K, int N, int64_t L, int32_t out[8]) {
+    FD_REQUIRE(out, "fd_selective_scan_bwd_geom: null pointer");
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (int rc = sb_shape("fd_selective_scan_bwd_geom", 1, batch, KD, K, N, L)) return rc;
+    const SbLayout w = sb_layout(batch, KD, K, N, L);
+    const int Dg = KD / K;
+    out[0] = w.ntiles;
+    out[1] = w.tgroups;
+    out[2] = (int32_t)(L - (int64_t)(w.ntiles - 1) * SB_TILE);
+    out[3] = w.S;
+    out[4] = w.NC;
+    out[5] = (Dg + w.S - 1) / w.S;          // rows of the largest split: split s walks rows [Dg s / S, Dg (s + 1) / S) of its group
+    out[6] = Dg;
+    return FD_OK;
 }
 
 extern "C" int fd_selective_scan_bwd_f32(const float *u, const float *delta, const float *A, const float *B, const float *C,
@@ -391,10 +419,7 @@ extern "C" int fd_selective_scan_bwd_f32(const float *u, const float *delta, con
                "fd_selective_scan_bwd_f32: null pointer");
     FD_REQUIRE(!D == !dD, "fd_selective_scan_bwd_f32: dD must be given exactly when D is");
     FD_REQUIRE(!delta_bias == !ddelta_bias, "fd_selective_scan_bwd_f32: ddelta_bias must be given exactly when delta_bias is");
-    FD_REQUIRE(nrows >= 1 && nrows <= 4, "fd_selective_scan_bwd_f32: nrows=%d not in 1..4", nrows);
-    FD_REQUIRE(batch > 0 && KD > 0 && K > 0 && L > 0 && KD % (K * nrows) == 0,
-               "fd_selective_scan_bwd_f32: u.shape[1]=%d must be a multiple of B.shape[1]*nrows=%d*%d", KD, K, nrows);
-    FD_REQUIRE(N >= 1 && N <= 256, "fd_selective_scan_bwd_f32: d_state=%d not in 1..256", N);
+    if (int rc = sb_shape("fd_selective_scan_bwd_f32", nrows, batch, KD, K, N, L)) return rc;
     FD_REQUIRE((((uintptr_t)u | (uintptr_t)delta | (uintptr_t)B | (uintptr_t)C | (uintptr_t)dout | (uintptr_t)du |
                  (uintptr_t)ddelta | (uintptr_t)dB | (uintptr_t)dC | (uintptr_t)ws) & 15) == 0,
                "fd_selective_scan_bwd_f32: tensors must be 16-byte aligned");
@@ -403,15 +428,14 @@ extern "C" int fd_selective_scan_bwd_f32(const float *u, const float *delta, con
     const int64_t rows = (int64_t)batch * KD, RN = rows * N;
     float *pa = ws, *hh = ws + w.comp, *gg = ws + 2 * w.comp, *part = ws + 3 * w.comp;
     float *pB = w.S > 1 ? part + w.part : dB, *pC = w.S > 1 ? part + w.part + w.bc : dC;
-    const int tgroups = (w.ntiles + SB_W - 1) / SB_W;
-    hipLaunchKernelGGL(scan_bwd_carry_kernel, dim3((unsigned)(rows * tgroups)), dim3(SB_T), 0, st, u, delta, A, B, C,
+    hipLaunchKernelGGL(scan_bwd_carry_kernel, dim3((unsigned)(rows * w.tgroups)), dim3(SB_T), 0, st, u, delta, A, B, C,
                        delta_bias, dout, delta_softplus, pa, hh, gg, KD, K, N, L, w.ntiles, rows);
     FD_LAUNCH_OK("fd_selective_scan_bwd_f32 (carry)");
     hipLaunchKernelGGL(scan_bwd_chain_kernel, dim3((unsigned)((RN + SB_T - 1) / SB_T)), dim3(SB_T), 0, st, pa, hh, gg, RN,
                        w.ntiles);
     FD_LAUNCH_OK("fd_selective_scan_bwd_f32 (chain)");
     const dim3 grid((unsigned)((int64_t)batch * K * w.S * w.ntiles));
-    if (N <= 4)
+    if (w.NC == 4)
         hipLaunchKernelGGL(scan_bwd_main_kernel<4>, grid, dim3(SB_T), 0, st, u, delta, A, B, C, D, delta_bias, dout,
                            delta_softplus, du, ddelta, pB, pC, hh, gg, part, batch, KD, K, N, L, w.ntiles, w.S);
     else

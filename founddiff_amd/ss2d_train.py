@@ -30,6 +30,7 @@ from ._train import cast_grads, check_devices, check_tensors, empty, f32, ptr, s
 __all__ = ["ss2d_core_fn", "ss2d_forward", "SS2D"]
 
 _N_OK, _R_OK = (4, 8, 16, 32), (2, 4, 8, 16, 32)
+_B_MAX = 16383                       # batch x direction is a grid.y of the scan backward: 4 B <= 65535 (cs_shape_ok)
 _NAMES = ("xz", "conv_weight", "conv_bias", "x_proj_weight", "dt_projs_weight", "dt_projs_bias", "A_logs", "Ds", "norm_weight",
           "norm_bias", "local")
 
@@ -54,9 +55,9 @@ def _check(xz, conv_weight, conv_bias, x_proj_weight, dt_projs_weight, dt_projs_
     if not ok:
         raise RuntimeError(f"ss2d_core_fn: inconsistent shapes {shapes} (4 directions, d_inner = xz.shape[-1] / 2, conv_weight "
                            "(d_inner, 1, 3, 3), local (B, d_inner) or (B, 1, d_inner))")
-    if D % 64 or D > 1024 or N not in _N_OK or R not in _R_OK or B < 1 or H < 1 or W < 1:
+    if D % 64 or D > 1024 or N not in _N_OK or R not in _R_OK or not 1 <= B <= _B_MAX or H < 1 or W < 1:
         raise RuntimeError(f"ss2d_core_fn: unsupported shape d_inner={D} (multiple of 64, at most 1024), d_state={N} (one of "
-                           f"{_N_OK}), dt_rank={R} (one of {_R_OK}), image {H}x{W}, batch {B}")
+                           f"{_N_OK}), dt_rank={R} (one of {_R_OK}), image {H}x{W}, batch {B} (at most {_B_MAX})")
     check_devices("ss2d_core_fn", named)
     return B, H, W, D, N, R
 

@@ -376,6 +376,12 @@ int fd_selective_scan_bwd_f32(const float *u, const float *delta, const float *A
                               const float *D, const float *delta_bias, const float *dout, int delta_softplus, int nrows,
                               int batch, int KD, int K, int N, int64_t L, float *du, float *ddelta, float *dA, float *dB,
                               float *dC, float *dD, float *ddelta_bias, float *ws, void *stream);
+/* What that call launches for a shape -- the launcher's own layout, host only:
+ *   out[0] tiles of 256 positions   out[1] carry workgroups per row (4 tiles each)   out[2] length of the last tile
+ *   out[3] row splits S per (batch, group, tile)   out[4] states per chunk of the main kernel (4, 8)
+ *   out[5] rows of the largest split   out[6] rows per group KD / K   out[7] 0
+ * Returns what the call returns for the shape (with nrows = 1): an error, and out all 0, for a refused one.        */
+int fd_selective_scan_bwd_geom(int batch, int KD, int K, int N, int64_t L, int32_t out[8]);
 
 /* ---- The reference's cross_selective_scan (src/emamba2.py:295-367) up to out_norm, for training, fp32 (fd_cross_scan_bwd.hip).
  * Forward: x [B,D,H,W] (NCHW, forward_corev2's layout) -> xc [B,H,W,D] (NHWC), the x_proj gather as fd_conv2d with ndir = 4
@@ -389,11 +395,17 @@ int fd_selective_scan_bwd_f32(const float *u, const float *delta, const float *A
  * reference's EfficientScan / EfficientMerge (src/emamba2.py:191-199, 253-260).  Deterministic (fixed-order sums, no float
  * atomics); tile sizes, channel splits and reduction orders depend on (H, W, D, N, R) only, so a slice's dx is the same bits
  * alone or in a batch.  ws: fd_cross_scan_bwd_ws_floats(...) floats, 0 for an unsupported shape.  D % 64 == 0,
- * N in {4, 8, 16, 32}, R in {2, 4, 8, 16, 32}; xc, dy, ws 16-byte aligned.                                                 */
+ * N in {4, 8, 16, 32}, R in {2, 4, 8, 16, 32}, B <= 16383 (batch x direction is a grid.y); xc, dy, ws 16-byte aligned.       */
 int fd_cross_scan_fwd_f32(const float *x, const float *x_proj_w, const float *dtw, const float *dtb, const float *A,
                           const float *Ds, float *xc, float *xdbl, float *y, float *ws, int B, int H, int W, int D, int N,
                           int R, void *stream);
 int64_t fd_cross_scan_bwd_ws_floats(int B, int H, int W, int D, int N, int R);
+/* What the backward (either layout) launches for a shape -- the launcher's own layout, host only, of B only the validity:
+ *   out[0] positions per lane E (4 where R + 2N <= 24, else 1)   out[1] tile length 64 E   out[2] L = ceil(H/2) ceil(W/2)
+ *   out[3] tiles   out[4] length of the last tile   out[5] channel splits S   out[6] x_proj blocks of 256 rows
+ *   out[7] static LDS bytes of the larger of the scan and the x_proj kernel
+ * Returns what the call returns for the shape: an error, and out all 0, for a refused one.                           */
+int fd_cross_scan_bwd_geom(int B, int H, int W, int D, int N, int R, int32_t out[8]);
 int fd_cross_scan_bwd_f32(const float *xc, const float *xdbl, const float *x_proj_w, const float *dtw, const float *dtb,
                           const float *A, const float *Ds, const float *dy, float *dx, float *dx_proj_w, float *ddtw,
                           float *ddtb, float *dA, float *dDs, float *ws, int B, int H, int W, int D, int N, int R,

@@ -9,9 +9,10 @@ import torch
 import torch.nn.functional as F
 
 
-def scan_grads_f64(u, delta, A, B, C, D, delta_bias, dout, softplus, chunk=1024):
-    """(du, ddelta, dA, dB, dC, dD, ddelta_bias) in float64; B / C 4-D (b, K, N, L); D / delta_bias may be None."""
-    f = lambda t: None if t is None else t.to(torch.float64)
+def scan_grads_f64(u, delta, A, B, C, D, delta_bias, dout, softplus, chunk=1024, dtype=torch.float64):
+    """(du, ddelta, dA, dB, dC, dD, ddelta_bias) in float64; B / C 4-D (b, K, N, L); D / delta_bias may be None.
+    dtype=torch.float32: the same restatement in the kernels' own precision, for its distance from the float64 one."""
+    f = lambda t: None if t is None else t.to(dtype)
     u, delta, A, B, C, D, bias, dout = map(f, (u, delta, A, B, C, D, delta_bias, dout))
     b, KD, L = u.shape
     K, N = B.shape[1], A.shape[1]
@@ -26,10 +27,10 @@ def scan_grads_f64(u, delta, A, B, C, D, delta_bias, dout, softplus, chunk=1024)
     u5, dt5, dy5 = (t.reshape(b, K, Dg, L, 1) for t in (u, dt, dout))
     B5, C5 = (t.permute(0, 1, 3, 2).unsqueeze(2) for t in (B, C))
     A4 = A.reshape(K, Dg, 1, N)
-    H = torch.empty(b, K, Dg, L, N, dtype=torch.float64, device=u.device)
+    H = torch.empty(b, K, Dg, L, N, dtype=dtype, device=u.device)
     G = torch.empty_like(H)
     spans = [(c0, min(c0 + chunk, L)) for c0 in range(0, L, chunk)]
-    h = torch.zeros(b, K, Dg, N, dtype=torch.float64, device=u.device)
+    h = torch.zeros(b, K, Dg, N, dtype=dtype, device=u.device)
     for c0, c1 in spans:
         a = torch.exp(dt5[:, :, :, c0:c1] * A4)
         bu = dt5[:, :, :, c0:c1] * B5[:, :, :, c0:c1] * u5[:, :, :, c0:c1]
@@ -44,11 +45,11 @@ def scan_grads_f64(u, delta, A, B, C, D, delta_bias, dout, softplus, chunk=1024)
             g = c[:, :, :, i] + x
             G[:, :, :, c0 + i] = g
             x = a[:, :, :, i] * g
-    du = torch.empty(b, K, Dg, L, dtype=torch.float64, device=u.device)
+    du = torch.empty(b, K, Dg, L, dtype=dtype, device=u.device)
     ddt = torch.empty_like(du)
-    dB = torch.empty(b, K, L, N, dtype=torch.float64, device=u.device)
+    dB = torch.empty(b, K, L, N, dtype=dtype, device=u.device)
     dC = torch.empty_like(dB)
-    dA = torch.zeros(K, Dg, N, dtype=torch.float64, device=u.device)
+    dA = torch.zeros(K, Dg, N, dtype=dtype, device=u.device)
     for c0, c1 in spans:
         s = slice(c0, c1)
         Hc, Gc = H[:, :, :, s], G[:, :, :, s]

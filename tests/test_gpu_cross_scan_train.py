@@ -3,86 +3,21 @@ csrc/fd_cross_scan_bwd.hip) against float64: autograd on the CPU through the ora
 selective_scan_torch for small images, and on the GPU through the oracle's efficient_scan / efficient_merge, the two einsums and a
 test-local autograd wrapper around tests/scan_bwd_ref.py for the block shapes and level 0.
 
-Gates (those of test_gpu_scan_bwd.py): rel_err < 1e-5 for y, < 1e-4 for dx, < 1e-3 for the weight gradients (sums over
-batch x L); rel_err = max abs error over the reference's max abs value.  Measured errors are in each test's docstring."""
+Gates (those of test_gpu_scan_bwd.py): rel_err < 1e-5 for y and dx, < 1e-4 for the weight gradients (sums over
+batch x L); rel_err = max abs error over the reference's max abs value.  Every comparison prints its error
+before it asserts (pytest -s); the docstrings quote the figures of one run on an MI355X."""
 import pytest
 import torch
 import torch.nn.functional as F
 
 from conftest import rel_err
-from scan_bwd_ref import scan_grads_f64
+from scan_bwd_cases import _params, _ref_y, _ScanF64, _x          # noqa: F401 (test_gpu_ss2d_train.py imports them from here)
 
 pytestmark = pytest.mark.gpu
 
 BLOCK_SHAPES = [(128, 4, 4), (128, 8, 4), (256, 16, 8), (512, 32, 16), (1024, 32, 32), (512, 16, 16), (256, 8, 8)]  # (d_inner, N, R)
 PARAMS = ("x_proj_weight", "dt_projs_weight", "dt_projs_bias", "A_logs", "Ds")
-GATES = dict(y=1e-5, x=1e-4, x_proj_weight=1e-3, dt_projs_weight=1e-3, dt_projs_bias=1e-3, A_logs=1e-3, Ds=1e-3)
-
-
-def _params(D, N, R, seed):
-    """SS2D's initialisation scales (src/emamba2.py: x_proj ~ d_inner^-0.5, dt_proj ~ dt_rank^-0.5, dt bias of a softplus-inverse
-    dt in [1e-3, 1e-1], A_logs = log(1..N), Ds = 1), drawn in fp32 so that the oracle's .float() casts are exact"""
-    g = torch.Generator().manual_seed(seed)
-    dt = torch.exp(torch.rand(4, D, generator=g) * (torch.log(torch.tensor(0.1)) - torch.log(torch.tensor(1e-3)))
-                   + torch.log(torch.tensor(1e-3)))
-    return dict(
-        x_proj_weight=torch.randn(4, R + 2 * N, D, generator=g) * D ** -0.5,
-        dt_projs_weight=torch.randn(4, D, R, generator=g) * R ** -0.5,
-        dt_projs_bias=dt + torch.log(-torch.expm1(-dt)),
-        A_logs=torch.log(torch.arange(1, N + 1).float())[None].repeat(4 * D, 1) + 0.05 * torch.randn(4 * D, N, generator=g),
-        Ds=1 + 0.1 * torch.randn(4 * D, generator=g))
-
-
-def _x(B, D, H, W, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(B, D, H, W, generator=g), torch.randn(B, H, W, D, generator=g)
-
-
-def _scan_f64_fwd(u, delta, A, B, C, D, bias):
-    """y of the selective scan (softplus), float64, by a loop over the sequence on u's device"""
-    b, KD, L = u.shape
-    K, N = B.shape[1], A.shape[1]
-    dt = F.softplus(delta + bias[None, :, None])
-    Bx, Cx = B.repeat_interleave(KD // K, dim=1), C.repeat_interleave(KD // K, dim=1)      # (b, KD, N, L)
-    y = torch.empty_like(u)
-    h = torch.zeros(b, KD, N, dtype=u.dtype, device=u.device)
-    for c0 in range(0, L, 1024):
-        c1 = min(c0 + 1024, L)
-        a = torch.exp(dt[:, :, c0:c1, None] * A[None, :, None])
-        bu = (dt[:, :, c0:c1] * u[:, :, c0:c1])[..., None] * Bx[..., c0:c1].transpose(2, 3)
-        cc = Cx[..., c0:c1].transpose(2, 3)
-        for i in range(c1 - c0):
-            h = a[:, :, i] * h + bu[:, :, i]
-            y[:, :, c0 + i] = (h * cc[:, :, i]).sum(-1)
-    return y + D[None, :, None] * u
-
-
-class _ScanF64(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, delta, A, B, C, D, bias):
-        ctx.save_for_backward(u, delta, A, B, C, D, bias)
-        return _scan_f64_fwd(u, delta, A, B, C, D, bias)
-
-    @staticmethod
-    def backward(ctx, dout):
-        return scan_grads_f64(*ctx.saved_tensors, dout, True)
-
-
-def _ref_y(x, p, scan):
-    """the reference's cross_selective_scan up to out_norm: (B, H, W, D)"""
-    from oracle import nets
-    Bn, D, H, W = x.shape
-    N = p["A_logs"].shape[1]
-    K, _, R = p["dt_projs_weight"].shape
-    xs = nets.efficient_scan(x)
-    L = xs.shape[-1]
-    x_dbl = torch.einsum("bkdl,kcd->bkcl", xs, p["x_proj_weight"])
-    dts, Bs, Cs = torch.split(x_dbl, [R, N, N], dim=2)
-    dts = torch.einsum("bkrl,kdr->bkdl", dts, p["dt_projs_weight"])
-    ys = scan(xs.reshape(Bn, -1, L), dts.reshape(Bn, -1, L), -torch.exp(p["A_logs"]), Bs.contiguous(), Cs.contiguous(),
-              p["Ds"], p["dt_projs_bias"].reshape(-1))
-    y = nets.efficient_merge(ys.view(Bn, K, -1, L), H, W)
-    return y.transpose(1, 2).reshape(Bn, H, W, D)
+GATES = dict(y=1e-5, x=1e-5, x_proj_weight=1e-4, dt_projs_weight=1e-4, dt_projs_bias=1e-4, A_logs=1e-4, Ds=1e-4)
 
 
 def _grads(fn, x, p, dy, device, dtype):
@@ -102,6 +37,7 @@ def _check(got, ref, tag):
     for name, gate in GATES.items():
         assert got[name].shape == ref[name].shape, (tag, name)
         e = rel_err(got[name].cpu(), ref[name].cpu())
+        print(f"cross_scan_train[{tag}] {name} {e:.3e}")
         assert e < gate, f"{tag}: {name} error {e:.3e} >= {gate:.0e}"
 
 

@@ -1,10 +1,10 @@
 """founddiff_amd.ss2d_train (csrc/fd_ss2d_train.hip, the NHWC entries of csrc/fd_cross_scan_bwd.hip) against float64 and against
 the reference's captured outputs.
 
-Gates, the project's own: rel_err (max abs error over the reference's max abs value) < 1e-5 for forward outputs, < 1e-4 for
-gradients of activations, < 1e-3 for parameter gradients (sums over batch x pixels), as test_gpu_scan_bwd.py and
-test_gpu_cross_scan_train.py hold against float64; < 1e-4 against the reference's captured fp32 outputs, as
-test_gpu_e2e.py::test_mamba_block[fp32].  Measured errors are in each test's docstring."""
+Gates against float64, rel_err = max abs error over the reference's max abs value: < 1e-5 for forward outputs, < 1e-4 for
+gradients of activations, < 1e-3 for parameter gradients (sums over batch x pixels).  The SS2D core is held to CORE_GATES, the
+gates of test_gpu_scan_bwd.py and test_gpu_cross_scan_train.py: 1e-5 and 1e-4.  Against the reference's captured fp32 outputs:
+< 1e-4, as test_gpu_e2e.py::test_mamba_block[fp32].  Measured errors are in each test's docstring."""
 import math
 
 import pytest
@@ -19,7 +19,9 @@ pytestmark = pytest.mark.gpu
 ACT, PARAM, OUT = 1e-4, 1e-3, 1e-5
 CORE = ("xz", "conv_weight", "conv_bias", "x_proj_weight", "dt_projs_weight", "dt_projs_bias", "A_logs", "Ds", "norm_weight",
         "norm_bias", "local")
-CORE_GATES = dict(out=OUT, xz=ACT, local=ACT, **{k: PARAM for k in CORE[1:-1]})
+# the core: 1e-5 for out and the activation gradients, 1e-4 for the parameter gradients, as test_gpu_scan_bwd_cases.py holds the scan
+# backward underneath (measured on an MI355X: activations up to 4.5e-7, parameters up to 2.2e-6)
+CORE_GATES = dict(out=OUT, xz=1e-5, local=1e-5, **{k: 1e-4 for k in CORE[1:-1]})
 SENTINEL = -12345.0
 
 

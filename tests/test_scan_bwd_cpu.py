@@ -1,5 +1,7 @@
 """The selective-scan backward's host side, without a GPU: the C ABI of both builds of the library and the Python
 binding's argument checks (founddiff_amd/selective_scan_train.py)."""
+import ctypes
+
 import pytest
 import torch
 
@@ -20,6 +22,13 @@ def test_workspace_size_at_level0():
         n = lib.fd_selective_scan_bwd_ws_floats(2, 512, 4, 4, 65536)
         assert n > 0 and n % 4 == 0
         assert n >= 3 * 256 * 2 * 512 * 4                  # Pa, h and g carries of every (tile, row, state)
+        # exactly: the geometry query's 256 tiles and single row split (2 x 4 x 256 workgroups fill the chip) leave the three
+        # composite arrays [tile][batch KD][N] and the parameter partials [N + 2][KD][batch][tile], no dB / dC slabs
+        out = (ctypes.c_int32 * 8)()
+        assert lib.fd_selective_scan_bwd_geom(2, 512, 4, 4, 65536, out) == 0
+        assert list(out) == [256, 64, 256, 1, 4, 128, 128, 0]
+        ntiles, S = out[0], out[3]
+        assert n == 3 * ntiles * 2 * 512 * 4 + (4 + 2) * 512 * 2 * ntiles + (0 if S == 1 else 2 * S * 2 * 4 * 4 * 65536) == 4718592
         assert lib.fd_selective_scan_bwd_ws_floats(2, 510, 4, 4, 65536) == 0
         assert lib.fd_selective_scan_bwd_ws_floats(0, 512, 4, 4, 65536) == 0
 
