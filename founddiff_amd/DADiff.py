@@ -1174,6 +1174,10 @@ class Trainer(object):
     `__len__`, `__getitem__ -> [ndct, ldct]` ((1,H,W) tensors in [0,1]) and `load_name(i)`; `train_dataset` needs the first two.
     `augment=True` applies the reference's RandomFlip + RandomRotate90 to every training pair (data/pdf_dataset.py:521-545), both
     images under one transform, drawn per item by diffusion_train.train_augment; `augment_flip` is ignored, as before.
+    `crop_size` (an int or (h, w), multiples of 2 ** (levels - 1) of the U-Net; None: whole slices) trains on the reference's
+    CropToFixed patches (data/transforms.py:196-249): every training pair is cut to the window diffusion_train.train_crop draws
+    per item, reflect-padded where the slice is smaller, before the flip / rot90, which then needs a square crop for its odd
+    rotations and no longer square slices; sample() and test() keep whole slices.
     `train_dataset` may be a data.DeviceSliceStore: train() then gathers (and augments) every micro-batch on the device and
     uploads no image.  `seed` keys what train() draws (diffusion_train.train_batch_indices / train_t_and_seeds / train_augment),
     `log_every` is how often the loss is read back from the device.  One U-Net only (train() raises for two: RAdam)."""
@@ -1184,9 +1188,19 @@ class Trainer(object):
                  amp=False, fp16=False, split_batches=True, convert_image_to=None, condition=False, sub_dir=False,
                  equalizeHist=False, crop_patch=False, generation=False, num_unet=2, checkpoint_folder=None,
                  is_train=True, train_logger=None, dataset=None, device=None, train_dataset=None, seed=0, log_every=100,
-                 augment=False):
+                 augment=False, crop_size=None):
         import logging
         import os as _os
+        self.crop_size = None
+        if crop_size is not None:
+            from .data import crop_pair
+            ch, cw = crop_pair("Trainer", crop_size, "crop_size")
+            unet = getattr(getattr(diffusion_model, "model", None), "unet0", None)
+            step = 2 ** (len(getattr(unet, "dim_mults", (1,))) - 1)
+            if ch < 1 or cw < 1 or ch % step or cw % step:
+                raise RuntimeError(f"Trainer: crop_size {ch} x {cw} must be positive multiples of {step} (the U-Net has "
+                                   f"{len(getattr(unet, 'dim_mults', (1,)))} levels)")
+            self.crop_size = (ch, cw)
         self.opt = opt
         self.checkpoint_folder = checkpoint_folder or "."
         self.results_folder = self.checkpoint_folder + "/sample"
@@ -1296,9 +1310,9 @@ class Trainer(object):
         through diffusion_train.train_step (clip 1.0, Adam, zero_grad, the EMA), a preview from the EMA model every
         save_and_sample_every steps and save() on the reference's schedule (its FID run is not built).  Micro-batch m of step s,
         its t, its noise and (with augment) its flip / rot90 codes are functions of (seed, s, m) alone; the losses stay on the
-        device and are read every log_every steps.  From a data.DeviceSliceStore, or with augment, a micro-batch is a
-        diffusion_train.StoreBatch: its indices, codes, t and seeds go up as one table and nothing waits for the host; a host
-        dataset without augment is loaded, stacked and uploaded as before."""
+        device and are read every log_every steps.  From a data.DeviceSliceStore, or with augment or crop_size, a micro-batch is a
+        diffusion_train.StoreBatch: its indices, codes, windows, t and seeds go up as one table and nothing waits for the host; a
+        host dataset without augment and crop_size is loaded, stacked and uploaded as before."""
         from .data import DeviceSliceStore
         self._setup_training()
         ds = self.train_dataset
@@ -1313,11 +1327,14 @@ class Trainer(object):
                 idx = dt.train_batch_indices(self.seed, self.step, m, self.batch_size, len(ds), acc)
                 self.batch_log.append(idx)
                 t, sd = dt.train_t_and_seeds(self.seed, self.step, m, idx, T)
-                if isinstance(ds, DeviceSliceStore) or self.augment:
+                if isinstance(ds, DeviceSliceStore) or self.augment or self.crop_size:
                     store, local = (ds, idx) if isinstance(ds, DeviceSliceStore) else \
                         (DeviceSliceStore.from_items([ds[i] for i in idx], self.device), list(range(len(idx))))
-                    codes = dt.train_augment(self.seed, self.step, m, idx, store.H == store.W) if self.augment else None
-                    batches.append(dt.StoreBatch(store, local, codes))
+                    crop = self.crop_size
+                    square = store.H == store.W if crop is None else crop[0] == crop[1]
+                    codes = dt.train_augment(self.seed, self.step, m, idx, square) if self.augment else None
+                    windows = dt.train_crop(self.seed, self.step, m, idx, store.H, store.W, crop) if crop else None
+                    batches.append(dt.StoreBatch(store, local, codes, windows, crop))
                     ts.append(t)
                     seeds.append(sd)
                     continue

@@ -177,6 +177,9 @@ SIGNATURES = {
     "fd_store_gather_f32": (i32, [vp, vp, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "fd_res_qsample_store_f32": (i32, [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32,
                                        i32, vp]),
+    "fd_store_crop_f32": (i32, [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "fd_res_qsample_crop_f32": (i32, [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32,
+                                      i32, i32, i32, i32, vp]),
     "fd_init_conv7_fwd_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "fd_init_conv7_wgrad_ws_floats": (i64, [i32, i32, i32, i32, i32]),
     "fd_init_conv7_wgrad_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),

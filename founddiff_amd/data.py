@@ -1,5 +1,6 @@
 """CT slice I/O, the normalisation contract, the mixed-dose datasets on either side of the sampling path, and a paired dataset held
-on the GPU (DeviceSliceStore) whose batches a HIP kernel gathers and augments (csrc/fd_train_data.hip).
+on the GPU (DeviceSliceStore) whose batches a HIP kernel gathers and augments (csrc/fd_train_data.hip) or cuts to patches first
+(csrc/fd_train_crop.hip).
 
 Reference contract:
   * slices are `.npy` arrays in HU + 1024, stored (1, H, W) (`ToTensor(expand_dims=False)` asserts ndim 3,
@@ -220,13 +221,34 @@ def upload_table(rows, device):
     return tab.pin_memory().to(device, non_blocking=True)
 
 
-def check_batch(fn, store, indices, codes):
-    """(indices, codes) of a batch from `store` as int64 arrays (codes None stays None): types, then shapes, then ranges"""
+def crop_pair(fn, crop, name="crop"):
+    """`crop` as (ch, cw): an int, or an (h, w) pair of integers"""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    c = (crop, crop) if is_int(crop) else crop
+    if not (isinstance(c, (tuple, list)) and len(c) == 2 and all(is_int(v) for v in c)):
+        raise RuntimeError(f"{fn}: {name} must be an int or an (h, w) pair of integers (got {crop!r})")
+    return int(c[0]), int(c[1])
+
+
+def crop_pads(n, c):
+    """(before, after): the reflect padding of an axis of length n cropped to c >= n (CropToFixed, data/transforms.py:196-249)"""
+    before = max(c - n, 0) // 2
+    return before, max(c - n, 0) - before
+
+
+def window_rows(windows):
+    """the (B, 2) windows as two rows of a batch's (rows, B) table: side by side they are the (B, 2) array again"""
+    return list(np.ascontiguousarray(windows, dtype=np.int64).reshape(2, -1))
+
+
+def check_batch(fn, store, indices, codes, windows=None, crop=None):
+    """(indices, codes, windows, crop) of a batch from `store`: int64 arrays (codes and windows None stay None) and crop as
+    (ch, cw) or None: types, then shapes, then ranges"""
     if not isinstance(store, DeviceSliceStore):
         raise RuntimeError(f"{fn}: store must be a DeviceSliceStore (got {type(store).__name__})")
     out = []
-    for name, v in (("indices", indices), ("codes", codes)):
-        if v is None and name == "codes":
+    for name, v in (("indices", indices), ("codes", codes), ("windows", windows)):
+        if v is None and name != "indices":
             out.append(None)
             continue
         if isinstance(v, torch.Tensor):
@@ -241,19 +263,41 @@ def check_batch(fn, store, indices, codes):
             raise RuntimeError(f"{fn}: {name} must be a sequence of integers (got {type(v).__name__}"
                                f"{'' if a is None else ' of ' + str(a.dtype)})")
         out.append(a.astype(np.int64))
-    idx, cd = out
+    idx, cd, win = out
+    if crop is not None:
+        crop = crop_pair(fn, crop)
+    elif win is not None:
+        raise RuntimeError(f"{fn}: windows need a crop (got crop=None)")
     if idx.ndim != 1 or idx.size < 1 or (cd is not None and cd.shape != idx.shape):
         raise RuntimeError(f"{fn}: inconsistent shapes indices{idx.shape} codes{None if cd is None else cd.shape} (both (B,), B >= 1)")
+    if win is not None and win.shape != (idx.size, 2):
+        raise RuntimeError(f"{fn}: inconsistent shapes indices{idx.shape} windows{win.shape} (windows (B, 2): y0, x0 per item)")
     if idx.size > 65535:
         raise RuntimeError(f"{fn}: unsupported shape indices{idx.shape} (at most 65535 slices)")
+    H, W = store.H, store.W
+    if crop is not None:
+        ch, cw = crop
+        if not (1 <= ch <= 32768 and 1 <= cw <= 32768):
+            raise RuntimeError(f"{fn}: unsupported shape crop {ch} x {cw} (1 <= h, w <= 32768)")
+        if crop_pads(H, ch)[1] > H - 1 or crop_pads(W, cw)[1] > W - 1:
+            raise RuntimeError(f"{fn}: unsupported shape crop {ch} x {cw} of {H} x {W} slices (one reflection only: a pad of at most "
+                               f"{H - 1} rows and {W - 1} columns on either side)")
     if idx.min() < 0 or idx.max() >= len(store):
         raise RuntimeError(f"{fn}: index {int(idx[(idx < 0) | (idx >= len(store))][0])} outside [0, {len(store)})")
     if cd is not None:
         if cd.min() < 0 or cd.max() >= 16:
             raise RuntimeError(f"{fn}: code {int(cd[(cd < 0) | (cd >= 16)][0])} outside [0, 16)")
-        if store.H != store.W and (cd & 4).any():
-            raise RuntimeError(f"{fn}: code {int(cd[(cd & 4) != 0][0])} transposes (k odd), the store's slices are {store.H} x {store.W}")
-    return idx, cd
+        if crop is None and H != W and (cd & 4).any():
+            raise RuntimeError(f"{fn}: code {int(cd[(cd & 4) != 0][0])} transposes (k odd), the store's slices are {H} x {W}")
+        if crop is not None and crop[0] != crop[1] and (cd & 4).any():
+            raise RuntimeError(f"{fn}: code {int(cd[(cd & 4) != 0][0])} transposes (k odd), the crop is {crop[0]} x {crop[1]}")
+    if win is not None:
+        ny, nx = max(H - crop[0], 1), max(W - crop[1], 1)
+        bad = (win[:, 0] < 0) | (win[:, 0] >= ny) | (win[:, 1] < 0) | (win[:, 1] >= nx)
+        if bad.any():
+            y0, x0 = (int(v) for v in win[bad][0])
+            raise RuntimeError(f"{fn}: window ({y0}, {x0}) outside [0, {ny}) x [0, {nx}) (a {crop[0]} x {crop[1]} crop of {H} x {W} slices)")
+    return idx, cd, win, crop
 
 
 class DeviceSliceStore:
@@ -261,8 +305,9 @@ class DeviceSliceStore:
     ld (n_ld, H, W) and nd_index (n_ld,) int64, on the host (nd_index) and on the device (nd_index_dev): item i is the pair
     [nd[nd_index[i]], ld[i]], so several dose levels share one stored NDCT.  It has the dataset surface (__len__,
     __getitem__ -> device views, load_name), so it also serves as `dataset=` of Trainer.sample / test; batch() gathers a batch
-    under the flip / rot90 codes of diffusion_train.train_augment in one launch (fd_store_gather_f32), and
-    diffusion_train.StoreBatch hands one to the training step without assembling it."""
+    under the flip / rot90 codes of diffusion_train.train_augment in one launch (fd_store_gather_f32; cut to the windows of
+    diffusion_train.train_crop first with crop=: fd_store_crop_f32), and diffusion_train.StoreBatch hands one to the training step
+    without assembling it."""
 
     def __init__(self, nd, ld, nd_index, names=None):
         fn = "DeviceSliceStore"
@@ -397,15 +442,28 @@ class DeviceSliceStore:
     def nbytes(self):
         return 4 * (self.nd.numel() + self.ld.numel()) + 8 * self.n_ld
 
-    def batch(self, indices, codes=None):
+    def batch(self, indices, codes=None, windows=None, crop=None):
         """(x_start, x_input), both (B, 1, H, W): items `indices` under the transform `codes` (diffusion_train.train_augment;
-        None: as stored), in one launch.  A transposing code (k odd) needs square slices."""
-        idx, cd = check_batch("DeviceSliceStore.batch", self, indices, codes)
+        None: as stored), in one launch.  A transposing code (k odd) needs square slices.
+        crop (an int or (h, w)): the reference's CropToFixed first, then the transform on the crop; both results are
+        (B, 1, h, w).  windows (B, 2) = (y0, x0) per item (diffusion_train.train_crop; None: zeros), each inside
+        [0, max(H - h, 1)) x [0, max(W - w, 1)); an axis no longer than the crop is taken whole and reflect-padded to it, once:
+        a pad of at most H - 1 / W - 1 on either side.  A transposing code then needs a square crop, whatever the slices are."""
+        idx, cd, win, crop = check_batch("DeviceSliceStore.batch", self, indices, codes, windows, crop)
         B = len(idx)
         with torch.no_grad(), torch.cuda.device(self.device):
-            tab = upload_table([self.nd_index[idx], idx] + ([] if cd is None else [cd]), self.device)
+            rows = [self.nd_index[idx], idx] + ([] if cd is None else [cd])
+            at = len(rows)
+            tab = upload_table(rows + ([] if win is None else window_rows(win)), self.device)
             new = empty(self.device)
-            x_start, x_input = new(B, 1, self.H, self.W), new(B, 1, self.H, self.W)
-            L.call("fd_store_gather_f32", ptr(self.nd), ptr(self.ld), self.n_nd, self.n_ld, ptr(tab[0]), ptr(tab[1]),
-                   None if cd is None else ptr(tab[2]), ptr(x_start), ptr(x_input), B, self.H, self.W, stream(self.device))
+            codes_ptr = None if cd is None else ptr(tab[2])
+            if crop is None:
+                x_start, x_input = new(B, 1, self.H, self.W), new(B, 1, self.H, self.W)
+                L.call("fd_store_gather_f32", ptr(self.nd), ptr(self.ld), self.n_nd, self.n_ld, ptr(tab[0]), ptr(tab[1]), codes_ptr,
+                       ptr(x_start), ptr(x_input), B, self.H, self.W, stream(self.device))
+            else:
+                x_start, x_input = new(B, 1, *crop), new(B, 1, *crop)
+                L.call("fd_store_crop_f32", ptr(self.nd), ptr(self.ld), self.n_nd, self.n_ld, ptr(tab[0]), ptr(tab[1]), codes_ptr,
+                       None if win is None else ptr(tab[at]), ptr(x_start), ptr(x_input), B, self.H, self.W, crop[0], crop[1],
+                       stream(self.device))
         return x_start, x_input

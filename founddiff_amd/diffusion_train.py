@@ -12,7 +12,8 @@
     train_step(diffusion_or_fn, opt, batch, ...)   p_losses -> backward per loss -> opt.step()
     StoreBatch(store, indices, codes)              a micro-batch that stays in a data.DeviceSliceStore: accepted wherever
                                                    [x_start, x_input] is; q_sample then gathers, flips / rotates and diffuses it in
-                                                   one launch (csrc/fd_train_data.hip), fed by one int64 table from pinned memory
+                                                   one launch (csrc/fd_train_data.hip), fed by one int64 table from pinned memory;
+                                                   with windows and crop it is cut to patches in that launch (csrc/fd_train_crop.hip)
 
 Binding for a training run:
 
@@ -30,18 +31,18 @@ The checkpoint of DADiff.Trainer.save (checkpoint_pack / checkpoint_unpack) has 
 reason: no test reads a file written by either.
 
 chunk_table, ema_schedule, adam_state_unpack, adam_state_pack, train_batch_indices, train_t_and_seeds, train_augment,
-augment_source_index, checkpoint_pack and checkpoint_unpack are pure host code.
+augment_source_index, train_crop, crop_source_index, checkpoint_pack and checkpoint_unpack are pure host code.
 """
 import numpy as np
 import torch
 
 from . import _lib as L
 from ._train import empty, ptr, stream, workspace
-from .data import check_batch, upload_table
+from .data import check_batch, crop_pads, crop_pair, upload_table, window_rows
 
 __all__ = ["q_sample", "residual_loss", "p_losses_fn", "p_losses", "ClipAdamEMA", "train_step", "chunk_table", "ema_schedule",
            "adam_state_unpack", "adam_state_pack", "train_batch_indices", "train_t_and_seeds", "train_augment", "augment_source_index",
-           "StoreBatch", "checkpoint_pack", "checkpoint_unpack", "CHUNK"]
+           "train_crop", "crop_source_index", "StoreBatch", "checkpoint_pack", "checkpoint_unpack", "CHUNK"]
 
 CHUNK = 4096                      # elements of a parameter per workgroup (fd_opt_chunk_elems())
 _LOSS_TYPES = {"l1": 1, "l2": 2}
@@ -168,6 +169,31 @@ def augment_source_index(code, H, W):
     return i, j
 
 
+def train_crop(seed, step, micro, indices, H, W, crop):
+    """The crop window (y0, x0) of every item of `indices` in micro-batch `micro` of step `step`, an int64 (len(indices), 2)
+    array, for `crop` = an int or (ch, cw) out of (H, W) slices: y0 = _mix64(seed, step, micro, index, 0x63) % max(H - ch, 1),
+    x0 = _mix64(seed, step, micro, index, 0x64) % max(W - cw, 1), keyed per item like train_augment, so an item's window does not
+    depend on what else is in its batch.  This is the reference's CropToFixed (data/transforms.py:196-249): its
+    randint(max_size - crop_size) is uniform over [0, H - ch), so the last possible offset H - ch is never drawn (kept), and its
+    randint(1) makes the start 0 when ch >= H (the axis is then taken whole and reflect-padded to ch)."""
+    ch, cw = crop_pair("train_crop", crop)
+    ny, nx = max(int(H) - ch, 1), max(int(W) - cw, 1)
+    out = [(_mix64(seed, step, micro, i, 0x63) % ny, _mix64(seed, step, micro, i, 0x64) % nx) for i in indices]
+    return np.asarray(out, dtype=np.int64).reshape(-1, 2)
+
+
+def crop_source_index(code, y0, x0, H, W, ch, cw):
+    """(i, j), two (ch, cw) integer arrays: output pixel (y, x) of the window (y0, x0) of a ch x cw crop under the transform `code`
+    is source pixel (i[y, x], j[y, x]) of the (H, W) slice.  The crop comes first (an axis no longer than the crop is taken whole
+    and reflect-padded, (c - n) // 2 in front and the rest behind, as np.pad(mode="reflect") does: no edge repeat, one
+    reflection), then augment_source_index on the crop.  The formula the kernels of csrc/fd_train_crop.hip implement, in numpy."""
+    ic, jc = augment_source_index(code, ch, cw)
+
+    def refl(v, n):
+        return np.where(v < 0, -v, np.where(v >= n, 2 * (n - 1) - v, v))
+    return refl(y0 + ic - crop_pads(H, ch)[0], H), refl(x0 + jc - crop_pads(W, cw)[0], W)
+
+
 CHECKPOINT_KEYS = ("step", "model", "opt0", "ema", "scaler")
 
 
@@ -283,11 +309,13 @@ def _check_qsample(fn, x_start, x_input, t, schedule, noise, slice_seeds, dims=(
 class StoreBatch:
     """Items `indices` of a data.DeviceSliceStore under the transform `codes` (train_augment; None: as stored): a micro-batch
     that is never assembled.  Accepted wherever [x_start, x_input] is (q_sample, p_losses_fn, p_losses, train_step,
-    ResidualDiffusion.forward / p_losses); the images are the store's, in [0, 1].  Everything is checked here: types, shapes,
-    then the ranges of the indices and the codes."""
+    ResidualDiffusion.forward / p_losses); the images are the store's, in [0, 1].  With `crop` (an int or (h, w)) every item is
+    first cut to the window of `windows` ((B, 2) = (y0, x0) per item, train_crop; None: zeros) and the codes apply to the crop
+    (DeviceSliceStore.batch has the rules); the batch is then (B, 1, h, w).  Everything is checked here: types, shapes, then the
+    ranges of the indices, the codes and the windows."""
 
-    def __init__(self, store, indices, codes=None):
-        self.indices, self.codes = check_batch("StoreBatch", store, indices, codes)
+    def __init__(self, store, indices, codes=None, windows=None, crop=None):
+        self.indices, self.codes, self.windows, self.crop = check_batch("StoreBatch", store, indices, codes, windows, crop)
         self.store = store
 
     def __len__(self):
@@ -299,7 +327,7 @@ class StoreBatch:
 
     @property
     def shape(self):
-        return (len(self.indices), 1, self.store.H, self.store.W)
+        return (len(self.indices), 1) + ((self.store.H, self.store.W) if self.crop is None else self.crop)
 
 
 def _check_qsample_store(fn, sb, t, schedule, noise, slice_seeds):
@@ -343,25 +371,35 @@ def _q_sample_store(sb, t, schedule, noise, slice_seeds, step, normalize, x0_out
         ac, bc = _upload_tables(ac, bc, dev)
         if noise is None and slice_seeds is None:
             slice_seeds = torch.randint(0, 1 << 62, (B,), device=dev, dtype=torch.int64)
-        # one table: the NDCT slots, the indices, then whichever of the codes, t and the seeds are on the host
+        # one table: the NDCT slots, the indices, then whichever of the codes, t and the seeds are on the host, then the windows
+        # (two rows: side by side the (B, 2) array)
         rows, at = [st.nd_index[sb.indices], sb.indices], {}
         for name, v in (("codes", sb.codes), ("t", t), ("seeds", slice_seeds)):
             if isinstance(v, np.ndarray):
                 at[name] = len(rows)
                 rows.append(v)
+        if sb.windows is not None:
+            at["windows"] = len(rows)
+            rows += window_rows(sb.windows)
         tab = upload_table(rows, dev)
         col = lambda name, v: tab[at[name]] if name in at else (None if v is None else v.contiguous())
         codes, tt, seeds = col("codes", sb.codes), col("t", t), col("seeds", slice_seeds)
         new = empty(dev)
-        x_in, x_res, times = new(B, 2, st.H, st.W), new(sb.shape), new(2, B)
+        x_in, x_res, times = new((B, 2) + sb.shape[2:]), new(sb.shape), new(2, B)
         x0 = new(sb.shape) if x0_out else None
         if noise is None:
             nz, out = None, new(sb.shape)
         else:
             nz, out = noise.detach().contiguous(), None
-        L.call("fd_res_qsample_store_f32", ptr(st.nd), ptr(st.ld), st.n_nd, st.n_ld, ptr(tab[0]), ptr(tab[1]), ptr(codes), ptr(tt),
-               ptr(ac), ptr(bc), ac.numel(), ptr(nz), ptr(seeds), int(step) & 0x7FFFFFFF, int(bool(normalize)), ptr(x_in), ptr(x_res),
-               ptr(out), ptr(times), ptr(x0), B, st.H, st.W, stream(dev))
+        if sb.crop is None:
+            L.call("fd_res_qsample_store_f32", ptr(st.nd), ptr(st.ld), st.n_nd, st.n_ld, ptr(tab[0]), ptr(tab[1]), ptr(codes), ptr(tt),
+                   ptr(ac), ptr(bc), ac.numel(), ptr(nz), ptr(seeds), int(step) & 0x7FFFFFFF, int(bool(normalize)), ptr(x_in),
+                   ptr(x_res), ptr(out), ptr(times), ptr(x0), B, st.H, st.W, stream(dev))
+        else:
+            L.call("fd_res_qsample_crop_f32", ptr(st.nd), ptr(st.ld), st.n_nd, st.n_ld, ptr(tab[0]), ptr(tab[1]), ptr(codes),
+                   ptr(col("windows", None)), ptr(tt), ptr(ac), ptr(bc), ac.numel(), ptr(nz), ptr(seeds), int(step) & 0x7FFFFFFF,
+                   int(bool(normalize)), ptr(x_in), ptr(x_res), ptr(out), ptr(times), ptr(x0), B, st.H, st.W, sb.crop[0], sb.crop[1],
+                   stream(dev))
     res = (x_in, x_res, (noise if out is None else out), times)
     return res + (x0,) if x0_out else res
 
@@ -376,7 +414,9 @@ def q_sample(x_start, x_input, t, schedule, noise=None, slice_seeds=None, step=0
     betas_cumsum[t] T; with x0_out a fifth result, the normalised x_start (pred_x0_noise's target).  Nothing is differentiable.
     x_start may be a StoreBatch (x_input is then None): the gather, the flip / rot90 of its codes and all of the above are one
     launch of fd_res_qsample_store_f32, bit for bit what store.batch() followed by this function gives; t and slice_seeds may
-    then stay on the host, and go up with the indices and the codes as one int64 table from pinned memory."""
+    then stay on the host, and go up with the indices and the codes as one int64 table from pinned memory.  A StoreBatch with a
+    crop takes fd_res_qsample_crop_f32 instead: every result is (B, ., h, w), with the bits of store.batch(..., windows, crop)
+    followed by this function."""
     fn = "q_sample"
     if isinstance(x_start, StoreBatch):
         if x_input is not None:

@@ -770,6 +770,27 @@ int fd_res_qsample_store_f32(const float *nd, const float *ld, int64_t n_nd, int
                              int normalize, float *x_in, float *x_res, float *noise_out, float *times, float *x0, int B,
                              int H, int W, void *stream);
 
+/* ---- the same batch cut to patches (fd_train_crop.hip; CropToFixed, data/transforms.py:196-249) --------------
+ * As above, with windows (int64 [B][2] = y0, x0 per item; null: all 0) and the crop CH x CW: item b is first cut to the window
+ * [y0, y0 + CH) x [x0, x0 + CW) of its slices (y0, x0 clamped to [0, max(H - CH, 0)] x [0, max(W - CW, 0)]); an axis no longer
+ * than the crop is taken whole and reflect-padded to it, (c - n) / 2 in front and the rest behind, without an edge repeat and
+ * with one reflection: a pad of at most H - 1 / W - 1 on either side.  The code then applies to the crop: source pixel
+ * (refl(y0 - pad_top + ic, H), refl(x0 - pad_left + jc, W)) for the crop pixel (ic, jc) the map above gives on CH x CW;
+ * refl(v, n) = -v below 0, 2 (n - 1) - v from n on.  An odd k needs CH == CW (it is dropped otherwise), whatever H and W are.
+ * Every output is [B][CH][CW]; the forms are those above on CH, CW (per pixel where CW % 4 != 0 or an output pointer is not
+ * 16-byte aligned).  The source rows are read at 4-byte alignment, so nd and ld need none.  H, W, CH, CW <= 32768.
+ * fd_store_crop_f32: x_start, x_input = the two cropped, transformed images: a copy.
+ * fd_res_qsample_crop_f32: fd_res_qsample_f32 on that batch without assembling it; output pixel p of the crop takes element
+ *   p % 4 of the keyed stream's group p / 4: the bits of fd_store_crop_f32 followed by fd_res_qsample_f32. */
+int fd_store_crop_f32(const float *nd, const float *ld, int64_t n_nd, int64_t n_ld, const int64_t *nd_slot,
+                      const int64_t *ld_slot, const int64_t *codes, const int64_t *windows, float *x_start, float *x_input,
+                      int B, int H, int W, int CH, int CW, void *stream);
+int fd_res_qsample_crop_f32(const float *nd, const float *ld, int64_t n_nd, int64_t n_ld, const int64_t *nd_slot,
+                            const int64_t *ld_slot, const int64_t *codes, const int64_t *windows, const int64_t *t,
+                            const float *alphas_cumsum, const float *betas_cumsum, int T, const float *noise,
+                            const int64_t *seeds, int noise_step, int normalize, float *x_in, float *x_res, float *noise_out,
+                            float *times, float *x0, int B, int H, int W, int CH, int CW, void *stream);
+
 /* ---- the two outer convolutions of the U-Net for training (fd_outer_train.hip; src/DADiff.py:553-555, 681) ----
  * Exact fp32 on the VALU, deterministic, no float atomics, no host synchronisation; out and dx of a slice do not depend on its
  * batch.  Byte bounds: DESIGN.md section 4.
