@@ -1137,6 +1137,41 @@ class ResidualDiffusion(nn.Module):
             t = torch.randint(0, self.num_timesteps, (imgs[0].shape[0],), device=imgs[0].device).long()
         return dt.p_losses_fn(model_fn, imgs, t, schedule, objective, loss_type, noise, slice_seeds, step, 1.0, normalize=True)
 
+    @torch.no_grad()
+    def eval_items(self, imgs, t, noise=None, slice_seeds=None, step=0, precision="fp32"):
+        """What forward() measures, per slice and forward-only: imgs, t, noise, slice_seeds and step as forward takes them (t is
+        required) -> one (B, 2) device tensor per U-Net the objective trains, diffusion_train.val_items of its output: column 0
+        the slice's loss against p_losses' target (the mean over the batch is forward()'s loss), column 1 the one-step
+        denoising error clamp(x_input - clamp(pred_res)) against x_start in [0, 1] units where the output is a residual
+        ('pred_res', and unet0 of 'pred_res_noise'), NaN elsewhere.  q_sample, then per U-Net its inference engine:
+        encode_condition, forward, val_items; unet0 gets times[0] (times[1] for 'pred_noise'), unet1 times[1].  Nothing asks for
+        the trainable view or touches requires_grad, so this runs on a model that never trained, on the EMA copy and on two
+        U-Nets.  precision: the engine's; 'fp32' by default, the precision training runs in, None for the model's sampling
+        precision.  The engines hold packed weights: after an optimiser step, weights_changed() comes first."""
+        fn = "ResidualDiffusion.eval_items"
+        _, schedule, objective, loss_type = dt._diffusion_args(fn, self)
+        if isinstance(imgs, dt.StoreBatch):
+            dt._check_qsample_store(fn, imgs, t, schedule, noise, slice_seeds)
+            x_in, x_res, noise, times, x0 = dt.q_sample(imgs, None, t, schedule, noise, slice_seeds, step, True, x0_out=True)
+        else:
+            if not isinstance(imgs, (list, tuple)) or len(imgs) != 2:
+                raise RuntimeError(f"{fn}: imgs must be [x_start, x_input] (condition=True without an input condition)")
+            dt._check_qsample(fn, imgs[0], imgs[1], t, schedule, noise, slice_seeds, dims=(4,))
+            x_in, x_res, noise, times, x0 = dt.q_sample(imgs[0], imgs[1], t, schedule, noise, slice_seeds, step, True, x0_out=True)
+        x_t, x_input = x_in[:, 0:1].contiguous(), x_in[:, 1:2].contiguous()
+        # (U-Net, its time input, its target, whether its output is a residual): UnetRes.forward's routing, p_losses_fn's targets
+        plan = {"pred_res": [("unet0", 0, x_res, True)], "pred_noise": [("unet0", 1, noise, False)],
+                "pred_res_noise": [("unet0", 0, x_res, True), ("unet1", 1, noise, False)],
+                "pred_x0_noise": [("unet0", 0, x0, False), ("unet1", 1, noise, False)]}[objective]
+        out = []
+        with torch.cuda.device(x_in.device):
+            for name, ti, target, residual in plan:
+                eng = getattr(self.model, name).engine(precision)
+                eng.encode_condition(x_input)
+                pred = eng.forward(x_t, x_input, times[ti])
+                out.append(dt.val_items(pred, target, loss_type, *((x_input, x0) if residual else ())))
+        return out
+
 
 class _Accel:
     """Stand-in for the accelerate attributes train.py reads (train.py:162-177)."""
@@ -1180,7 +1215,12 @@ class Trainer(object):
     rotations and no longer square slices; sample() and test() keep whole slices.
     `train_dataset` may be a data.DeviceSliceStore: train() then gathers (and augments) every micro-batch on the device and
     uploads no image.  `seed` keys what train() draws (diffusion_train.train_batch_indices / train_t_and_seeds / train_augment),
-    `log_every` is how often the loss is read back from the device.  One U-Net only (train() raises for two: RAdam)."""
+    `log_every` is how often the loss is read back from the device.  One U-Net only (train() raises for two: RAdam).
+    `val_dataset` (as train_dataset, or a data.DeviceSliceStore) is what validate() evaluates the EMA model on, forward-only: the
+    held-out loss and the one-step PSNR / RMSE per noise band of `val_bands` (increasing edges inside [0, T]), on the first
+    `val_items` items (None: all), keyed by `val_seed`, `val_batch_size` (item, band) pairs per launch sequence.  train() calls
+    it every `validate_every` steps (0: never) and, with `keep_best`, saves model-best.pt whenever a validation beats every
+    earlier one of this process.  All of it is off by default."""
 
     def __init__(self, opt, diffusion_model, folder=None, *, train_batch_size=16, gradient_accumulate_every=1,
                  augment_flip=True, train_lr=1e-4, train_num_steps=100000, ema_update_every=10, ema_decay=0.995,
@@ -1188,9 +1228,24 @@ class Trainer(object):
                  amp=False, fp16=False, split_batches=True, convert_image_to=None, condition=False, sub_dir=False,
                  equalizeHist=False, crop_patch=False, generation=False, num_unet=2, checkpoint_folder=None,
                  is_train=True, train_logger=None, dataset=None, device=None, train_dataset=None, seed=0, log_every=100,
-                 augment=False, crop_size=None):
+                 augment=False, crop_size=None, val_dataset=None, validate_every=0, val_bands=(0, 250, 500, 750, 1000),
+                 val_items=None, val_seed=0, val_batch_size=8, keep_best=False):
         import logging
         import os as _os
+        self.val_bands = dt.check_bands("Trainer", val_bands, getattr(diffusion_model, "num_timesteps", 1000))
+        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+        if not is_int(validate_every) or validate_every < 0 or not is_int(val_batch_size) or not 1 <= val_batch_size <= 65535 or \
+                not is_int(val_seed) or not (val_items is None or (is_int(val_items) and val_items >= 1)):
+            raise RuntimeError(f"Trainer: invalid validation arguments validate_every={validate_every!r} val_items={val_items!r} "
+                               f"val_seed={val_seed!r} val_batch_size={val_batch_size!r} (integers; validate_every >= 0, val_items "
+                               f"None or >= 1, 1 <= val_batch_size <= 65535)")
+        if validate_every > 0 and val_dataset is None:
+            raise RuntimeError(f"Trainer: validate_every={validate_every} needs a val_dataset")
+        self.val_dataset, self.validate_every, self.val_items = val_dataset, int(validate_every), val_items
+        self.val_seed, self.val_batch_size, self.keep_best = int(val_seed), int(val_batch_size), bool(keep_best)
+        self.val_log = []                    # validate()'s results of this process, in order; not part of a checkpoint
+        self.best = None                     # with keep_best: the entry of val_log that save("best") was last called for
+        self._val_store = None               # val_dataset on the device, made at the first validate()
         self.crop_size = None
         if crop_size is not None:
             from .data import crop_pair
@@ -1312,7 +1367,12 @@ class Trainer(object):
         its t, its noise and (with augment) its flip / rot90 codes are functions of (seed, s, m) alone; the losses stay on the
         device and are read every log_every steps.  From a data.DeviceSliceStore, or with augment or crop_size, a micro-batch is a
         diffusion_train.StoreBatch: its indices, codes, windows, t and seeds go up as one table and nothing waits for the host; a
-        host dataset without augment and crop_size is loaded, stacked and uploaded as before."""
+        host dataset without augment and crop_size is loaded, stacked and uploaded as before.
+        With validate_every > 0 every validate_every-th step is followed by validate(), which reads the weights and writes none:
+        the run's tensors and counters are those of the same run without it.  With keep_best a validation that beats every
+        earlier one of this process is followed by save("best") (_keep_best).  val_log and best are not part of a checkpoint,
+        whose keys stay diffusion_train.CHECKPOINT_KEYS: a resumed run starts with both empty and re-establishes its best at its
+        first validation, overwriting model-best.pt whatever the interrupted run had reached."""
         from .data import DeviceSliceStore
         self._setup_training()
         ds = self.train_dataset
@@ -1348,6 +1408,10 @@ class Trainer(object):
             self.step += 1
             if self.log_every > 0 and self.step % self.log_every == 0:                 # the one synchronisation of these steps
                 self.train_logger.info("Iters: [%d/%d], loss_unet0: %.6f" % (self.step, self.train_num_steps, float(self.losses[0])))
+            if self.validate_every > 0 and self.step % self.validate_every == 0:
+                res = self.validate()
+                if self.keep_best:
+                    self._keep_best(res)
             if self.step % every == 0:
                 milestone = self.step // every
                 self.sample(milestone)
@@ -1363,6 +1427,73 @@ class Trainer(object):
         model_sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
         data = dt.checkpoint_pack(self.step, model_sd, ema_sd, self.opt0.state_dict(), index, n)
         torch.save(data, self.results_folder + "/" + f"model-{milestone}.pt")
+
+    # ---- held-out evaluation during a run (the reference has none before its full test() at step 50 000, src/DADiff.py:1731-1745)
+    @torch.no_grad()
+    def validate(self, precision="fp32"):
+        """The EMA model (the model itself until train() copies it) on val_dataset: whole slices, no crop, no augmentation, the
+        first val_items of them (None: all).  Every item is evaluated once per noise band of val_bands, at the t and with the
+        noise diffusion_train.val_draws keys by (val_seed, item, band), in batches of val_batch_size (item, band) pairs through
+        diffusion_train.StoreBatch and ResidualDiffusion.eval_items on the `precision` engine; a host dataset goes to the device
+        once, at the first call.  Returns {"step", "bands", "loss", "psnr", "rmse", "n"}: loss, psnr and rmse are lists per
+        U-Net, then per band, of diffusion_train.val_summary's means (psnr and rmse of the one-step denoising error, NaN for an
+        output that is no residual), n the items per band; the dict is appended to val_log and logged, one line per band and
+        one over all bands.  Deterministic: the numbers depend on the weights alone, not on the step, the training seed or
+        val_batch_size."""
+        from .data import DeviceSliceStore
+        fn = "Trainer.validate"
+        if self.val_dataset is None:
+            raise RuntimeError(f"{fn}: give the constructor a val_dataset (__len__, __getitem__ -> [ndct, ldct])")
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{fn}: the model must live on the GPU (there is no CPU path)")
+        if self._val_store is None:
+            ds = self.val_dataset
+            self._val_store = ds if isinstance(ds, DeviceSliceStore) else DeviceSliceStore.from_dataset(ds, self.device)
+        store, ema = self._val_store, self.ema.ema_model
+        n = len(store) if self.val_items is None else min(int(self.val_items), len(store))
+        item, band, t, seeds = dt.val_draws(self.val_seed, range(n), self.val_bands, ema.num_timesteps)
+        self._fresh_engines()
+        rows = []
+        for s in range(0, len(item), self.val_batch_size):
+            sl = slice(s, s + self.val_batch_size)
+            rows.append(ema.eval_items(dt.StoreBatch(store, item[sl]), t[sl], slice_seeds=seeds[sl], precision=precision))
+        nb = len(self.val_bands) - 1
+        per_unet = [torch.cat([r[u] for r in rows]).cpu().numpy() for u in range(len(rows[0]))]      # the one synchronisation
+        sums = [dt.val_summary(v, band, nb) for v in per_unet]
+        res = {"step": self.step, "bands": list(self.val_bands), "loss": [s["loss"] for s in sums], "psnr": [s["psnr"] for s in sums],
+               "rmse": [s["rmse"] for s in sums], "n": sums[0]["n"]}
+        self.val_log.append(res)
+        info = self.train_logger.info
+        for u, s in enumerate(sums):
+            for k in range(nb):
+                info("Iters: [%d/%d], unet%d t in [%d, %d): val_loss: %.6f, val_psnr: %.4f, val_rmse: %.6f (%d items)" % (
+                    self.step, self.train_num_steps, u, self.val_bands[k], self.val_bands[k + 1], s["loss"][k], s["psnr"][k],
+                    s["rmse"][k], s["n"][k]))
+            tot = dt.val_summary(per_unet[u], np.zeros(len(band), dtype=np.int64), 1)
+            info("Iters: [%d/%d], unet%d val_loss: %.6f, val_psnr: %.4f, val_rmse: %.6f" % (
+                self.step, self.train_num_steps, u, tot["loss"][0], tot["psnr"][0], tot["rmse"][0]))
+        return res
+
+    @staticmethod
+    def _val_score(res):
+        """("psnr", the mean one-step PSNR over the items of every band) where a U-Net has a residual output, else ("loss", the
+        mean loss over items, bands and U-Nets)"""
+        mean = lambda per_band: float(np.average(per_band, weights=res["n"]))
+        psnr = [mean(p) for p in res["psnr"] if not np.isnan(p).all()]
+        if psnr:
+            return "psnr", float(np.mean(psnr))
+        return "loss", float(np.mean([mean(v) for v in res["loss"]]))
+
+    def _keep_best(self, res):
+        """save("best") if `res` (a result of validate()) beats every earlier one of this process: a higher mean one-step PSNR,
+        or a lower mean loss where no U-Net has a residual output.  self.best = {"step", "metric", "value"} of the winner."""
+        metric, value = self._val_score(res)
+        old = self.best
+        if old is None or np.isnan(old["value"]) or (value > old["value"] if metric == "psnr" else value < old["value"]):
+            self.best = {"step": res["step"], "metric": metric, "value": value}
+            self.save("best")
+            self.train_logger.info("Iters: [%d/%d], best val_%s so far: %.6f, saved model-best.pt" % (
+                self.step, self.train_num_steps, metric, value))
 
     # anatomy groups of the reference's 2020 test list, in item order: (name, slices per dose level); each holds
     # 4 dose levels back to back (src/DADiff.py:1918-1950).  "head" is taken from the END of the list, as there.

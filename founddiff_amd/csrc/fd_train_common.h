@@ -1,5 +1,5 @@
 // fd_train_common.h -- what the training kernels (fd_*_train.hip, fd_*_bwd.hip) share: the host-side size helpers, the sigmoid, the
-// four-element load / store, the fixed-order partial sum and the split-K tap correlation behind both convolution weight gradients.  Everything sits in an
+// four-element load / store, the workgroup sum, the fixed-order partial sum and the split-K tap correlation behind both convolution weight gradients.  Everything sits in an
 // anonymous namespace: each file that includes this header gets its own copy of the kernels it launches, and of no other.
 #pragma once
 #include <type_traits>
@@ -36,6 +36,20 @@ __device__ __forceinline__ void store4(float *p, int n, const float v[4]) {
         for (int e = 0; e < 4; ++e)
             if (e < n) p[e] = v[e];
     }
+}
+
+// the sum of v over the 256 lanes, in a fixed tree order; every lane gets it.  red: 256 floats of LDS, the caller's; a second sum
+// in one kernel takes a second array (the first one's red[0] may still be read when the next sum writes it)
+__device__ __forceinline__ float block_sum256(float v, float *red) {
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    return red[0];
 }
 
 // ---- the fixed-order partial sum -----------------------------------------------------------------------------------------------

@@ -26,19 +26,6 @@ constexpr int LS_G = 32;               // partials per launch_sum group
 constexpr int TT_COLS = 8;             // per-tensor table row: p, g, m, v, ema, flags, 0, 0 (int64 each)
 constexpr int64_t TT_ACTIVE = 1, TT_VEC = 2;
 
-// the sum of v over the 256 lanes, in a fixed tree order; every lane gets it
-__device__ __forceinline__ float block_sum256(float v, float *red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // ---- q_sample ------------------------------------------------------------------------------------------------------------------
 // grid (groups of four pixels / 256, b); one group per lane.  VEC: npix % 4 == 0 and every pointer 16-byte aligned.
 template <bool VEC, bool KEYED>

@@ -14,6 +14,10 @@
                                                    [x_start, x_input] is; q_sample then gathers, flips / rotates and diffuses it in
                                                    one launch (csrc/fd_train_data.hip), fed by one int64 table from pinned memory;
                                                    with windows and crop it is cut to patches in that launch (csrc/fd_train_crop.hip)
+    val_items(pred, target, loss_type, ...)        per slice, without a gradient: the loss and the one-step denoising error of a
+                                                   model output (csrc/fd_validate.hip); val_draws keys the t and the noise of a
+                                                   held-out evaluation per (item, noise band), val_summary reduces the rows per
+                                                   band on the host (ResidualDiffusion.eval_items, Trainer.validate)
 
 Binding for a training run:
 
@@ -31,7 +35,8 @@ The checkpoint of DADiff.Trainer.save (checkpoint_pack / checkpoint_unpack) has 
 reason: no test reads a file written by either.
 
 chunk_table, ema_schedule, adam_state_unpack, adam_state_pack, train_batch_indices, train_t_and_seeds, train_augment,
-augment_source_index, train_crop, crop_source_index, checkpoint_pack and checkpoint_unpack are pure host code.
+augment_source_index, train_crop, crop_source_index, checkpoint_pack, checkpoint_unpack, check_bands, val_draws and val_summary are
+pure host code.
 """
 import numpy as np
 import torch
@@ -42,7 +47,8 @@ from .data import check_batch, crop_pads, crop_pair, upload_table, window_rows
 
 __all__ = ["q_sample", "residual_loss", "p_losses_fn", "p_losses", "ClipAdamEMA", "train_step", "chunk_table", "ema_schedule",
            "adam_state_unpack", "adam_state_pack", "train_batch_indices", "train_t_and_seeds", "train_augment", "augment_source_index",
-           "train_crop", "crop_source_index", "StoreBatch", "checkpoint_pack", "checkpoint_unpack", "CHUNK"]
+           "train_crop", "crop_source_index", "StoreBatch", "checkpoint_pack", "checkpoint_unpack", "CHUNK", "check_bands", "val_draws",
+           "val_items", "val_summary"]
 
 CHUNK = 4096                      # elements of a parameter per workgroup (fd_opt_chunk_elems())
 _LOSS_TYPES = {"l1": 1, "l2": 2}
@@ -192,6 +198,55 @@ def crop_source_index(code, y0, x0, H, W, ch, cw):
     def refl(v, n):
         return np.where(v < 0, -v, np.where(v >= n, 2 * (n - 1) - v, v))
     return refl(y0 + ic - crop_pads(H, ch)[0], H), refl(x0 + jc - crop_pads(W, cw)[0], W)
+
+
+# What Trainer.validate draws is a pure function of (val_seed, dataset index, band): the same items meet the same t and the same
+# noise at every validation of every run, so two numbers differ by the weights alone.
+def check_bands(fn, bands, num_timesteps):
+    """`bands` as a tuple of ints: at least two strictly increasing edges inside [0, num_timesteps]"""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if not isinstance(bands, (tuple, list)) or len(bands) < 2 or not all(is_int(v) for v in bands):
+        raise RuntimeError(f"{fn}: bands must be a tuple of at least two integer edges (got {bands!r})")
+    edges = tuple(int(v) for v in bands)
+    if any(hi <= lo for lo, hi in zip(edges, edges[1:])) or edges[0] < 0 or edges[-1] > int(num_timesteps):
+        raise RuntimeError(f"{fn}: the band edges {edges} must increase strictly inside [0, {int(num_timesteps)}]")
+    return edges
+
+
+def val_draws(val_seed, indices, bands, num_timesteps):
+    """(item, band, t, slice_seeds), four int64 arrays with one row per (item, band) pair, items outer and bands inner, of a
+    validation over the dataset items `indices`.  `bands` are increasing edges inside [0, num_timesteps]; band k is
+    [bands[k], bands[k + 1]): t = bands[k] + _mix64(val_seed, index, k, 0x76) % (bands[k + 1] - bands[k]), the slice's noise seed
+    _mix64(val_seed, index, k, 0x6E) >> 2 (62 bits, as q_sample draws them).  Both are functions of (val_seed, index, k) alone:
+    not of the training seed, the step, or what else is evaluated with the item."""
+    edges = check_bands("val_draws", bands, num_timesteps)
+    rows = [(int(i), k, lo + _mix64(val_seed, i, k, 0x76) % (hi - lo), _mix64(val_seed, i, k, 0x6E) >> 2)
+            for i in indices for k, (lo, hi) in enumerate(zip(edges, edges[1:]))]
+    a = np.asarray(rows, dtype=np.int64).reshape(-1, 4)
+    return a[:, 0].copy(), a[:, 1].copy(), a[:, 2].copy(), a[:, 3].copy()
+
+
+def val_summary(items, band, n_bands):
+    """The rows of val_items gathered on the host, (n, 2) = (loss, one-step MSE in [0, 1] units) with their band indices (n,),
+    per band in float64: {"loss": mean loss, "mse": mean MSE, "psnr": mean of -10 log10(mse), "rmse": mean of sqrt(mse), "n": the
+    item count}, lists of n_bands.  PSNR and RMSE are averaged over items, as the reference averages its per-slice metrics
+    (src/DADiff.py:1883-1886, 1952).  A band without items has n = 0 and NaN means; NaN rows (no residual output) give NaN."""
+    it, bd = np.asarray(items, dtype=np.float64), np.asarray(band)
+    if it.ndim != 2 or it.shape[1] != 2 or bd.shape != (it.shape[0],) or bd.dtype.kind not in "iu" or int(n_bands) < 1:
+        raise RuntimeError(f"val_summary: inconsistent shapes items{it.shape} band{bd.shape} (items (n, 2), band (n,) integers, "
+                           f"n_bands >= 1)")
+    if bd.size and (bd.min() < 0 or bd.max() >= n_bands):
+        raise RuntimeError(f"val_summary: band {int(bd[(bd < 0) | (bd >= n_bands)][0])} outside [0, {int(n_bands)})")
+    out = {"loss": [], "mse": [], "psnr": [], "rmse": [], "n": []}
+    mean = lambda v: float(v.sum() / v.size) if v.size else float("nan")
+    for k in range(int(n_bands)):
+        rows = it[bd == k]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cols = (rows[:, 0], rows[:, 1], -10.0 * np.log10(rows[:, 1]), np.sqrt(rows[:, 1]))
+        for name, v in zip(("loss", "mse", "psnr", "rmse"), cols):
+            out[name].append(mean(v))
+        out["n"].append(int(rows.shape[0]))
+    return out
 
 
 CHECKPOINT_KEYS = ("step", "model", "opt0", "ema", "scaler")
@@ -498,6 +553,38 @@ def residual_loss(pred, target, loss_type, scale=1.0):
     The target gets no gradient."""
     _check_loss("residual_loss", pred, target, loss_type, scale)
     return _Loss.apply(pred, target, loss_type, scale)
+
+
+def val_items(pred, target, loss_type, x_input=None, x_start=None):
+    """(B, 2) on the device, one row per slice, from one pass of fd_val_items_f32 (csrc/fd_validate.hip) that writes no gradient:
+    column 0 = the slice's mean of |pred - target| ('l1') or (pred - target)^2 ('l2'), so that its mean over the batch is
+    residual_loss(pred, target, loss_type); column 1 = the one-step denoising error of a residual output, the mean of
+    (u(x0_hat) - u(x_start))^2 with x0_hat = clamp(x_input - clamp(pred, -1, 1), -1, 1) -- the samplers' last step, applied at
+    whatever noise level pred was made at -- and u(v) = clamp((v + 1) / 2, 0, 1), the [0, 1] units of compute_psnr / compute_rmse.
+    x_input and x_start are the normalised images ([-1, 1], as q_sample returns them), shaped as pred; give both, or neither:
+    column 1 is then NaN.  A slice's row does not depend on the rest of its batch.  Nothing is differentiable."""
+    fn = "val_items"
+    _check_f32(fn, (("pred", pred), ("target", target), ("x_input", x_input), ("x_start", x_start)), optional=("x_input", "x_start"))
+    if loss_type not in _LOSS_TYPES:
+        raise RuntimeError(f"{fn}: invalid loss type {loss_type!r} ('l1' or 'l2')")
+    if (x_input is None) != (x_start is None):
+        raise RuntimeError(f"{fn}: give both x_input and x_start, or neither")
+    named = (("pred", pred), ("target", target), ("x_input", x_input), ("x_start", x_start))
+    if pred.dim() < 1 or pred.numel() < 1 or any(v is not None and v.shape != pred.shape for _, v in named):
+        shapes = " ".join(f"{n}{tuple(v.shape)}" for n, v in named if v is not None)
+        raise RuntimeError(f"{fn}: inconsistent shapes {shapes} (equal, (B, ...))")
+    if pred.shape[0] > 65535:
+        raise RuntimeError(f"{fn}: unsupported shape pred{tuple(pred.shape)} (at most 65535 slices)")
+    _check_gpu(fn, named)
+    dev, B = pred.device, pred.shape[0]
+    npix = pred.numel() // B
+    with torch.no_grad(), torch.cuda.device(dev):
+        pf, tf = pred.detach().contiguous(), target.detach().contiguous()
+        xi, x0 = (None, None) if x_input is None else (x_input.detach().contiguous(), x_start.detach().contiguous())
+        items = empty(dev)(B, 2)
+        ws = workspace("fd_val_items_ws_floats", dev, B, npix)
+        L.call("fd_val_items_f32", ptr(pf), ptr(tf), ptr(xi), ptr(x0), _LOSS_TYPES[loss_type], ptr(items), ptr(ws), B, npix, stream(dev))
+    return items
 
 
 def p_losses_fn(model_fn, imgs, t, schedule, objective="pred_res", loss_type="l1", noise=None, slice_seeds=None, step=0, scale=1.0,

@@ -748,6 +748,18 @@ int fd_opt_adam_ema_f32(const int64_t *chunks, const int64_t *tensors, const int
                         double lr, double beta1, double beta2, double eps, int ema_mode, double ema_decay, int zero_grad,
                         int skip_nonfinite, void *stream);
 
+/* ---- what a held-out evaluation reads off a model output (fd_validate.hip) -------------------------------------
+ * fd_val_items_f32: items [B][2], from one pass over pred, target (and x_input, x_start) [B][npix] and two small sums, without
+ *   a gradient.  items[b][0] = mean_i(|pred - target| or (pred - target)^2) (loss_type 1 = l1, 2 = l2): its mean over b is the
+ *   loss of fd_res_loss_f32.  items[b][1] = mean_i((u(x0_hat) - u(x_start))^2), x0_hat = clamp(x_input - clamp(pred, -1, 1), -1, 1)
+ *   (the samplers' last step, applied to a residual output), u(v) = clamp((v + 1) / 2, 0, 1): the one-step denoising error in
+ *   the [0, 1] units of fd_metrics.  x_input and x_start: both, or both null (column 1 is then NaN).  Deterministic, no float
+ *   atomics; a slice's row depends on npix alone, not on its batch.  The shape limits are fd_res_loss_f32's.
+ *   ws: fd_val_items_ws_floats(B, npix) floats (0: unsupported shape). */
+int64_t fd_val_items_ws_floats(int B, int64_t npix);
+int fd_val_items_f32(const float *pred, const float *target, const float *x_input, const float *x_start, int loss_type,
+                     float *items, float *ws, int B, int64_t npix, void *stream);
+
 /* ---- a training batch from a slice store on the device (fd_train_data.hip; data/pdf_dataset.py:521-545) -------
  * nd [n_nd][H][W], ld [n_ld][H][W] fp32 in [0, 1].  Item b of the batch is the pair nd[nd_slot[b]], ld[ld_slot[b]] (int64 [B],
  * clamped to the store), both under the transform codes[b] (int64 [B], low 4 bits; a null codes is all 0):
