@@ -11,7 +11,8 @@ through `founddiff_amd.engine.DAEngine`.
 Training runs on the same classes: `Unet.trainable()` is a `unet_train.UnetTrunk` over the very
 parameters of the tree, `Unet.train_forward` runs the frozen DA-CLIP tower on the fp32 engine and the trunk under autograd on the HIP
 training kernels, `ResidualDiffusion.forward` / `p_losses` are the reference's (diffusion_train), and `Trainer.train / save / load`
-are its loop and checkpoint around `diffusion_train.ClipAdamEMA`.  One U-Net only: the reference optimises two with RAdam.
+are its loop and checkpoint around `diffusion_train.ClipAdamEMA`.  Two U-Nets, which the reference optimises with RAdam, train
+around `diffusion_train.ClipRAdamEMA` on request: `UnetRes.trainable()` and `Trainer(optimizer="radam")`; the defaults raise.
 """
 import copy
 import ctypes as C
@@ -305,14 +306,29 @@ class UnetRes(nn.Module):
                               learned_sinusoidal_dim=learned_sinusoidal_dim, condition=condition,
                               input_condition=input_condition, precision=precision, clip_cfg=clip_cfg)
 
+    def _unets(self):
+        return [self.unet0, self.unet1] if self.num_unet == 2 else [self.unet0]
+
+    def trainable(self):
+        """Unet.trainable() of every U-Net of this model: the list of views (one per U-Net).  With two U-Nets this is the
+        opt-in to training them: forward, under gradients, then returns both training forwards, and
+        ResidualDiffusion.forward / p_losses two losses (Trainer(optimizer='radam') asks for it itself)."""
+        return [u.trainable() for u in self._unets()]
+
     def forward(self, x, time, x_self_cond=None, reuse_condition=False):
         """src/DADiff.py:817-836.  time = [alphas_cumsum[t]*T, betas_cumsum[t]*T].  With gradients enabled on a model whose
         trainable view exists (Unet.trainable(): ResidualDiffusion.forward and Trainer.train ask for it) the call is a training
         forward, Unet.train_forward; under no_grad, and on a model that never trained, it is the engine as ever."""
-        if torch.is_grad_enabled() and self.unet0._trainable is not None:
-            if self.num_unet != 1:
-                raise NotImplementedError("training two U-Nets: the reference optimises them with RAdam, which is not built "
-                                          "(DESIGN.md section 8)")
+        views = [u._trainable is not None for u in self._unets()]
+        if torch.is_grad_enabled() and any(views):
+            if self.num_unet == 2:
+                # two training forwards (src/DADiff.py:817-823): unet0 at time[0], unet1 at time[1], each behind its own frozen tower
+                if not all(views):
+                    raise NotImplementedError("training two U-Nets: the reference optimises them with RAdam, and one of the two has "
+                                              "no trainable view: call model.trainable() (DESIGN.md section 8)")
+                if self.objective not in ("pred_res_noise", "pred_x0_noise"):
+                    raise ValueError(f"objective {self.objective!r} needs num_unet=1 (src/DADiff.py:826-831)")
+                return [self.unet0.train_forward(x, time[0]), self.unet1.train_forward(x, time[1])]
             if self.objective not in ("pred_res", "pred_noise"):
                 raise ValueError(f"objective {self.objective!r} needs num_unet=2 (src/DADiff.py:826-831)")
             return [self.unet0.train_forward(x, time[1] if self.objective == "pred_noise" else time[0])]
@@ -1110,8 +1126,12 @@ class ResidualDiffusion(nn.Module):
 
     def _train_ready(self, fn):
         if getattr(self.model, "num_unet", 1) != 1:
-            raise NotImplementedError(f"{fn}: training two U-Nets: the reference optimises them with RAdam, which is not built "
-                                      "(DESIGN.md section 8); objectives 'pred_res' and 'pred_noise' train one")
+            # opt-in: the raising default is pinned by tests
+            if any(getattr(self.model, n)._trainable is None for n in ("unet0", "unet1")):
+                raise NotImplementedError(f"{fn}: training two U-Nets: the reference optimises them with RAdam, and this is opt-in: "
+                                          "call model.trainable() on the UnetRes first, or train through Trainer(optimizer=\"radam\") "
+                                          "(DESIGN.md section 8); objectives 'pred_res' and 'pred_noise' train one")
+            return
         self.model.unet0.trainable()
 
     def p_losses(self, imgs, t, noise=None, slice_seeds=None, step=0, scale=1.0):
@@ -1124,7 +1144,8 @@ class ResidualDiffusion(nn.Module):
         """src/DADiff.py:1382-1397: imgs = [x_start, x_input], (B, 1, H, W) in [0, 1], or a diffusion_train.StoreBatch -> the list
         of losses (one U-Net: one), differentiable in the trunk's parameters.  t (B,) int64 is drawn as the reference draws it unless given; noise, or
         slice_seeds (+ step) for the keyed per-slice stream, as diffusion_train.q_sample takes them.  RuntimeError for CPU tensors
-        (there is no CPU path), NotImplementedError for two U-Nets."""
+        (there is no CPU path).  Two U-Nets ('pred_res_noise', 'pred_x0_noise') give two losses once model.trainable() was called
+        (Trainer(optimizer='radam') does), NotImplementedError before that."""
         fn = "ResidualDiffusion.forward"
         self._train_ready(fn)
         model_fn, schedule, objective, loss_type = dt._diffusion_args(fn, self)
@@ -1215,7 +1236,13 @@ class Trainer(object):
     rotations and no longer square slices; sample() and test() keep whole slices.
     `train_dataset` may be a data.DeviceSliceStore: train() then gathers (and augments) every micro-batch on the device and
     uploads no image.  `seed` keys what train() draws (diffusion_train.train_batch_indices / train_t_and_seeds / train_augment),
-    `log_every` is how often the loss is read back from the device.  One U-Net only (train() raises for two: RAdam).
+    `log_every` is how often the loss is read back from the device.
+    `optimizer`: None or 'adam' is clip + Adam(`adam_betas`) on one U-Net, and train() / save() raise NotImplementedError for
+    two; 'radam' is the reference's optimiser of two U-Nets (src/DADiff.py:1598-1602, 1707): one diffusion_train.ClipRAdamEMA
+    with `radam_betas` (RAdam's defaults, as there) over the trainable parameters of every U-Net -- one clip over both, both
+    updates and the one EMA in three launches -- and a checkpoint with 'opt0' and 'opt1' (diffusion_train.CHECKPOINT_KEYS_2).
+    It is opt-in because the raising default is pinned by tests.  On one U-Net 'radam' is the reference's
+    commented-out alternative (line 1594): the checkpoint keeps its five keys, 'opt0' in RAdam's layout.
     `val_dataset` (as train_dataset, or a data.DeviceSliceStore) is what validate() evaluates the EMA model on, forward-only: the
     held-out loss and the one-step PSNR / RMSE per noise band of `val_bands` (increasing edges inside [0, T]), on the first
     `val_items` items (None: all), keyed by `val_seed`, `val_batch_size` (item, band) pairs per launch sequence.  train() calls
@@ -1228,10 +1255,15 @@ class Trainer(object):
                  amp=False, fp16=False, split_batches=True, convert_image_to=None, condition=False, sub_dir=False,
                  equalizeHist=False, crop_patch=False, generation=False, num_unet=2, checkpoint_folder=None,
                  is_train=True, train_logger=None, dataset=None, device=None, train_dataset=None, seed=0, log_every=100,
-                 augment=False, crop_size=None, val_dataset=None, validate_every=0, val_bands=(0, 250, 500, 750, 1000),
-                 val_items=None, val_seed=0, val_batch_size=8, keep_best=False):
+                 augment=False, crop_size=None, optimizer=None, radam_betas=(0.9, 0.999), val_dataset=None, validate_every=0,
+                 val_bands=(0, 250, 500, 750, 1000), val_items=None, val_seed=0, val_batch_size=8, keep_best=False):
         import logging
         import os as _os
+        if optimizer not in (None, "adam", "radam"):
+            raise RuntimeError(f"Trainer: optimizer must be None, 'adam' or 'radam' (got {optimizer!r})")
+        if len(tuple(radam_betas)) != 2 or not all(isinstance(b, (int, float)) and 0 <= b < 1 for b in radam_betas):
+            raise RuntimeError(f"Trainer: radam_betas must be two numbers in [0, 1) (got {radam_betas!r})")
+        self.optimizer, self.radam_betas = optimizer or "adam", tuple(float(b) for b in radam_betas)
         self.val_bands = dt.check_bands("Trainer", val_bands, getattr(diffusion_model, "num_timesteps", 1000))
         is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
         if not is_int(validate_every) or validate_every < 0 or not is_int(val_batch_size) or not 1 <= val_batch_size <= 65535 or \
@@ -1301,7 +1333,10 @@ class Trainer(object):
         data = torch.load(str(path), map_location="cpu", weights_only=False)
         if for_training:
             index, n = self._setup_training()
-            step, model_sd, ema_sd, opt_sd = dt.checkpoint_unpack(data, index, n)
+            if self._two_unets():
+                step, model_sd, ema_sd, opt_sd = dt.checkpoint_unpack2(data, index, self._unet_index())
+            else:
+                step, model_sd, ema_sd, opt_sd = dt.checkpoint_unpack(data, index, n, optimizer=self.optimizer)
             load_weights(self.model, model_sd, f"{path}['model']")
             load_weights(self.ema.ema_model, ema_sd, f"{path}['ema']")
             self.model.to(self.device)
@@ -1335,10 +1370,10 @@ class Trainer(object):
         """The EMA copy and the optimiser, made once: (the places of the trainable parameters in diffusion.parameters(), their
         number).  Until here self.ema.ema_model is self.model."""
         dif = self.model
-        if getattr(dif.model, "num_unet", 1) != 1:
-            raise NotImplementedError("Trainer.train: two U-Nets are optimised with RAdam in the reference, which is not built "
-                                      "(DESIGN.md section 8)")
-        dif.model.unet0.trainable()
+        if getattr(dif.model, "num_unet", 1) != 1 and self.optimizer != "radam":
+            raise NotImplementedError("Trainer.train: two U-Nets are optimised with RAdam in the reference: pass optimizer='radam' "
+                                      "(the default, Adam, trains one U-Net; DESIGN.md section 8)")
+        dif.model.trainable()
         params = list(dif.parameters())
         index = [i for i, p in enumerate(params) if p.requires_grad]
         if self.opt0 is None:
@@ -1347,10 +1382,19 @@ class Trainer(object):
             if self.ema.ema_model is dif:
                 self.ema = _EMAView(dif.clone())
             eparams = list(self.ema.ema_model.parameters())
-            self.opt0 = dt.ClipAdamEMA([params[i] for i in index], [eparams[i] for i in index], lr=self.train_lr,
-                                       betas=self.adam_betas, max_norm=1.0, ema_beta=self.ema_decay,
-                                       ema_update_every=self.ema_update_every)
+            cls, betas = (dt.ClipRAdamEMA, self.radam_betas) if self.optimizer == "radam" else (dt.ClipAdamEMA, self.adam_betas)
+            self.opt0 = cls([params[i] for i in index], [eparams[i] for i in index], lr=self.train_lr, betas=betas, max_norm=1.0,
+                            ema_beta=self.ema_decay, ema_update_every=self.ema_update_every)
         return index, len(params)
+
+    def _two_unets(self):
+        return getattr(self.model.model, "num_unet", 1) == 2
+
+    def _unet_index(self):
+        """the places of unet0.parameters() and of unet1.parameters() in diffusion.parameters(), each in its U-Net's order
+        (diffusion_train.checkpoint_pack2)"""
+        place = {id(p): i for i, p in enumerate(self.model.parameters())}
+        return tuple([place[id(p)] for p in u.parameters()] for u in (self.model.model.unet0, self.model.model.unet1))
 
     def _fresh_engines(self):
         """before anything samples after a step has written the weights"""
@@ -1371,8 +1415,9 @@ class Trainer(object):
         With validate_every > 0 every validate_every-th step is followed by validate(), which reads the weights and writes none:
         the run's tensors and counters are those of the same run without it.  With keep_best a validation that beats every
         earlier one of this process is followed by save("best") (_keep_best).  val_log and best are not part of a checkpoint,
-        whose keys stay diffusion_train.CHECKPOINT_KEYS: a resumed run starts with both empty and re-establishes its best at its
-        first validation, overwriting model-best.pt whatever the interrupted run had reached."""
+        whose keys stay diffusion_train.CHECKPOINT_KEYS (CHECKPOINT_KEYS_2 for two U-Nets): a resumed run starts with both empty
+        and re-establishes its best at its first validation, overwriting model-best.pt whatever the interrupted run had reached.
+        optimizer='radam' runs the same loop around ClipRAdamEMA, on one U-Net or two; the log line then has loss_unet1 too."""
         from .data import DeviceSliceStore
         self._setup_training()
         ds = self.train_dataset
@@ -1407,7 +1452,8 @@ class Trainer(object):
             self._stale = True
             self.step += 1
             if self.log_every > 0 and self.step % self.log_every == 0:                 # the one synchronisation of these steps
-                self.train_logger.info("Iters: [%d/%d], loss_unet0: %.6f" % (self.step, self.train_num_steps, float(self.losses[0])))
+                self.train_logger.info("Iters: [%d/%d], " % (self.step, self.train_num_steps) +
+                                       ", ".join("loss_unet%d: %.6f" % (u, float(v)) for u, v in enumerate(self.losses)))
             if self.validate_every > 0 and self.step % self.validate_every == 0:
                 res = self.validate()
                 if self.keep_best:
@@ -1425,7 +1471,10 @@ class Trainer(object):
         index, n = self._setup_training()
         ema_sd = {k: v.detach().clone() for k, v in self.ema.ema_model.state_dict().items()}
         model_sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        data = dt.checkpoint_pack(self.step, model_sd, ema_sd, self.opt0.state_dict(), index, n)
+        if self._two_unets():
+            data = dt.checkpoint_pack2(self.step, model_sd, ema_sd, self.opt0.state_dict(), index, self._unet_index())
+        else:
+            data = dt.checkpoint_pack(self.step, model_sd, ema_sd, self.opt0.state_dict(), index, n)
         torch.save(data, self.results_folder + "/" + f"model-{milestone}.pt")
 
     # ---- held-out evaluation during a run (the reference has none before its full test() at step 50 000, src/DADiff.py:1731-1745)

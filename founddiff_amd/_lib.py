@@ -174,6 +174,7 @@ SIGNATURES = {
     "fd_opt_sumsq_f32": (i32, [vp, vp, vp, i32, vp]),
     "fd_opt_clip_coef": (i32, [vp, i32, vp, vp, i32, f32, i32, vp, vp]),
     "fd_opt_adam_ema_f32": (i32, [vp, vp, vp, vp, i32, f64, f64, f64, f64, i32, f64, i32, i32, vp]),
+    "fd_opt_radam_ema_f32": (i32, [vp, vp, vp, vp, i32, f64, f64, f64, f64, i32, f64, i32, i32, vp]),
     "fd_val_items_ws_floats": (i64, [i32, i64]),
     "fd_val_items_f32": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, i64, vp]),
     "fd_store_gather_f32": (i32, [vp, vp, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp]),

@@ -7,6 +7,7 @@
 //   fd_opt_sumsq_f32       per chunk sum of g^2                                  \  clip_grad_norm_(max_norm) + Adam + zero_grad
 //   fd_opt_clip_coef       total norm, clip coefficient, non-finite flag, steps   > + the EMA update, over a chunk table the host
 //   fd_opt_adam_ema_f32    the update itself                                     /  builds once
+//   fd_opt_radam_ema_f32   the same with torch.optim.RAdam's update rule (two U-Nets, src/DADiff.py:1598-1602) in Adam's place
 //
 // No float atomics; every sum has a fixed order that depends on the tensor's own size only (a slice's loss partials on npix, a
 // parameter's chunks on its numel); nothing synchronises with the host; the clip coefficient, the non-finite flag and the Adam step
@@ -222,7 +223,11 @@ struct AdamK {
     int ema_mode, zero_grad;
 };
 
-template <bool VEC>
+// RULE of adam4: Adam; RAdam on a rectified step (step_size holds lr / bc1 * r * sqrt(bc2), eps joins sqrt(v) uncorrected);
+// RAdam before that (step_size = lr / bc1, v is updated and does not enter p)
+constexpr int RULE_ADAM = 0, RULE_RADAM_RECT = 1, RULE_RADAM_PLAIN = 2;
+
+template <bool VEC, int RULE = RULE_ADAM>
 __device__ __forceinline__ void adam4(const AdamK &k, float *p, float *g, float *m, float *v, float *ema, int n) {
     float pv[4], gv[4], mv[4], vv[4], ev[4];
     load4<VEC>(p, n, pv);
@@ -236,8 +241,14 @@ __device__ __forceinline__ void adam4(const AdamK &k, float *p, float *g, float 
         const float gc = k.coef * gv[e];
         mv[e] = fmaf(k.w1, gc - mv[e], mv[e]);
         vv[e] = fmaf(k.w2 * gc, gc, k.beta2 * vv[e]);
-        const float denom = sqrtf(vv[e]) / k.bc2_sqrt + k.eps;
-        pv[e] = fmaf(-k.step_size, mv[e] / denom, pv[e]);
+        if constexpr (RULE == RULE_ADAM) {
+            const float denom = sqrtf(vv[e]) / k.bc2_sqrt + k.eps;
+            pv[e] = fmaf(-k.step_size, mv[e] / denom, pv[e]);
+        } else if constexpr (RULE == RULE_RADAM_RECT) {
+            pv[e] = fmaf(-k.step_size, mv[e] / (sqrtf(vv[e]) + k.eps), pv[e]);
+        } else {
+            pv[e] = fmaf(-k.step_size, mv[e], pv[e]);
+        }
         if (lerp) ev[e] = fmaf(-k.ema_w, ev[e] - pv[e], ev[e]);
         gv[e] = 0.f;
     }
@@ -287,6 +298,59 @@ __global__ __launch_bounds__(256) void opt_adam_kernel(const int64_t *__restrict
         if (o.vec && n == 4) adam4<true>(k, p + i0, g + i0, m + i0, v + i0, ema ? ema + i0 : nullptr, 4);
         else adam4<false>(k, p + i0, g + i0, m + i0, v + i0, ema ? ema + i0 : nullptr, n);
     }
+}
+
+template <int RULE>
+__device__ __forceinline__ void radam_chunk(const AdamK &k, const OptChunk &o, int tid) {
+    float *p = (float *)o.row[0] + o.off, *g = (float *)o.row[1] + o.off, *m = (float *)o.row[2] + o.off;
+    float *v = (float *)o.row[3] + o.off, *ema = o.row[4] ? (float *)o.row[4] + o.off : nullptr;
+#pragma unroll
+    for (int j = 0; j < OPT_VPL; ++j) {
+        const int i0 = 4 * (j * 256 + tid);
+        if (i0 >= o.len) continue;
+        const int n = min(4, o.len - i0);
+        if (o.vec && n == 4) adam4<true, RULE>(k, p + i0, g + i0, m + i0, v + i0, ema ? ema + i0 : nullptr, 4);
+        else adam4<false, RULE>(k, p + i0, g + i0, m + i0, v + i0, ema ? ema + i0 : nullptr, n);
+    }
+}
+
+// grid (chunk).  torch.optim.RAdam's update (_single_tensor_radam) of this chunk's tensor at its own step count: the variance
+// rectification is on or off per tensor, so per workgroup, and tensors at different steps take different branches in one launch
+__global__ __launch_bounds__(256) void opt_radam_kernel(const int64_t *__restrict__ chunks, const int64_t *__restrict__ tensors,
+                                                       const int *__restrict__ steps, const float *__restrict__ rec, double lr,
+                                                       double beta1, double beta2, double eps, int ema_mode, double ema_decay,
+                                                       int zero_grad, int skip_nonfinite) {
+    __shared__ float s_step;
+    __shared__ int s_rect;
+    const int tid = threadIdx.x;
+    const OptChunk o = opt_chunk(chunks, tensors);
+    if (!o.active) return;
+    if (skip_nonfinite && rec[2] != 0.f) return;
+    if (tid == 0) {                                                      // this tensor's scalars, in double (radam_scalars)
+        const double step = (double)steps[chunks[3 * (int64_t)blockIdx.x]];
+        const double b2s = pow(beta2, step);
+        const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - b2s;
+        const double rho_inf = 2.0 / (1.0 - beta2) - 1.0, rho = rho_inf - 2.0 * step * b2s / bc2;
+        double size = lr / bc1;
+        const int rect = rho > 5.0;                                      // rho <= rho_inf: with rho_inf <= 5 nothing divides by rho_inf - 4
+        if (rect) size *= sqrt((rho - 4.0) * (rho - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho)) * sqrt(bc2);
+        s_step = (float)size;
+        s_rect = rect;
+    }
+    __syncthreads();
+    AdamK k;
+    k.coef = rec[1];
+    k.w1 = (float)(1.0 - beta1);
+    k.beta2 = (float)beta2;
+    k.w2 = (float)(1.0 - beta2);
+    k.step_size = s_step;
+    k.bc2_sqrt = 1.f;
+    k.eps = (float)eps;
+    k.ema_w = (float)(1.0 - ema_decay);
+    k.ema_mode = ema_mode;
+    k.zero_grad = zero_grad;
+    if (s_rect) radam_chunk<RULE_RADAM_RECT>(k, o, tid);
+    else radam_chunk<RULE_RADAM_PLAIN>(k, o, tid);
 }
 
 }  // namespace
@@ -388,5 +452,17 @@ extern "C" int fd_opt_adam_ema_f32(const int64_t *chunks, const int64_t *tensors
     hipLaunchKernelGGL(opt_adam_kernel, dim3((unsigned)nchunk), dim3(256), 0, (hipStream_t)stream, chunks, tensors, steps, rec, lr,
                        beta1, beta2, eps, ema_mode, ema_decay, zero_grad, skip_nonfinite);
     FD_LAUNCH_OK("fd_opt_adam_ema_f32");
+    return FD_OK;
+}
+
+extern "C" int fd_opt_radam_ema_f32(const int64_t *chunks, const int64_t *tensors, const int *steps, const float *rec, int nchunk,
+                                    double lr, double beta1, double beta2, double eps, int ema_mode, double ema_decay,
+                                    int zero_grad, int skip_nonfinite, void *stream) {
+    FD_REQUIRE(chunks && tensors && steps && rec, "fd_opt_radam_ema_f32: null pointer");
+    FD_REQUIRE(nchunk > 0, "fd_opt_radam_ema_f32: no chunks (nchunk=%d)", nchunk);
+    FD_REQUIRE(ema_mode >= 0 && ema_mode <= 2, "fd_opt_radam_ema_f32: ema_mode must be 0, 1 or 2 (got %d)", ema_mode);
+    hipLaunchKernelGGL(opt_radam_kernel, dim3((unsigned)nchunk), dim3(256), 0, (hipStream_t)stream, chunks, tensors, steps, rec, lr,
+                       beta1, beta2, eps, ema_mode, ema_decay, zero_grad, skip_nonfinite);
+    FD_LAUNCH_OK("fd_opt_radam_ema_f32");
     return FD_OK;
 }

@@ -9,6 +9,8 @@
     p_losses_fn(model_fn, imgs, t, schedule, ...)  p_losses on a free function model_fn(x_in, [time0, time1]) -> list of (B, 1, H, W)
     p_losses(self, imgs, t, ...)                   the same on the reference's attribute names
     ClipAdamEMA(params, ema_params, ...)           clip_grad_norm_ + torch.optim.Adam + zero_grad + the EMA update: three launches
+    ClipRAdamEMA(params, ema_params, ...)          the same around torch.optim.RAdam's rule: the reference's optimiser of two U-Nets,
+                                                   one object over the parameters of both (joint clip, both updates, one EMA)
     train_step(diffusion_or_fn, opt, batch, ...)   p_losses -> backward per loss -> opt.step()
     StoreBatch(store, indices, codes)              a micro-batch that stays in a data.DeviceSliceStore: accepted wherever
                                                    [x_start, x_input] is; q_sample then gathers, flips / rotates and diffuses it in
@@ -36,7 +38,9 @@ reason: no test reads a file written by either.
 
 chunk_table, ema_schedule, adam_state_unpack, adam_state_pack, train_batch_indices, train_t_and_seeds, train_augment,
 augment_source_index, train_crop, crop_source_index, checkpoint_pack, checkpoint_unpack, check_bands, val_draws and val_summary are
-pure host code.
+pure host code, and so are radam_scalars, optimizer_kind, checkpoint_pack2 and checkpoint_unpack2: the checkpoint of two U-Nets has
+the reference's six keys (CHECKPOINT_KEYS_2), 'opt0' and 'opt1' in torch.optim.RAdam's layout, which the tests load into
+torch.optim.RAdam itself.
 """
 import numpy as np
 import torch
@@ -48,7 +52,8 @@ from .data import check_batch, crop_pads, crop_pair, upload_table, window_rows
 __all__ = ["q_sample", "residual_loss", "p_losses_fn", "p_losses", "ClipAdamEMA", "train_step", "chunk_table", "ema_schedule",
            "adam_state_unpack", "adam_state_pack", "train_batch_indices", "train_t_and_seeds", "train_augment", "augment_source_index",
            "train_crop", "crop_source_index", "StoreBatch", "checkpoint_pack", "checkpoint_unpack", "CHUNK", "check_bands", "val_draws",
-           "val_items", "val_summary"]
+           "val_items", "val_summary", "ClipRAdamEMA", "radam_scalars", "optimizer_kind", "CHECKPOINT_KEYS", "CHECKPOINT_KEYS_2",
+           "checkpoint_pack2", "checkpoint_unpack2"]
 
 CHUNK = 4096                      # elements of a parameter per workgroup (fd_opt_chunk_elems())
 _LOSS_TYPES = {"l1": 1, "l2": 2}
@@ -99,10 +104,55 @@ def adam_state_unpack(sd, n):
 
 def adam_state_pack(steps, exp_avg, exp_avg_sq, group):
     """the inverse: torch.optim.Adam's layout, state[i] = {step, exp_avg, exp_avg_sq} for every parameter that has taken a step;
-    group: the hyperparameters of the one param group (its "params" is replaced)"""
+    group: the hyperparameters of the one param group (its "params" is replaced).  torch.optim.RAdam keeps the same three
+    entries per parameter: with its group this is RAdam's layout."""
     state = {i: {"step": torch.tensor(float(s)), "exp_avg": exp_avg[i], "exp_avg_sq": exp_avg_sq[i]}
              for i, s in enumerate(steps) if s > 0}
     return {"state": state, "param_groups": [dict(group, params=list(range(len(steps))))]}
+
+
+def radam_scalars(step, lr, beta1, beta2):
+    """(rectified, step_size, factor) of torch.optim.RAdam (_single_tensor_radam, not capturable) for a tensor at step count
+    `step` >= 1, in Python floats (doubles), as lane 0 of a workgroup of fd_opt_radam_ema_f32 computes them:
+
+        bc1 = 1 - beta1^s, bc2 = 1 - beta2^s, rho_inf = 2 / (1 - beta2) - 1, rho = rho_inf - 2 s beta2^s / bc2
+        step_size = lr / bc1
+        rho > 5:  factor = sqrt((rho - 4)(rho - 2) rho_inf / ((rho_inf - 4)(rho_inf - 2) rho)) sqrt(bc2),
+                  p -= step_size factor m / (sqrt(v) + eps)          (eps joins sqrt(v) uncorrected: not Adam's denominator)
+        else:     factor = 1,  p -= step_size m
+
+    The kernel rounds step_size * factor to float once.  rho <= rho_inf, so with rho_inf <= 5 (beta2 <= 2 / 3) no step is
+    rectified and nothing is divided by rho_inf - 4."""
+    s = int(step)
+    if s < 1 or not 0 <= beta1 < 1 or not 0 <= beta2 < 1:
+        raise RuntimeError(f"radam_scalars: invalid arguments step={step} beta1={beta1} beta2={beta2} (step >= 1, betas in [0, 1))")
+    b2s = float(beta2) ** s
+    bc1, bc2 = 1.0 - float(beta1) ** s, 1.0 - b2s
+    rho_inf = 2.0 / (1.0 - float(beta2)) - 1.0
+    rho = rho_inf - 2.0 * s * b2s / bc2
+    if rho > 5.0:
+        r = ((rho - 4.0) * (rho - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho)) ** 0.5
+        return True, float(lr) / bc1, r * bc2 ** 0.5
+    return False, float(lr) / bc1, 1.0
+
+
+def optimizer_kind(group):
+    """'adam' or 'radam' for a param group of a state dict, None for neither: torch.optim.Adam's groups carry amsgrad,
+    torch.optim.RAdam's decoupled_weight_decay and no amsgrad"""
+    if "amsgrad" in group:
+        return "adam"
+    return "radam" if "decoupled_weight_decay" in group else None
+
+
+def _check_kind(fn, entry, sd, want):
+    """`sd` (the state dict under `entry`) was written by the optimiser `want` ('adam', 'radam'; None: not checked)"""
+    if want is None:
+        return
+    got = [optimizer_kind(g) for g in sd["param_groups"]]
+    if any(k != want for k in got):
+        names = {"adam": "torch.optim.Adam (ClipAdamEMA)", "radam": "torch.optim.RAdam (ClipRAdamEMA)", None: "an unknown optimiser"}
+        raise RuntimeError(f"{fn}: '{entry}' was written by {names[got[0]]}, this run uses {names[want]}: Adam and RAdam state do "
+                           f"not load into each other")
 
 
 # What Trainer.train draws is a pure function of (seed, step, micro-batch): no generator state lives in a checkpoint, and a run resumed
@@ -269,16 +319,82 @@ def checkpoint_pack(step, model_sd, ema_model_sd, opt_sd, trainable_index, n_par
     return {"step": int(step), "model": model_sd, "opt0": adam_state_pack(S, M, V, group), "ema": ema, "scaler": None}
 
 
-def checkpoint_unpack(data, trainable_index, n_params):
-    """the inverse: (step, model_sd, ema_model_sd, opt_sd) with opt_sd as ClipAdamEMA.load_state_dict takes it"""
+def checkpoint_unpack(data, trainable_index, n_params, optimizer=None):
+    """the inverse: (step, model_sd, ema_model_sd, opt_sd) with opt_sd as ClipAdamEMA.load_state_dict takes it.  optimizer
+    ('adam' or 'radam'; None: not checked): the optimiser 'opt0' must have been written by (optimizer_kind)."""
     if set(data) != set(CHECKPOINT_KEYS):
         raise RuntimeError(f"checkpoint_unpack: expected the keys {CHECKPOINT_KEYS} (got {sorted(data)})")
+    _check_kind("checkpoint_unpack", "opt0", data["opt0"], optimizer)
     S, M, V = adam_state_unpack(data["opt0"], n_params)
     frozen = set(range(n_params)) - set(trainable_index)
     if any(S[i] for i in frozen):
         raise RuntimeError("checkpoint_unpack: 'opt0' holds state for a frozen parameter")
     group = {k: val for k, val in data["opt0"]["param_groups"][0].items() if k != "params"}
     opt_sd = adam_state_pack([S[i] for i in trainable_index], [M[i] for i in trainable_index], [V[i] for i in trainable_index], group)
+    ema = data["ema"]
+    opt_sd["ema_step"], opt_sd["ema_copied"] = int(ema["step"].reshape(-1)[0]), bool(ema["initted"].reshape(-1)[0])
+    ema_model_sd = {k[len("ema_model."):]: val for k, val in ema.items() if k.startswith("ema_model.")}
+    return int(data["step"]), data["model"], ema_model_sd, opt_sd
+
+
+CHECKPOINT_KEYS_2 = ("step", "model", "opt0", "opt1", "ema", "scaler")
+
+
+def _unet_places(fn, trainable_index, unet_index):
+    """(u, k) per trainable parameter: it is parameter k of U-Net u"""
+    if len(unet_index) != 2:
+        raise RuntimeError(f"{fn}: unet_index must hold the places of unet0's and of unet1's parameters (got {len(unet_index)} lists)")
+    where = {}
+    for u, places in enumerate(unet_index):
+        for k, i in enumerate(places):
+            if i in where:
+                raise RuntimeError(f"{fn}: parameter {i} is listed twice in unet_index")
+            where[i] = (u, k)
+    missing = [i for i in trainable_index if i not in where]
+    if missing:
+        raise RuntimeError(f"{fn}: trainable parameter {missing[0]} belongs to neither U-Net")
+    return [where[i] for i in trainable_index]
+
+
+def checkpoint_pack2(step, model_sd, ema_model_sd, opt_sd, trainable_index, unet_index):
+    """The dictionary of Trainer.save for two U-Nets (src/DADiff.py:1637-1645): CHECKPOINT_KEYS_2.  opt_sd is
+    ClipRAdamEMA.state_dict() of the ONE optimiser over the trainable parameters of both U-Nets; trainable_index[j] is the place
+    of its parameter j in diffusion.parameters(), unet_index = (the places of unet0.parameters(), those of unet1.parameters()),
+    each in that U-Net's own order.  'opt0' has torch.optim.RAdam's layout over unet0.parameters(), 'opt1' over
+    unet1.parameters(), as the reference's two optimisers write them; frozen parameters and any that never took a step carry no
+    state.  'ema' as checkpoint_pack writes it: the reference keeps one EMA of the whole model."""
+    fn = "checkpoint_pack2"
+    _check_kind(fn, "opt_sd", opt_sd, "radam")
+    steps, m, v = adam_state_unpack(opt_sd, len(trainable_index))
+    sizes = [len(places) for places in unet_index]
+    S, M, V = ([[0] * n for n in sizes], [[None] * n for n in sizes], [[None] * n for n in sizes])
+    for j, (u, k) in enumerate(_unet_places(fn, trainable_index, unet_index)):
+        S[u][k], M[u][k], V[u][k] = steps[j], m[j], v[j]
+    group = {k: val for k, val in opt_sd["param_groups"][0].items() if k != "params"}
+    ema = {"ema_model." + k: val for k, val in ema_model_sd.items()}
+    ema["initted"] = torch.tensor([bool(opt_sd.get("ema_copied", False))])
+    ema["step"] = torch.tensor([int(opt_sd.get("ema_step", 0))])
+    return {"step": int(step), "model": model_sd, "opt0": adam_state_pack(S[0], M[0], V[0], group),
+            "opt1": adam_state_pack(S[1], M[1], V[1], group), "ema": ema, "scaler": None}
+
+
+def checkpoint_unpack2(data, trainable_index, unet_index):
+    """the inverse: (step, model_sd, ema_model_sd, opt_sd) with opt_sd as ClipRAdamEMA.load_state_dict takes it, over the
+    trainable parameters of both U-Nets in trainable_index's order.  The hyperparameters are 'opt0''s."""
+    fn = "checkpoint_unpack2"
+    if set(data) != set(CHECKPOINT_KEYS_2):
+        raise RuntimeError(f"{fn}: expected the keys {CHECKPOINT_KEYS_2} (got {sorted(data)})")
+    places = _unet_places(fn, trainable_index, unet_index)
+    S, M, V = [], [], []
+    for u, entry in enumerate(("opt0", "opt1")):
+        _check_kind(fn, entry, data[entry], "radam")
+        s, m, v = adam_state_unpack(data[entry], len(unet_index[u]))
+        S.append(s), M.append(m), V.append(v)
+    live = set(places)
+    if any(S[u][k] for u in range(2) for k in range(len(S[u])) if (u, k) not in live):
+        raise RuntimeError(f"{fn}: 'opt0' or 'opt1' holds state for a frozen parameter")
+    group = {k: val for k, val in data["opt0"]["param_groups"][0].items() if k != "params"}
+    opt_sd = adam_state_pack([S[u][k] for u, k in places], [M[u][k] for u, k in places], [V[u][k] for u, k in places], group)
     ema = data["ema"]
     opt_sd["ema_step"], opt_sd["ema_copied"] = int(ema["step"].reshape(-1)[0]), bool(ema["initted"].reshape(-1)[0])
     ema_model_sd = {k[len("ema_model."):]: val for k, val in ema.items() if k.startswith("ema_model.")}
@@ -659,10 +775,12 @@ class ClipAdamEMA:
     state_dict() / load_state_dict() use torch.optim.Adam's layout (the reference's `opt0` checkpoint entry), plus the EMA counter
     under "ema_step" / "ema_copied"."""
 
+    _update_entry = "fd_opt_adam_ema_f32"        # the third launch of step(): the update rule (ClipRAdamEMA has RAdam's)
+
     def __init__(self, params, ema_params=None, lr=1e-4, betas=(0.9, 0.99), eps=1e-8, max_norm=1.0, ema_beta=0.995,
                  ema_update_every=10, ema_update_after_step=100, ema_inv_gamma=1.0, ema_power=2 / 3, ema_min_value=0.0,
                  skip_nonfinite=False):
-        fn = "ClipAdamEMA"
+        fn = type(self).__name__
         if isinstance(params, torch.Tensor):
             raise RuntimeError(f"{fn}: params must be an iterable of tensors (got one tensor)")
         params = list(params)
@@ -712,7 +830,7 @@ class ClipAdamEMA:
         self._host[:, 3] = [v.data_ptr() for v in self.exp_avg_sq]
 
     def _upload_table(self):
-        fn, h = "ClipAdamEMA.step", self._host
+        fn, h = type(self).__name__ + ".step", self._host
         grads = [p.grad for p in self.params]
         for i, (p, g) in enumerate(zip(self.params, grads)):
             if g is None:
@@ -741,7 +859,8 @@ class ClipAdamEMA:
         """One update on the current stream.  ema_mode / ema_decay override the schedule for this call (0: leave the EMA alone, 1: copy,
         2: decayed update).  Returns the device record (4 floats): total_norm, coef, nonfinite, 0."""
         if ema_mode is not None and (ema_mode not in (0, 1, 2) or (ema_mode == 2 and ema_decay is None)):
-            raise RuntimeError(f"ClipAdamEMA.step: ema_mode must be 0, 1 or 2, with an ema_decay for 2 (got {ema_mode}, {ema_decay})")
+            raise RuntimeError(f"{type(self).__name__}.step: ema_mode must be 0, 1 or 2, with an ema_decay for 2 (got {ema_mode}, "
+                               f"{ema_decay})")
         with torch.cuda.device(self.device):
             self._upload_table()
             s0 = self.ema_step
@@ -757,7 +876,7 @@ class ClipAdamEMA:
             L.call("fd_opt_sumsq_f32", ptr(self._chunks), ptr(self._table), ptr(self._part), self.nchunk, st)
             L.call("fd_opt_clip_coef", ptr(self._part), self.nchunk, ptr(self._table), ptr(self._steps), self.nt,
                    -1.0 if self.max_norm is None else float(self.max_norm), skip, ptr(self._rec), st)
-            L.call("fd_opt_adam_ema_f32", ptr(self._chunks), ptr(self._table), ptr(self._steps), ptr(self._rec), self.nchunk, self.lr,
+            L.call(self._update_entry, ptr(self._chunks), ptr(self._table), ptr(self._steps), ptr(self._rec), self.nchunk, self.lr,
                    self.betas[0], self.betas[1], self.eps, mode, decay, int(bool(zero_grad)), skip, st)
         return self._rec
 
@@ -785,7 +904,7 @@ class ClipAdamEMA:
         for i, p in enumerate(self.params):
             for name, t in (("exp_avg", m[i]), ("exp_avg_sq", v[i])):
                 if t is not None and (not isinstance(t, torch.Tensor) or t.shape != p.shape):
-                    raise RuntimeError(f"ClipAdamEMA.load_state_dict: inconsistent shapes: {name} of parameter {i} is "
+                    raise RuntimeError(f"{type(self).__name__}.load_state_dict: inconsistent shapes: {name} of parameter {i} is "
                                        f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}, the parameter "
                                        f"{tuple(p.shape)}")
         with torch.no_grad():
@@ -800,6 +919,38 @@ class ClipAdamEMA:
         self.lr, self.betas, self.eps = float(group.get("lr", self.lr)), tuple(map(float, group.get("betas", self.betas))), \
             float(group.get("eps", self.eps))
         self.ema_step, self.ema_copied = int(sd.get("ema_step", self.ema_step)), bool(sd.get("ema_copied", self.ema_copied))
+
+
+class ClipRAdamEMA(ClipAdamEMA):
+    """ClipAdamEMA with torch.optim.RAdam(params, lr, betas, eps, weight_decay=0)'s update in Adam's place (fd_opt_radam_ema_f32;
+    radam_scalars has the rule): what the reference optimises two U-Nets with (src/DADiff.py:1598-1602), after one
+    clip_grad_norm_ over both and before one EMA of the whole model.  One object over list(unet0.parameters()) +
+    list(unet1.parameters()) is therefore the reference's joint clip, its two optimisers and its EMA, in the same three launches
+    per step(): every tensor has its own step count and its own branch of the rule.  The constructor's arguments are
+    ClipAdamEMA's; betas default to RAdam's (0.9, 0.999), which is what the reference runs with -- not its adam_betas.  There is
+    no weight decay.  state_dict() / load_state_dict() use torch.optim.RAdam's layout."""
+
+    _update_entry = "fd_opt_radam_ema_f32"
+
+    def __init__(self, params, ema_params=None, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0, ema_beta=0.995,
+                 ema_update_every=10, ema_update_after_step=100, ema_inv_gamma=1.0, ema_power=2 / 3, ema_min_value=0.0,
+                 skip_nonfinite=False):
+        super().__init__(params, ema_params, lr, betas, eps, max_norm, ema_beta, ema_update_every, ema_update_after_step,
+                         ema_inv_gamma, ema_power, ema_min_value, skip_nonfinite)
+
+    def _group(self):
+        return torch.optim.RAdam([torch.zeros(1)], lr=self.lr, betas=self.betas, eps=self.eps,
+                                 weight_decay=0.0).state_dict()["param_groups"][0]
+
+    def load_state_dict(self, sd):
+        fn = "ClipRAdamEMA.load_state_dict"
+        for g in sd["param_groups"]:
+            if optimizer_kind(g) == "adam":
+                raise RuntimeError(f"{fn}: the state was written by torch.optim.Adam (ClipAdamEMA), this is torch.optim.RAdam "
+                                   f"(ClipRAdamEMA): Adam and RAdam state do not load into each other")
+            if g.get("weight_decay", 0) != 0:
+                raise RuntimeError(f"{fn}: weight_decay={g['weight_decay']} is not supported (the reference runs RAdam with 0)")
+        super().load_state_dict(sd)
 
 
 # ---- the loop body -----------------------------------------------------------------------------------------------------------------

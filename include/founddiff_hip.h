@@ -730,7 +730,11 @@ int fd_axpy_f32(const float *x, const float *noise, float s, float *out, int64_t
  *   fd_opt_clip_coef     rec[4] = total_norm, coef = min(1, max_norm / (total_norm + 1e-6)) (1 if max_norm < 0), nonfinite, 0;
  *                        steps[i] += 1 for every tensor with a gradient, unless skip_nonfinite and nonfinite
  *   fd_opt_adam_ema_f32  g' = coef g; Adam with the bias corrections of steps[i]; ema_mode 0: none, 1: ema = p,
- *                        2: ema -= (1 - ema_decay)(ema - p); zero_grad: g = 0; writes nothing if skip_nonfinite and nonfinite */
+ *                        2: ema -= (1 - ema_decay)(ema - p); zero_grad: g = 0; writes nothing if skip_nonfinite and nonfinite
+ *   fd_opt_radam_ema_f32 the same with torch.optim.RAdam's rule in Adam's place: with s = steps[i], bc1 = 1 - beta1^s,
+ *                        bc2 = 1 - beta2^s, rho_inf = 2 / (1 - beta2) - 1 and rho = rho_inf - 2 s beta2^s / bc2, a tensor with
+ *                        rho > 5 takes p -= lr / bc1 r sqrt(bc2) m / (sqrt(v) + eps), r = sqrt((rho - 4)(rho - 2) rho_inf /
+ *                        ((rho_inf - 4)(rho_inf - 2) rho)), every other one p -= lr / bc1 m; no weight decay */
 int fd_res_qsample_f32(const float *x_start, const float *x_input, const int64_t *t, const float *alphas_cumsum,
                        const float *betas_cumsum, int T, const float *noise, const int64_t *seeds, int noise_step,
                        int normalize, float *x_in, float *x_res, float *noise_out, float *times, int B, int64_t npix,
@@ -747,6 +751,9 @@ int fd_opt_clip_coef(const float *part, int nchunk, const int64_t *tensors, int 
 int fd_opt_adam_ema_f32(const int64_t *chunks, const int64_t *tensors, const int *steps, const float *rec, int nchunk,
                         double lr, double beta1, double beta2, double eps, int ema_mode, double ema_decay, int zero_grad,
                         int skip_nonfinite, void *stream);
+int fd_opt_radam_ema_f32(const int64_t *chunks, const int64_t *tensors, const int *steps, const float *rec, int nchunk,
+                         double lr, double beta1, double beta2, double eps, int ema_mode, double ema_decay, int zero_grad,
+                         int skip_nonfinite, void *stream);
 
 /* ---- what a held-out evaluation reads off a model output (fd_validate.hip) -------------------------------------
  * fd_val_items_f32: items [B][2], from one pass over pred, target (and x_input, x_start) [B][npix] and two small sums, without
