@@ -177,6 +177,9 @@ SIGNATURES = {
     "fd_opt_radam_ema_f32": (i32, [vp, vp, vp, vp, i32, f64, f64, f64, f64, i32, f64, i32, i32, vp]),
     "fd_val_items_ws_floats": (i64, [i32, i64]),
     "fd_val_items_f32": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, i64, vp]),
+    "fd_ensemble_nblk": (i32, [i64]),
+    "fd_rows_repeat_f32": (i32, [vp, vp, i32, i32, i64, vp]),
+    "fd_ensemble_stats_f32": (i32, [vp, vp, vp, vp, vp, i32, i32, i64, vp]),
     "fd_store_gather_f32": (i32, [vp, vp, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "fd_res_qsample_store_f32": (i32, [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32,
                                        i32, vp]),

@@ -826,6 +826,20 @@ class DAEngine:
         self.local_all.copy_(other.local_all)
         self.dose_emb, self.ctx_emb = other.dose_emb, other.ctx_emb
 
+    def load_condition(self, prompt_emb, local_all):
+        """Take given conditioning rows ((B, time_dim), (B, loc_total), fp32: another engine's encode_condition, row for row) into
+        this engine's own buffers -- the addresses a captured loop graph of this batch size reads -- instead of running the tower
+        (ResidualDiffusion.sample_ensemble: the replicas of a slice share its rows)."""
+        B = prompt_emb.shape[0]
+        if tuple(prompt_emb.shape) != (B, self.time_dim) or tuple(local_all.shape) != (B, self.loc_total):
+            raise ValueError(f"load_condition: want ({B}, {self.time_dim}) and ({B}, {self.loc_total}), got "
+                             f"{tuple(prompt_emb.shape)} and {tuple(local_all.shape)}")
+        self.prompt_emb = self._b("prompt_emb", (B, self.time_dim), torch.float32)
+        self.local_all = self._b("local_all", (B, self.loc_total), torch.float32)
+        self.prompt_emb.copy_(prompt_emb)
+        self.local_all.copy_(local_all)
+        self.dose_emb = self.ctx_emb = None          # the encoder's own outputs belong to the engine that ran it
+
     # ------------------------------------------------------------------ one denoiser forward
     def time_cond(self, time):
         """time (B,) fp32 device -> adaLN vectors of all blocks (src/DADiff.py:703,709,484)."""

@@ -22,6 +22,25 @@ def compute_metrics(pred, target):
     return out
 
 
+def ensemble_stats(samples):
+    """samples (B,K,...) fp32 device tensor, K realisations per slice -> (mean, std) of shape (B,...) and spread (B,): the per-pixel
+    mean and two-pass sample standard deviation over k (0 for K = 1) and sqrt(mean over pixels of std^2), fd_ensemble_stats_f32."""
+    samples = samples.contiguous().float()
+    B, K = samples.shape[:2]
+    n = samples[0, 0].numel()
+    nblk = L.lib().fd_ensemble_nblk(n)
+    if nblk <= 0:
+        raise L.FoundDiffHipError(f"ensemble_stats: unsupported slice size {n}")
+    mean = torch.empty((B,) + tuple(samples.shape[2:]), device=samples.device)
+    std = torch.empty_like(mean)
+    ws = torch.empty(B * nblk, device=samples.device)
+    spread = torch.empty(B, device=samples.device)
+    stream = C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream)
+    L.call("fd_ensemble_stats_f32", samples.data_ptr(), mean.data_ptr(), std.data_ptr(), ws.data_ptr(), spread.data_ptr(), B, K, n,
+           stream)
+    return mean, std, spread
+
+
 def compute_psnr(input, target, max_val=1.0):
     return compute_metrics(input, target)[:, 0].mean()
 

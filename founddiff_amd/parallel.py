@@ -39,15 +39,28 @@ def gather_volume(local, world, n_total=None):
     return vol
 
 
-def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampler_kwargs=None):
+def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampler_kwargs=None, n_samples=1):
     """Denoise a whole volume ldct (N,1,H,W in [0,1], same tensor on every rank) with `diffusion`
     (a founddiff_amd.DADiff.ResidualDiffusion living on this rank's device).  x_T noise is keyed
     by the GLOBAL slice index, and so is the ancestral sampler's per-step noise (`slice_seeds`:
     fd_sched.hip's counter-based stream), so the result is invariant to `world` for both samplers.
-    Returns the (N,1,H,W) volume on every rank."""
+    Returns the (N,1,H,W) volume on every rank.
+    `n_samples` > 1: every slice is an ensemble of that many realisations (sample_ensemble) whose replica seeds derive from
+    `noise_seed` + the GLOBAL slice index; returns (mean, std), two (N,1,H,W) volumes, on every rank.  `sampler_kwargs` are
+    sample()'s and do not reach it."""
     n = ldct.shape[0]
     lo, hi = shard_range(n, world, rank)
     dev = next(diffusion.parameters()).device
+    if int(n_samples) > 1:
+        means, stds = [], []
+        for s in range(lo, hi, batch):
+            e = min(s + batch, hi)
+            ens = diffusion.sample_ensemble([ldct[s:e].to(dev)], int(n_samples),
+                                            slice_seeds=torch.arange(s, e, dtype=torch.int64) + int(noise_seed))
+            means.append(ens.mean)
+            stds.append(ens.std)
+        empty = ldct.new_zeros((0,) + tuple(ldct.shape[1:])).to(dev)
+        return tuple(gather_volume(torch.cat(v, 0) if v else empty, world, n) for v in (means, stds))
     outs = []
     for s in range(lo, hi, batch):
         e = min(s + batch, hi)

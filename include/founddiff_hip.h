@@ -767,6 +767,19 @@ int64_t fd_val_items_ws_floats(int B, int64_t npix);
 int fd_val_items_f32(const float *pred, const float *target, const float *x_input, const float *x_start, int loss_type,
                      float *items, float *ws, int B, int64_t npix, void *stream);
 
+/* ---- an ensemble of K keyed realisations per slice (fd_ensemble.hip; ResidualDiffusion.sample_ensemble) --------
+ * fp32, the same in both builds of the library.  Deterministic, no float atomics.
+ * fd_rows_repeat_f32: dst [B K][n], dst[b K + k] = src[b] (src [B][n]): a slice's input plane or conditioning row, once per
+ *   replica.  16-byte accesses when n % 4 == 0 and both pointers are 16-byte aligned, scalar otherwise.
+ * fd_ensemble_stats_f32: samples [B][K][n] -> mean [B][n] = (the fp32 sum in k order) / K; std [B][n] = the two-pass sample
+ *   standard deviation sqrt(sum_k (x - mean)^2 / (K - 1)) in k order, exactly 0 for K = 1; spread [B] = sqrt(mean_i std^2).
+ *   A slice's rows depend on K and n alone, not on B or on the other slices; the 16-byte form (n % 4 == 0, samples, mean and
+ *   std 16-byte aligned) and the scalar form give the same bits.  ws: B * fd_ensemble_nblk(n) floats (0: unsupported n). */
+int fd_ensemble_nblk(int64_t n);
+int fd_rows_repeat_f32(const float *src, float *dst, int B, int K, int64_t n, void *stream);
+int fd_ensemble_stats_f32(const float *samples, float *mean, float *std, float *ws, float *spread, int B, int K, int64_t n,
+                          void *stream);
+
 /* ---- a training batch from a slice store on the device (fd_train_data.hip; data/pdf_dataset.py:521-545) -------
  * nd [n_nd][H][W], ld [n_ld][H][W] fp32 in [0, 1].  Item b of the batch is the pair nd[nd_slot[b]], ld[ld_slot[b]] (int64 [B],
  * clamped to the store), both under the transform codes[b] (int64 [B], low 4 bits; a null codes is all 0):
