@@ -31,6 +31,7 @@ from . import diffusion_train as dt
 from .engine import DAEngine, _p
 from .ensemble import ensemble_passes, ensemble_seeds
 from .metrics import ensemble_stats
+from .tiling import tile_pair, tile_passes, tile_plan, tile_seeds, tile_weights
 
 ModelResPrediction = namedtuple("ModelResPrediction", ["pred_res", "pred_noise", "pred_x_start"])
 # sample_ensemble: mean, std (B,1,H,W) in [0, 1] units, spread (B,), samples (B,K,1,H,W) or None
@@ -256,6 +257,25 @@ class Unet(_ParamTree):
                 raise L.FoundDiffHipError("founddiff_amd runs on MI355X only: move the model to a ROCm device "
                                           "(`.to('cuda')`); there is no CPU path")
             eng = self._engine[key] = DAEngine(self.state_dict(), "", dev, prec, low_latency=self.low_latency)
+        return eng
+
+    def tower_engine(self, precision=None):
+        """A DAEngine(tower_only=True) of this UNet's frozen DA-CLIP encoder in the kernel mode `precision` (default: the sampling
+        precision), kept beside the engines of engine(): sample_tiled(condition="slice") runs the tower on whole slices here, so
+        that the engines of the tiles keep their tile-sized buffers and their captured graphs.  Same kernels and mode as
+        engine().encode_dose, hence the same bits."""
+        prec = precision or self.kernel_precision
+        if self._engine is None:
+            self._engine = {}
+        key = (prec, "tower") if not self.low_latency else (prec, "tower", "ll")
+        eng = self._engine.get(key)
+        if eng is None:
+            dev = next(self.parameters()).device
+            if dev.type != "cuda":
+                raise L.FoundDiffHipError("founddiff_amd runs on MI355X only: move the model to a ROCm device "
+                                          "(`.to('cuda')`); there is no CPU path")
+            tower = {k: v for k, v in self.state_dict().items() if k.startswith("dose_encoder.")}
+            eng = self._engine[key] = DAEngine(tower, "", dev, prec, low_latency=self.low_latency, tower_only=True)
         return eng
 
     @torch.no_grad()
@@ -1114,6 +1134,131 @@ class ResidualDiffusion(nn.Module):
             flat[sl].copy_(out[-1])
         return samples
 
+    # ---- a slice as overlapping tiles
+    def _tile_plan(self, H, W, th, tw, oy, ox, dev):
+        """The plan of tiling.py on the device, uploaded once per geometry: (ys, xs int32, wy, wx float32, my, mx, xs % 4 == 0)"""
+        cache = self.__dict__.setdefault("_tile_plans", {})
+        key = (H, W, th, tw, oy, ox, str(dev))
+        plan = cache.get(key)
+        if plan is None:
+            ys, xs = tile_plan(H, th, oy), tile_plan(W, tw, ox)
+            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a.astype(dt))).to(dev)
+            plan = cache[key] = (up(ys, np.int32), up(xs, np.int32), up(tile_weights(ys, H, th), np.float32),
+                                 up(tile_weights(xs, W, tw), np.float32), len(ys), len(xs), int(bool((xs % 4 == 0).all())))
+        return plan
+
+    @torch.no_grad()
+    def sample_tiled(self, x_input, tile, overlap=0, slice_seeds=None, condition="tile"):
+        """x_input = [ldct (B,1,H,W) in [0,1]] sampled as overlapping tiles of `tile` = th or (th, tw) pixels, `overlap` (an int or
+        a pair, at most tile // 2) pixels apart from full tiles (tiling.tile_plan: the last tile of an axis is shifted back to end
+        at the border), and blended on the device: what sample(last=True) returns, [x_T image, final image], both (B,1,H,W).  A
+        model trained on crops meets the operator it was trained under, an image larger than a checkpoint's size can be denoised,
+        and the engines' workspaces are those of a tile.
+        x_T is ONE keyed field per slice, fd_keyed_normal(slice seed, X_T_STEP) over the whole plane, and a tile's x_T noise is
+        its window of that field: overlapping tiles start from the same noise in their common pixels, on both samplers.  The first
+        returned image is x_input + sqrt(sum_scale) * field on the whole slice.  Tile (iy, ix) of slice b is an ordinary row of
+        sample() under the seed tiling.tile_seeds(slice_seeds, my * mx)[b, iy * mx + ix] (tile 0 keeps the slice's seed: a one-tile
+        plan is sample() of the slice under that x_T); the rows run slice-major in passes of at most streams x max_sub_batch
+        through the paths of sample().  The ancestral sampler's STEP noise is the keyed stream of the tile's own seed (the
+        graph-captured loop), so overlapping tiles see different step noise in their common pixels and the blend averages them.
+        The final image is the weighted mean of the tiles' final images, weights tiling.tile_weights (fd_tiles_blend_f32): a
+        pixel under one tile is that tile's value bit for bit.  Nothing returned depends on B or on the cut into passes.
+        condition="tile": the DA-CLIP tower runs on every tile, which is what crop training saw.  "slice": it runs once per slice
+        on the whole slice (Unet.tower_engine) and every tile of the slice takes those conditioning rows.
+        Not built: blending inside the loop (per-step fusion of the tiles), tiled ensembles, tiles larger than the slice,
+        last=False, input_condition=True."""
+        fn = "sample_tiled"
+        if self.input_condition:
+            raise RuntimeError(f"{fn}: input_condition=True is not built (one input plane per slice)")
+        if condition not in ("tile", "slice"):
+            raise RuntimeError(f"{fn}: condition must be 'tile' or 'slice' (got {condition!r})")
+        (th, tw), (oy, ox) = tile_pair(fn, tile, "tile"), tile_pair(fn, overlap, "overlap")
+        x01 = list(x_input)[0]
+        if not torch.is_tensor(x01) or x01.dim() != 4 or x01.shape[1] != 1:
+            raise RuntimeError(f"{fn}: x_input must be [ldct (B,1,H,W)]")
+        B, _, H, W = x01.shape
+        div = 2 ** (len(self.model.unet0.dim_mults) - 1)
+        if th < 1 or tw < 1 or th % div or tw % div:
+            raise RuntimeError(f"{fn}: tile {th} x {tw} must be positive multiples of {div} (the U-Net has "
+                               f"{len(self.model.unet0.dim_mults)} levels)")
+        if th > H or tw > W:
+            raise RuntimeError(f"{fn}: tile {th} x {tw} is larger than the slice {H} x {W} (padded tiles are not built)")
+        if not (0 <= oy <= th // 2 and 0 <= ox <= tw // 2):
+            raise RuntimeError(f"{fn}: overlap {oy} x {ox} must lie in [0, tile // 2] = [0, {th // 2}] x [0, {tw // 2}]")
+        x01 = x01.contiguous().float()
+        seeds = self._slice_seeds(slice_seeds, B, "cpu")
+        ys, xs, wy, wx, my, mx, x4 = self._tile_plan(H, W, th, tw, oy, ox, x01.device)
+        if B * my * mx > 65535:
+            raise RuntimeError(f"{fn}: {B} slices x {my} x {mx} tiles are more than 65535 rows: sample fewer slices per call")
+        rows = torch.from_numpy(tile_seeds(seeds.numpy(), my * mx).reshape(-1)).to(x01.device)
+        plan = (ys, xs, wy, wx, my, mx, x4, th, tw)
+        s = _stream(x01)
+        field = self._keyed_noise(seeds.to(x01.device), self.X_T_STEP, tuple(x01.shape))
+        x_T = torch.empty_like(x01)
+        L.call("fd_axpy_f32", _p(normalize_to_neg_one_to_one(x01)), _p(field), math.sqrt(self.sum_scale), _p(x_T), x_T.numel(), s)
+        tiles = self._tile_rows(x01, field, rows, plan, condition)
+        if self.model.unet0.kernel_precision == "fp16" and self.check_fp16_range and not bool(torch.isfinite(tiles).all()):
+            if self.model.unet0.precision != "auto":              # sample()'s rule, applied to the tiles
+                raise L.FoundDiffHipError(
+                    "precision='fp16': a sampled image is not finite -- an activation of this checkpoint left IEEE binary16's "
+                    "range (65504).  Use precision='bf16' (same speed, fp32's range, 8 significand bits), 'auto' or 'fp32s'.")
+            import warnings
+            warnings.warn("founddiff_amd: precision='auto': this checkpoint's activations leave IEEE binary16's range; "
+                          "this and every later sample() of the model run on the bfloat16 kernels")
+            for u in (getattr(self.model, "unet0", None), getattr(self.model, "unet1", None)):
+                if u is not None:
+                    u._auto_bf16 = True
+            tiles = self._tile_rows(x01, field, rows, plan, condition)
+        out = torch.empty_like(x01)
+        L.call("fd_tiles_blend_f32", _p(tiles), _p(wy), _p(wx), _p(ys), _p(xs), _p(out), B, H, W, th, tw, my, mx, x4, s)
+        return [unnormalize_to_zero_to_one(x_T), out]
+
+    def _tile_gather(self, src, plan):
+        ys, xs, _, _, my, mx, x4, th, tw = plan
+        B, _, H, W = src.shape
+        dst = torch.empty((B * my * mx, 1, th, tw), device=src.device, dtype=torch.float32)
+        L.call("fd_tiles_gather_f32", _p(src), _p(dst), _p(ys), _p(xs), B, H, W, th, tw, my, mx, x4, _stream(src))
+        return dst
+
+    def _tile_rows(self, x01, field, seeds, plan, condition):
+        """The B my mx final tile images (R,1,th,tw) of sample_tiled, in [0, 1] units; seeds (R,) int64 on the device."""
+        my, mx, th, tw = plan[4], plan[5], plan[7], plan[8]
+        B, T = x01.shape[0], my * mx
+        R = B * T
+        s = _stream(x01)
+        nz_rows = self._tile_gather(field, plan)
+        cond = None
+        if condition == "slice":
+            # the tower: once per slice on the whole slice, at most max_sub_batch slices at a time, on a tower-only engine per
+            # U-Net in use; the engine of the tiles turns its outputs into conditioning rows, repeated for the slice's tiles.  The
+            # rows of a preset are already in [-1, 1] (_sample)
+            x_n = normalize_to_neg_one_to_one(x01)
+            x_rows = self._tile_gather(x_n, plan)
+            engines = self._engines()
+            _, r0, r1, _ = self._plan()
+            unets = ([self.model.unet0] if r0 else []) + ([self.model.unet1] if r1 else [])
+            cond = [(e._b("til_prompt", (R, e.time_dim), torch.float32), e._b("til_local", (R, e.loc_total), torch.float32))
+                    for e in engines]
+            for c0 in range(0, B, self.max_sub_batch):
+                nb = min(self.max_sub_batch, B - c0)
+                for u, e, (pe, la) in zip(unets, engines, cond):
+                    e.condition_from(*u.tower_engine(e.mode).encode_dose(x_n[c0:c0 + nb]))
+                    L.call("fd_rows_repeat_f32", _p(e.prompt_emb), _p(pe[c0 * T:]), nb, T, e.time_dim, s)
+                    L.call("fd_rows_repeat_f32", _p(e.local_all), _p(la[c0 * T:]), nb, T, e.loc_total, s)
+        else:
+            x_rows = self._tile_gather(x01, plan)                  # plain rows of _sample, which normalises them itself
+        tiles = torch.empty((R, 1, th, tw), device=x01.device, dtype=torch.float32)
+        keyed_steps = not self._is_shipped() and not self.is_ddim_sampling      # _generic_loop's ancestral steps draw from torch
+        for lo, hi in tile_passes(B, my, mx, self.streams * self.max_sub_batch, self.streams):
+            sl = slice(lo, hi)
+            size = (hi - lo, 1, th, tw)
+            sd = seeds[sl].contiguous()
+            step_noise = (lambda t, sd=sd, size=size: self._keyed_noise(sd, t, size)) if keyed_steps else None
+            pre = {} if cond is None else {"cond": self._cond_rows(cond, sl)}
+            out = self._sample([x_rows[sl]], hi - lo, True, nz_rows[sl], step_noise, sd, **pre)
+            tiles[sl].copy_(out[-1])
+        return tiles
+
     def _sample(self, x_input, batch_size, last, noise, step_noise, slice_seeds, cond=None):
         """`cond`: the preset conditioning of sample_ensemble (_encode_all), whose x_input is already in [-1, 1]; it is sliced the
         way `noise` is and no tower runs."""
@@ -1321,7 +1466,7 @@ class Trainer(object):
     `crop_size` (an int or (h, w), multiples of 2 ** (levels - 1) of the U-Net; None: whole slices) trains on the reference's
     CropToFixed patches (data/transforms.py:196-249): every training pair is cut to the window diffusion_train.train_crop draws
     per item, reflect-padded where the slice is smaller, before the flip / rot90, which then needs a square crop for its odd
-    rotations and no longer square slices; sample() and test() keep whole slices.
+    rotations and no longer square slices; sample() and test() keep whole slices (test(tile=...) samples them as tiles of that size).
     `train_dataset` may be a data.DeviceSliceStore: train() then gathers (and augments) every micro-batch on the device and
     uploads no image.  `seed` keys what train() draws (diffusion_train.train_batch_indices / train_t_and_seeds / train_augment),
     `log_every` is how often the loss is read back from the device.
@@ -1335,7 +1480,10 @@ class Trainer(object):
     held-out loss and the one-step PSNR / RMSE per noise band of `val_bands` (increasing edges inside [0, T]), on the first
     `val_items` items (None: all), keyed by `val_seed`, `val_batch_size` (item, band) pairs per launch sequence.  train() calls
     it every `validate_every` steps (0: never) and, with `keep_best`, saves model-best.pt whenever a validation beats every
-    earlier one of this process.  All of it is off by default."""
+    earlier one of this process.  All of it is off by default.  `val_crop_size` (an int or (h, w); None: whole slices) makes
+    validate() evaluate the centred window of that size of every held-out slice -- the reference's CropToFixed(Center=True),
+    origin (n - c) // 2 per axis -- which is how a model trained with `crop_size` was trained; a crop larger than the slice
+    raises."""
 
     def __init__(self, opt, diffusion_model, folder=None, *, train_batch_size=16, gradient_accumulate_every=1,
                  augment_flip=True, train_lr=1e-4, train_num_steps=100000, ema_update_every=10, ema_decay=0.995,
@@ -1343,8 +1491,8 @@ class Trainer(object):
                  amp=False, fp16=False, split_batches=True, convert_image_to=None, condition=False, sub_dir=False,
                  equalizeHist=False, crop_patch=False, generation=False, num_unet=2, checkpoint_folder=None,
                  is_train=True, train_logger=None, dataset=None, device=None, train_dataset=None, seed=0, log_every=100,
-                 augment=False, crop_size=None, optimizer=None, radam_betas=(0.9, 0.999), val_dataset=None, validate_every=0,
-                 val_bands=(0, 250, 500, 750, 1000), val_items=None, val_seed=0, val_batch_size=8, keep_best=False):
+                 augment=False, crop_size=None, optimizer=None, radam_betas=(0.9, 0.999), val_crop_size=None, val_dataset=None,
+                 validate_every=0, val_bands=(0, 250, 500, 750, 1000), val_items=None, val_seed=0, val_batch_size=8, keep_best=False):
         import logging
         import os as _os
         if optimizer not in (None, "adam", "radam"):
@@ -1366,6 +1514,9 @@ class Trainer(object):
         self.val_log = []                    # validate()'s results of this process, in order; not part of a checkpoint
         self.best = None                     # with keep_best: the entry of val_log that save("best") was last called for
         self._val_store = None               # val_dataset on the device, made at the first validate()
+        self.val_crop_size = None if val_crop_size is None else dt.crop_pair("Trainer", val_crop_size, "val_crop_size")
+        if self.val_crop_size is not None and min(self.val_crop_size) < 1:
+            raise RuntimeError(f"Trainer: val_crop_size {self.val_crop_size} must be positive")
         self.crop_size = None
         if crop_size is not None:
             from .data import crop_pair
@@ -1568,8 +1719,9 @@ class Trainer(object):
     # ---- held-out evaluation during a run (the reference has none before its full test() at step 50 000, src/DADiff.py:1731-1745)
     @torch.no_grad()
     def validate(self, precision="fp32"):
-        """The EMA model (the model itself until train() copies it) on val_dataset: whole slices, no crop, no augmentation, the
-        first val_items of them (None: all).  Every item is evaluated once per noise band of val_bands, at the t and with the
+        """The EMA model (the model itself until train() copies it) on val_dataset: whole slices (with val_crop_size their centred
+        window of that size, through the store's explicit windows), no augmentation, the first val_items of them (None: all).
+        Every item is evaluated once per noise band of val_bands, at the t and with the
         noise diffusion_train.val_draws keys by (val_seed, item, band), in batches of val_batch_size (item, band) pairs through
         diffusion_train.StoreBatch and ResidualDiffusion.eval_items on the `precision` engine; a host dataset goes to the device
         once, at the first call.  Returns {"step", "bands", "loss", "psnr", "rmse", "n"}: loss, psnr and rmse are lists per
@@ -1587,13 +1739,21 @@ class Trainer(object):
             ds = self.val_dataset
             self._val_store = ds if isinstance(ds, DeviceSliceStore) else DeviceSliceStore.from_dataset(ds, self.device)
         store, ema = self._val_store, self.ema.ema_model
+        crop = self.val_crop_size
+        if crop is not None and (crop[0] > store.H or crop[1] > store.W):
+            raise RuntimeError(f"{fn}: val_crop_size {crop[0]} x {crop[1]} is larger than the slices {store.H} x {store.W}")
         n = len(store) if self.val_items is None else min(int(self.val_items), len(store))
         item, band, t, seeds = dt.val_draws(self.val_seed, range(n), self.val_bands, ema.num_timesteps)
         self._fresh_engines()
         rows = []
         for s in range(0, len(item), self.val_batch_size):
             sl = slice(s, s + self.val_batch_size)
-            rows.append(ema.eval_items(dt.StoreBatch(store, item[sl]), t[sl], slice_seeds=seeds[sl], precision=precision))
+            if crop is None:
+                batch = dt.StoreBatch(store, item[sl])
+            else:                                             # the centred window: CropToFixed(Center=True), origin (n - c) // 2
+                win = np.tile(np.array([[(store.H - crop[0]) // 2, (store.W - crop[1]) // 2]], dtype=np.int64), (len(item[sl]), 1))
+                batch = dt.StoreBatch(store, item[sl], None, win, crop)
+            rows.append(ema.eval_items(batch, t[sl], slice_seeds=seeds[sl], precision=precision))
         nb = len(self.val_bands) - 1
         per_unet = [torch.cat([r[u] for r in rows]).cpu().numpy() for u in range(len(rows[0]))]      # the one synchronisation
         sums = [dt.val_summary(v, band, nb) for v in per_unet]
@@ -1694,7 +1854,8 @@ class Trainer(object):
         return out
 
     @torch.no_grad()
-    def test(self, sample=False, last=True, FID=False, batch_size=1, n_samples=1, ensemble_seed=0):
+    def test(self, sample=False, last=True, FID=False, batch_size=1, n_samples=1, ensemble_seed=0, tile=None, overlap=0,
+             tile_condition="tile"):
         """Evaluation loop of src/DADiff.py:1817-1966: init() the schedule, denoise every slice,
         PSNR/SSIM/RMSE vs NDCT (on device), np.save each output in [0,1], per-anatomy / per-dose means.
         `batch_size` > 1 batches independent slices (the reference uses 1).  `sample=True` keeps the
@@ -1702,9 +1863,17 @@ class Trainer(object):
         reference's unconditional `self.sample` rounds (100, or up to 50000 images with FID).
         `n_samples` > 1: every slice is denoised as an ensemble (ResidualDiffusion.sample_ensemble) under the slice seed
         `ensemble_seed` + its dataset index; the metrics and the saved image are those of the ensemble mean, and outside
-        training the per-pixel standard deviation is saved beside it as `<name>_std.npy`."""
+        training the per-pixel standard deviation is saved beside it as `<name>_std.npy`.
+        `tile` (an int or (th, tw); None: whole slices, as ever): every slice is sampled as overlapping tiles
+        (ResidualDiffusion.sample_tiled with `overlap` and condition=`tile_condition`) under the slice seed `ensemble_seed` + its
+        dataset index; the metrics and the saved image are those of the blended slice.  Ensembles of tiled samples
+        (n_samples > 1) and last=False are not built and raise."""
         if int(n_samples) < 1:
             raise RuntimeError(f"Trainer.test: n_samples must be at least 1 (got {n_samples})")
+        if tile is not None and int(n_samples) > 1:
+            raise RuntimeError(f"Trainer.test: tile={tile!r} with n_samples={n_samples}: ensembles of tiled samples are not built")
+        if tile is not None and not last:
+            raise RuntimeError("Trainer.test: tile with last=False is not built (sample_tiled returns the final image)")
         # batch_size 1 is the reference's loop: one slice per sample() call -> the kernel set for a lone slice (DAEngine
         # low_latency: same arithmetic, chunked scans at every level; outputs differ from a batched run by fp32
         # summation order).  The switch is only ever turned ON here (FOUNDDIFF_LOW_LATENCY=1 stays in force for any batch
@@ -1715,15 +1884,16 @@ class Trainer(object):
                  if u is not None and hasattr(u, "low_latency")]
         saved = [u.low_latency for u in unets]
         try:
-            if batch_size == 1 and int(n_samples) == 1:       # (an ensemble is a batch of replicas: the default kernel set)
-                for u in unets:
+            if batch_size == 1 and int(n_samples) == 1 and tile is None:      # (an ensemble is a batch of replicas, a tiled slice
+                for u in unets:                                           # a batch of tiles: the default kernel set)
                     u.low_latency = True
-            return self._test(sample, last, FID, batch_size, int(n_samples), int(ensemble_seed))
+            tiled = None if tile is None else (tile, overlap, tile_condition)
+            return self._test(sample, last, FID, batch_size, int(n_samples), int(ensemble_seed), tiled)
         finally:
             for u, v in zip(unets, saved):
                 u.low_latency = v
 
-    def _test(self, sample, last, FID, batch_size, n_samples=1, ensemble_seed=0):
+    def _test(self, sample, last, FID, batch_size, n_samples=1, ensemble_seed=0, tiled=None):
         from .metrics import compute_metrics
         model = self.ema.ema_model                   # inference uses the EMA weights (src/DADiff.py:1818-1822)
         model.init()
@@ -1754,6 +1924,10 @@ class Trainer(object):
             if n_samples > 1:
                 ens = model.sample_ensemble(xs, n_samples, slice_seeds=[ensemble_seed + i for i in idx])
                 y_pred, y_std = ens.mean, ens.std
+            elif tiled is not None:
+                outs = model.sample_tiled(xs, tiled[0], tiled[1], slice_seeds=[ensemble_seed + i for i in idx], condition=tiled[2])
+                all_images_list = [y] + xs + list(outs)
+                y_pred = outs[-1]
             elif sample:
                 all_images_list = [y] + xs + list(model.sample(xs, batch_size=len(idx)))
                 y_pred = all_images_list[-1]

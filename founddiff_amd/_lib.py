@@ -180,6 +180,8 @@ SIGNATURES = {
     "fd_ensemble_nblk": (i32, [i64]),
     "fd_rows_repeat_f32": (i32, [vp, vp, i32, i32, i64, vp]),
     "fd_ensemble_stats_f32": (i32, [vp, vp, vp, vp, vp, i32, i32, i64, vp]),
+    "fd_tiles_gather_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "fd_tiles_blend_f32": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "fd_store_gather_f32": (i32, [vp, vp, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "fd_res_qsample_store_f32": (i32, [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32,
                                        i32, vp]),

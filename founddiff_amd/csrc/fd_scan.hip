@@ -928,6 +928,12 @@ void launch_scan_seq(const T *xc, const float *xdbl, const float *dtw, const flo
     }
 }
 
+// the carry-ins of a single chunk: n zeros
+__global__ __launch_bounds__(256) void scan_zero_kernel(float *__restrict__ p, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = 0.f;
+}
+
 static bool scan_cpl2_on() {
     const bool off = fd_dev(FD_DEV_SCAN_NO_CPL2);    // development switch
     return !off;
@@ -991,8 +997,9 @@ void launch_scan(const T *xc, const float *xdbl, const float *dtw, const float *
         else if (p.carry == 8) hipLaunchKernelGGL(scan_carry_kernel<8>, cgrid, cblock, 0, s, wsH, wsP, A, asc, g.nch, g.N, g.D);
         else hipLaunchKernelGGL(scan_carry_kernel<0>, cgrid, cblock, 0, s, wsH, wsP, A, asc, g.nch, g.N, g.D);
     }
-    else
-        (void)hipMemsetAsync(wsH, 0, half * sizeof(float), s);
+    else   // a kernel, not hipMemsetAsync: inside a captured loop graph the memset node left stale carry-ins in place (a level of
+           // 16 x 16 pixels, the only shape with one chunk: a sample() there differed from capture to capture and from the eager loop)
+        hipLaunchKernelGGL(scan_zero_kernel, dim3((unsigned)((half + 255) / 256)), dim3(256), 0, s, wsH, half);
     if (two) hipLaunchKernelGGL((scan_chunk_kernel<T, N, R, true, ODD, CPL>), grid, block, lds, s, xc, xdbl, dtw, dtb, A, Ds, y, wsH, wsP, g);
     else hipLaunchKernelGGL((scan_chunk_kernel<T, N, R, true, ODD>), grid, block, lds, s, xc, xdbl, dtw, dtb, A, Ds, y, wsH, wsP, g);
 }

@@ -799,9 +799,15 @@ class DAEngine:
     def encode_condition(self, x_cond):
         """DA-CLIP encoder + prompt path + per-block `local` vectors; t-independent,
         so it runs once per slice instead of once per step.  x_cond (B,1,H,W) fp32 in [-1,1]."""
-        B = x_cond.shape[0]
+        return self.condition_from(*self.encode_dose(x_cond))
+
+    def condition_from(self, dose, ctx):
+        """What encode_condition does behind the tower, for given tower outputs dose (B, 1024), ctx (B, 256), fp32: this engine's
+        prompt path and `local` vectors.  ResidualDiffusion.sample_tiled(condition="slice") runs the tower on whole slices on a
+        tower-only engine of the same kernel mode and hands its rows in here, so that this engine's image-sized buffers stay those
+        of its tiles."""
+        B = dose.shape[0]
         s = self.stream
-        dose, ctx = self.encode_dose(x_cond)
         # prompt path (src/DADiff.py:706-707)
         pr = self.prompt
         td = self.time_dim

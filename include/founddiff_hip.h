@@ -780,6 +780,24 @@ int fd_rows_repeat_f32(const float *src, float *dst, int B, int K, int64_t n, vo
 int fd_ensemble_stats_f32(const float *samples, float *mean, float *std, float *ws, float *spread, int B, int K, int64_t n,
                           void *stream);
 
+/* ---- a slice as overlapping tiles (fd_tiles.hip; ResidualDiffusion.sample_tiled; founddiff_amd/tiling.py) --------
+ * fp32, the same in both builds of the library.  Deterministic, no atomics, no workspace.  The plan: my x mx tiles of th x tw
+ * pixels at the origins ys [my], xs [mx] (int32, DEVICE memory; 0 <= ys <= H - th, 0 <= xs <= W - tw, a tile whose origin is
+ * outside that range is not touched); tile row r = (b my + iy) mx + ix.  xs_mult4: the host's word that every xs is a multiple
+ * of 4.  1 <= th <= H, 1 <= tw <= W, my, mx >= 1, B my mx <= 65535, H, W <= 32768.
+ * fd_tiles_gather_f32: dst [B my mx][th tw], dst[r] = the window of src[b] ([B][H W]) at (ys[iy], xs[ix]): a copy.  16-byte
+ *   accesses when xs_mult4, W % 4 == 0, tw % 4 == 0 and src, dst are 16-byte aligned, scalar otherwise: the same bits.
+ * fd_tiles_blend_f32: out [B][H W]; per pixel, over the tiles that cover it in row-major tile order (iy, then ix ascending):
+ *   w = wy[iy][y - ys[iy]] * wx[ix][x - xs[ix]] (wy [my][th], wx [mx][tw]), num = fmaf(w, v, num), den += w, out = num / den
+ *   with the correctly rounded division.  A gather: one lane per 4 pixels of an output row, so a pixel depends on H, W, the plan
+ *   and its covering tiles alone, not on B.  A pixel under ONE tile whose weight there is 1 (tiling.tile_weights gives that) has
+ *   den = 1 and out = that tile's value, bit for bit.  The 16-byte form (xs_mult4, W % 4 == 0, tw % 4 == 0, tiles, wx and out
+ *   16-byte aligned) and the scalar form give the same bits.  A pixel no tile covers is 0 / 0. */
+int fd_tiles_gather_f32(const float *src, float *dst, const int *ys, const int *xs, int B, int H, int W, int th, int tw, int my,
+                        int mx, int xs_mult4, void *stream);
+int fd_tiles_blend_f32(const float *tiles, const float *wy, const float *wx, const int *ys, const int *xs, float *out, int B,
+                       int H, int W, int th, int tw, int my, int mx, int xs_mult4, void *stream);
+
 /* ---- a training batch from a slice store on the device (fd_train_data.hip; data/pdf_dataset.py:521-545) -------
  * nd [n_nd][H][W], ld [n_ld][H][W] fp32 in [0, 1].  Item b of the batch is the pair nd[nd_slot[b]], ld[ld_slot[b]] (int64 [B],
  * clamped to the store), both under the transform codes[b] (int64 [B], low 4 bits; a null codes is all 0):
