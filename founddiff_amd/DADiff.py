@@ -1432,11 +1432,21 @@ class _Accel:
     is_local_main_process = True
     is_main_process = True
 
-    def __init__(self, device):
-        self.device = device
+    def __init__(self, device, group=None, data_parallel=False):
+        """data_parallel: the attributes become those of this rank of `group` (Trainer(data_parallel=True))"""
+        self.device, self.group, self.data_parallel = device, group, bool(data_parallel)
+        if self.data_parallel:
+            import torch.distributed as dist
+            self.is_main_process = dist.get_rank(group) == 0
+            self.is_local_main_process = int(os.environ.get("LOCAL_RANK", dist.get_rank(group))) == 0
 
     def wait_for_everyone(self):
-        pass
+        if self.data_parallel:
+            import torch.distributed as dist
+            if dist.get_backend(self.group) == "nccl" and self.device.index is not None:
+                dist.barrier(group=self.group, device_ids=[self.device.index])
+            else:
+                dist.barrier(group=self.group)
 
 
 class _EMAView:
@@ -1483,7 +1493,18 @@ class Trainer(object):
     earlier one of this process.  All of it is off by default.  `val_crop_size` (an int or (h, w); None: whole slices) makes
     validate() evaluate the centred window of that size of every held-out slice -- the reference's CropToFixed(Center=True),
     origin (n - c) // 2 per axis -- which is how a model trained with `crop_size` was trained; a crop larger than the slice
-    raises."""
+    raises.
+    `data_parallel=True` (off by default; `process_group` None: the default group) trains on the W ranks of an initialised
+    torch.distributed group, one process per GPU, the reference's accelerate / DDP run (src/DADiff.py:1546-1623, 1705-1720).
+    init_process_group is the caller's job (give it a finite timeout=, so that a lost peer ends in an error).  Micro-batch a of
+    rank r is global micro-batch a W + r of A W, A = gradient_accumulate_every per rank: that number and that count key the
+    indices, t, seeds, codes and windows, and the loss scale is 1 / (A W); diffusion_train.GradReducer adds the ranks' gradients
+    in rank order, so that every parameter, EMA tensor, optimiser tensor and logged loss is bit for bit that of one process with
+    gradient_accumulate_every = A W, whatever W.  Batch semantics: the reference's split_batches=True splits one batch of
+    train_batch_size over the ranks; here a rank keeps train_batch_size and A W counts the micro-batches of a step.  Rank 0's
+    model and buffers are broadcast once when training is set up; a DeviceSliceStore is held whole by every rank; previews,
+    validate() and the checkpoint file are rank 0's, save() is called by every rank and ends in a barrier and check_replicas(),
+    load(for_training=True) runs on every rank.  `split_batches` itself is ignored, as before."""
 
     def __init__(self, opt, diffusion_model, folder=None, *, train_batch_size=16, gradient_accumulate_every=1,
                  augment_flip=True, train_lr=1e-4, train_num_steps=100000, ema_update_every=10, ema_decay=0.995,
@@ -1491,10 +1512,21 @@ class Trainer(object):
                  amp=False, fp16=False, split_batches=True, convert_image_to=None, condition=False, sub_dir=False,
                  equalizeHist=False, crop_patch=False, generation=False, num_unet=2, checkpoint_folder=None,
                  is_train=True, train_logger=None, dataset=None, device=None, train_dataset=None, seed=0, log_every=100,
-                 augment=False, crop_size=None, optimizer=None, radam_betas=(0.9, 0.999), val_crop_size=None, val_dataset=None,
+                 augment=False, crop_size=None, optimizer=None, radam_betas=(0.9, 0.999), val_crop_size=None, data_parallel=False,
+                 process_group=None, val_dataset=None,
                  validate_every=0, val_bands=(0, 250, 500, 750, 1000), val_items=None, val_seed=0, val_batch_size=8, keep_best=False):
         import logging
         import os as _os
+        self.data_parallel, self.process_group = bool(data_parallel), process_group
+        self.world, self.rank = 1, 0
+        if self.data_parallel:
+            import torch.distributed as dist
+            if not (dist.is_available() and dist.is_initialized()):
+                raise RuntimeError("Trainer: data_parallel=True needs an initialised process group: call "
+                                   "torch.distributed.init_process_group (with a finite timeout=) before the constructor")
+            self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
+        self._reducer = None                 # diffusion_train.GradReducer, made with the optimiser
+        self.fingerprints = None             # with data_parallel: every rank's fingerprint at the last replica check
         if optimizer not in (None, "adam", "radam"):
             raise RuntimeError(f"Trainer: optimizer must be None, 'adam' or 'radam' (got {optimizer!r})")
         if len(tuple(radam_betas)) != 2 or not all(isinstance(b, (int, float)) and 0 <= b < 1 for b in radam_betas):
@@ -1538,7 +1570,7 @@ class Trainer(object):
         self.sub_dir, self.crop_patch = sub_dir, crop_patch
         self.image_size = diffusion_model.image_size
         self.device = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
-        self.accelerator = _Accel(self.device)
+        self.accelerator = _Accel(self.device, process_group, self.data_parallel)
         self.model = diffusion_model.to(self.device)
         self.ema = _EMAView(self.model)      # inference uses the EMA weights (src/DADiff.py:1818-1822)
         self.sample_dataset = dataset if dataset is not None else folder
@@ -1553,6 +1585,7 @@ class Trainer(object):
         self.augment = bool(augment)
         self.opt0 = None                     # ClipAdamEMA, made with the EMA copy at the first train() / save() / load(for_training=True)
         self.losses = None                   # the last step's losses, on the device
+        self.loss_log = []                   # (step, [loss per U-Net]) of every logged step (the last 1024), as floats
         self.batch_log = []                  # a debugging aid: the dataset indices train() drew, one list per micro-batch (the
                                              # last 1024); diffusion_train.train_batch_indices gives the same without a run
         self._stale = False                  # a step has written the weights since the engines were packed
@@ -1618,13 +1651,45 @@ class Trainer(object):
         if self.opt0 is None:
             if self.device.type != "cuda":
                 raise RuntimeError("Trainer.train: the model must live on the GPU (there is no CPU path)")
+            if self.data_parallel:
+                # once: every replica starts from rank 0's model and buffers; from here on identical gradients keep them identical
+                from .parallel import broadcast_tensors
+                broadcast_tensors(list(dif.parameters()) + list(dif.buffers()), 0, self.process_group)
+                if self.ema.ema_model is not dif:
+                    broadcast_tensors(list(self.ema.ema_model.parameters()) + list(self.ema.ema_model.buffers()), 0, self.process_group)
+                dif.weights_changed()
             if self.ema.ema_model is dif:
                 self.ema = _EMAView(dif.clone())
             eparams = list(self.ema.ema_model.parameters())
             cls, betas = (dt.ClipRAdamEMA, self.radam_betas) if self.optimizer == "radam" else (dt.ClipAdamEMA, self.adam_betas)
             self.opt0 = cls([params[i] for i in index], [eparams[i] for i in index], lr=self.train_lr, betas=betas, max_norm=1.0,
                             ema_beta=self.ema_decay, ema_update_every=self.ema_update_every)
+            if self.data_parallel:
+                self._reducer = dt.GradReducer(self.opt0, self.process_group)
         return index, len(params)
+
+    def fingerprint(self):
+        """an int64 sum of the parameters, the EMA copy's, the optimiser's moments and its step counts, each viewed as int32: equal
+        on two replicas whose tensors are bitwise equal (and almost surely different otherwise).  Reads the device."""
+        self._setup_training()
+        tensors = [p.detach() for p in self.model.parameters()] + [p.detach() for p in self.ema.ema_model.parameters()] + \
+            [self.opt0._m, self.opt0._v, self.opt0._steps]
+        tot = torch.zeros((), dtype=torch.int64, device=self.device)
+        for t in tensors:
+            if t.element_size() == 4 and t.numel():
+                tot = tot + t.contiguous().view(-1).view(torch.int32).sum(dtype=torch.int64)
+        return int(tot.item()) + int(self.opt0.ema_step)
+
+    def check_replicas(self):
+        """data_parallel: every rank's fingerprint() gathered on every rank (self.fingerprints); RuntimeError on every rank if two
+        differ -- the replicas have drifted apart, which identical gradients and identical optimisers cannot do."""
+        if not self.data_parallel:
+            return
+        from .parallel import gather_int64
+        self.fingerprints = gather_int64(self.fingerprint(), self.device, self.process_group)
+        if len(set(self.fingerprints)) != 1:
+            raise RuntimeError(f"Trainer: the replicas differ at step {self.step}: fingerprints per rank {self.fingerprints} "
+                               f"(parameters, EMA and optimiser state as int32 sums)")
 
     def _two_unets(self):
         return getattr(self.model.model, "num_unet", 1) == 2
@@ -1656,7 +1721,10 @@ class Trainer(object):
         earlier one of this process is followed by save("best") (_keep_best).  val_log and best are not part of a checkpoint,
         whose keys stay diffusion_train.CHECKPOINT_KEYS (CHECKPOINT_KEYS_2 for two U-Nets): a resumed run starts with both empty
         and re-establishes its best at its first validation, overwriting model-best.pt whatever the interrupted run had reached.
-        optimizer='radam' runs the same loop around ClipRAdamEMA, on one U-Net or two; the log line then has loss_unet1 too."""
+        optimizer='radam' runs the same loop around ClipRAdamEMA, on one U-Net or two; the log line then has loss_unet1 too.
+        With data_parallel every rank runs this loop over its own micro-batch numbers (a W + rank) and the gradients meet in
+        diffusion_train.GradReducer; rank 0 logs, previews and validates, every rank joins save() and the replica check that
+        also ends the run.  loss_log keeps (step, losses) of every logged step on every rank."""
         from .data import DeviceSliceStore
         self._setup_training()
         ds = self.train_dataset
@@ -1664,10 +1732,13 @@ class Trainer(object):
             raise RuntimeError("Trainer.train: give the constructor a train_dataset (__len__, __getitem__ -> [ndct, ldct])")
         if self.sample_dataset is None:
             self.sample_dataset = ds
-        acc, every, T = self.gradient_accumulate_every, self.save_and_sample_every, self.model.num_timesteps
+        every, T = self.save_and_sample_every, self.model.num_timesteps
+        # data_parallel: micro-batch a of this rank is global micro-batch a W + rank of the step's A W
+        W, rank, main = self.world, self.rank, self.rank == 0
+        acc = self.gradient_accumulate_every * W
         while self.step < self.train_num_steps:
             batches, ts, seeds = [], [], []
-            for m in range(acc):
+            for m in (dt.dp_micro(a, W, rank) for a in range(self.gradient_accumulate_every)):
                 idx = dt.train_batch_indices(self.seed, self.step, m, self.batch_size, len(ds), acc)
                 self.batch_log.append(idx)
                 t, sd = dt.train_t_and_seeds(self.seed, self.step, m, idx, T)
@@ -1687,27 +1758,48 @@ class Trainer(object):
                 ts.append(torch.from_numpy(t).to(self.device))
                 seeds.append(torch.from_numpy(sd).to(self.device))
             del self.batch_log[:-1024]
-            self.losses = dt.train_step(self.model, self.opt0, batches, t=ts, slice_seeds=seeds, step=self.step)
+            self.losses = dt.train_step(self.model, self.opt0, batches, t=ts, slice_seeds=seeds, step=self.step, reducer=self._reducer)
             self._stale = True
             self.step += 1
             if self.log_every > 0 and self.step % self.log_every == 0:                 # the one synchronisation of these steps
-                self.train_logger.info("Iters: [%d/%d], " % (self.step, self.train_num_steps) +
-                                       ", ".join("loss_unet%d: %.6f" % (u, float(v)) for u, v in enumerate(self.losses)))
+                vals = [float(v) for v in self.losses]
+                self.loss_log.append((self.step, vals))
+                del self.loss_log[:-1024]
+                if main:
+                    self.train_logger.info("Iters: [%d/%d], " % (self.step, self.train_num_steps) +
+                                           ", ".join("loss_unet%d: %.6f" % (u, v) for u, v in enumerate(vals)))
             if self.validate_every > 0 and self.step % self.validate_every == 0:
-                res = self.validate()
-                if self.keep_best:
+                res = self.validate() if main else None
+                if self.keep_best and not self.data_parallel:
                     self._keep_best(res)
+                elif self.keep_best:                                                   # rank 0 decides, every rank joins save()
+                    from .parallel import gather_int64
+                    if gather_int64(int(self._is_best(res)) if main else 0, self.device, self.process_group)[0]:
+                        self.save("best")
             if self.step % every == 0:
                 milestone = self.step // every
-                self.sample(milestone)
+                if main:
+                    self.sample(milestone)
                 if self.step > every * 10 * 4 and self.step % (every * 10) == 0:
                     self.save(milestone)
+        self.check_replicas()
         print("training complete")
 
     def save(self, milestone):
         """`<results>/model-N.pt` = {'step', 'model', 'opt0', 'ema', 'scaler': None} (src/DADiff.py:1626-1646;
         diffusion_train.checkpoint_pack)."""
         index, n = self._setup_training()
+        if self.data_parallel:
+            # every rank calls save(): rank 0 writes the file (its keys and layout are the single process's: a checkpoint written
+            # at W ranks of A micro-batches resumes at any W', A' with A' W' = A W), then a barrier and the replica check
+            if self.rank == 0:
+                self._write_checkpoint(milestone, index, n)
+            self.accelerator.wait_for_everyone()
+            self.check_replicas()
+            return
+        self._write_checkpoint(milestone, index, n)
+
+    def _write_checkpoint(self, milestone, index, n):
         ema_sd = {k: v.detach().clone() for k, v in self.ema.ema_model.state_dict().items()}
         model_sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
         if self._two_unets():
@@ -1784,13 +1876,19 @@ class Trainer(object):
     def _keep_best(self, res):
         """save("best") if `res` (a result of validate()) beats every earlier one of this process: a higher mean one-step PSNR,
         or a lower mean loss where no U-Net has a residual output.  self.best = {"step", "metric", "value"} of the winner."""
+        if self._is_best(res):
+            self.save("best")
+            self.train_logger.info("Iters: [%d/%d], best val_%s so far: %.6f, saved model-best.pt" % (
+                self.step, self.train_num_steps, self.best["metric"], self.best["value"]))
+
+    def _is_best(self, res):
+        """whether `res` beats every earlier validation of this process; self.best then becomes its entry"""
         metric, value = self._val_score(res)
         old = self.best
         if old is None or np.isnan(old["value"]) or (value > old["value"] if metric == "psnr" else value < old["value"]):
             self.best = {"step": res["step"], "metric": metric, "value": value}
-            self.save("best")
-            self.train_logger.info("Iters: [%d/%d], best val_%s so far: %.6f, saved model-best.pt" % (
-                self.step, self.train_num_steps, metric, value))
+            return True
+        return False
 
     # anatomy groups of the reference's 2020 test list, in item order: (name, slices per dose level); each holds
     # 4 dose levels back to back (src/DADiff.py:1918-1950).  "head" is taken from the END of the list, as there.

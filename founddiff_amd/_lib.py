@@ -175,6 +175,9 @@ SIGNATURES = {
     "fd_opt_clip_coef": (i32, [vp, i32, vp, vp, i32, f32, i32, vp, vp]),
     "fd_opt_adam_ema_f32": (i32, [vp, vp, vp, vp, i32, f64, f64, f64, f64, i32, f64, i32, i32, vp]),
     "fd_opt_radam_ema_f32": (i32, [vp, vp, vp, vp, i32, f64, f64, f64, f64, i32, f64, i32, i32, vp]),
+    "fd_grads_tail_floats": (i32, []),
+    "fd_grads_pack_f32": (i32, [vp, vp, vp, i32, vp, i64, vp, i32, i32, vp]),
+    "fd_grads_rank_sum_f32": (i32, [vp, vp, vp, i32, vp, i32, i64, vp, i64, i32, i32, vp]),
     "fd_val_items_ws_floats": (i64, [i32, i64]),
     "fd_val_items_f32": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, i64, vp]),
     "fd_ensemble_nblk": (i32, [i64]),

@@ -12,6 +12,9 @@
     ClipRAdamEMA(params, ema_params, ...)          the same around torch.optim.RAdam's rule: the reference's optimiser of two U-Nets,
                                                    one object over the parameters of both (joint clip, both updates, one EMA)
     train_step(diffusion_or_fn, opt, batch, ...)   p_losses -> backward per loss -> opt.step()
+    GradReducer(opt, group)                        data-parallel training: per micro-batch pack the gradients, all-gather, add the
+                                                   ranks' rows in rank order (csrc/fd_grad_sum.hip); train_step(reducer=...) is then
+                                                   bit for bit the single process over all ranks' micro-batches
     StoreBatch(store, indices, codes)              a micro-batch that stays in a data.DeviceSliceStore: accepted wherever
                                                    [x_start, x_input] is; q_sample then gathers, flips / rotates and diffuses it in
                                                    one launch (csrc/fd_train_data.hip), fed by one int64 table from pinned memory;
@@ -53,7 +56,7 @@ __all__ = ["q_sample", "residual_loss", "p_losses_fn", "p_losses", "ClipAdamEMA"
            "adam_state_unpack", "adam_state_pack", "train_batch_indices", "train_t_and_seeds", "train_augment", "augment_source_index",
            "train_crop", "crop_source_index", "StoreBatch", "checkpoint_pack", "checkpoint_unpack", "CHUNK", "check_bands", "val_draws",
            "val_items", "val_summary", "ClipRAdamEMA", "radam_scalars", "optimizer_kind", "CHECKPOINT_KEYS", "CHECKPOINT_KEYS_2",
-           "checkpoint_pack2", "checkpoint_unpack2"]
+           "checkpoint_pack2", "checkpoint_unpack2", "GradReducer", "ordered_sum", "dp_micro"]
 
 CHUNK = 4096                      # elements of a parameter per workgroup (fd_opt_chunk_elems())
 _LOSS_TYPES = {"l1": 1, "l2": 2}
@@ -953,9 +956,111 @@ class ClipRAdamEMA(ClipAdamEMA):
         super().load_state_dict(sd)
 
 
+# ---- data-parallel training: the ordered gradient sum --------------------------------------------------------------------------------
+def ordered_sum(rounds):
+    """The sum GradReducer computes, in numpy: `rounds` is a sequence of (W, N) float32 arrays, one per call, row r from rank r.
+    acc = 0; then acc = acc + rounds[a][r] for a outer and r inner, every add rounded to float32: global micro-batch a W + r in
+    its own order, which is the order a single process accumulates its A W micro-batches in."""
+    acc = None
+    for rows in rounds:
+        rows = np.asarray(rows, dtype=np.float32)
+        if rows.ndim != 2 or (acc is not None and rows.shape[1:] != acc.shape):
+            raise RuntimeError(f"ordered_sum: every round is a (W, N) array with one N (got {rows.shape})")
+        if acc is None:
+            acc = np.zeros(rows.shape[1], dtype=np.float32)
+        for r in range(rows.shape[0]):
+            acc = (acc + rows[r]).astype(np.float32)
+    if acc is None:
+        raise RuntimeError("ordered_sum: no rounds")
+    return acc
+
+
+def dp_micro(a, world, rank):
+    """the global number of micro-batch `a` of rank `rank` among `world`: a world + rank.  With A micro-batches per rank the step
+    has A world of them, and the ranks' numbers of round a are consecutive: the rank-ordered sum of round after round adds them
+    in global order."""
+    if world < 1 or not 0 <= rank < world or a < 0:
+        raise RuntimeError(f"dp_micro: invalid arguments a={a} world={world} rank={rank}")
+    return int(a) * int(world) + int(rank)
+
+
+class GradReducer:
+    """The gradient sum of data-parallel training over ClipAdamEMA's tables: GradReducer(opt, group=None), W = the size of the
+    (initialised) process group, None being the default one.  Every rank calls reduce() once per micro-batch, after all of that
+    micro-batch's backward passes (the U-Nets' parameter sets are disjoint: each tensor holds one contribution):
+
+      1. fd_grads_pack_f32: the gradients of the tensors that have one go to a flat buffer (the layout of the optimiser's moments:
+         offs = cumsum((numel + 3) & ~3), padding zero), the micro-batch's losses into the tail behind them, and the gradients are
+         zeroed, so the next backward starts from 0 as a single process's does after zero_grad;
+      2. parallel.all_gather_flat: every rank receives every rank's buffer, (W, N);
+      3. fd_grads_rank_sum_f32: v = first ? 0 : acc; v = v + recv[r] for r = 0 .. W - 1 in that order; on the last micro-batch v
+         goes to the .grad tensors, otherwise to acc.
+
+    With micro-batch a of rank r being global micro-batch a W + r (dp_micro), the .grad tensors after the last call hold, bit for
+    bit, what a single process accumulates over the A W micro-batches in its own order, on every rank; opt.step() then runs
+    unchanged, and replicated optimisers and EMAs stay identical without a broadcast.  losses() gives the summed losses, one 0-dim
+    tensor per U-Net, in the same order of addition.  Memory: (W + 2) N floats, N = the padded parameter count + 4.  A tensor
+    whose .grad is None on this rank contributes zeros and is not written.  There is no CPU path."""
+
+    def __init__(self, opt, group=None):
+        import torch.distributed as dist
+        fn = "GradReducer"
+        if not isinstance(opt, ClipAdamEMA):
+            raise RuntimeError(f"{fn}: opt must be a ClipAdamEMA (got {type(opt).__name__})")
+        if not (dist.is_available() and dist.is_initialized()):
+            raise RuntimeError(f"{fn}: torch.distributed is not initialised (call init_process_group first)")
+        self.opt, self.group = opt, group
+        self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
+        if not 1 <= self.world <= 64:
+            raise RuntimeError(f"{fn}: the group has {self.world} ranks (fd_grads_rank_sum_f32 sums at most 64)")
+        dev = self.device = opt.device
+        offs = np.cumsum([0] + [(p.numel() + 3) & ~3 for p in opt.params]).astype(np.int64)
+        with torch.cuda.device(dev):
+            self.tail = int(L.lib().fd_grads_tail_floats())
+            self.P, self.N = int(offs[-1]), int(offs[-1]) + self.tail
+            self._offs = torch.from_numpy(offs[:-1].copy()).to(dev)
+            self.flat, self.acc = torch.zeros(self.N, device=dev), torch.zeros(self.N, device=dev)
+            self.recv = torch.zeros(self.world, self.N, device=dev)
+        self.n_losses = 0
+
+    def pack(self, losses=(), zero=True):
+        """step 1 alone: this rank's gradients and `losses` (at most 4 scalars on the device) into self.flat"""
+        opt, dev = self.opt, self.device
+        losses = list(losses)
+        if len(losses) > self.tail:
+            raise RuntimeError(f"GradReducer: the tail holds {self.tail} losses (got {len(losses)})")
+        with torch.no_grad(), torch.cuda.device(dev):
+            opt._upload_table()
+            tail = torch.stack([v.detach().reshape(()).float() for v in losses]) if losses else None
+            if tail is not None and tail.device != dev:
+                raise RuntimeError(f"GradReducer: the losses live on {tail.device}, the parameters on {dev}")
+            L.call("fd_grads_pack_f32", ptr(opt._chunks), ptr(opt._table), ptr(self._offs), opt.nchunk, ptr(self.flat), self.P,
+                   ptr(tail), len(losses), int(bool(zero)), stream(dev))
+        self.n_losses = len(losses)
+        return self.flat
+
+    def rank_sum(self, first, last):
+        """step 3 alone: self.recv's rows in rank order onto self.acc (first: onto 0), into the gradients when `last`"""
+        opt, dev = self.opt, self.device
+        with torch.no_grad(), torch.cuda.device(dev):
+            L.call("fd_grads_rank_sum_f32", ptr(opt._chunks), ptr(opt._table), ptr(self._offs), opt.nchunk, ptr(self.recv), self.world,
+                   self.N, ptr(self.acc), self.P, int(bool(first)), int(bool(last)), stream(dev))
+
+    def reduce(self, losses=(), first=True, last=True):
+        """one micro-batch: pack and zero, all-gather, rank-sum"""
+        from .parallel import all_gather_flat
+        self.pack(losses, zero=True)
+        all_gather_flat(self.flat, self.recv, self.group)
+        self.rank_sum(first, last)
+
+    def losses(self):
+        """the losses summed so far, one 0-dim device tensor per loss of the last call"""
+        return [self.acc[self.P + u].clone() for u in range(self.n_losses)]
+
+
 # ---- the loop body -----------------------------------------------------------------------------------------------------------------
 def train_step(diffusion_or_fn, opt, batch, t=None, noise=None, slice_seeds=None, step=0, schedule=None, objective="pred_res",
-               loss_type="l1", normalize=True):
+               loss_type="l1", normalize=True, reducer=None):
     """The loop body of Trainer.train (src/DADiff.py:1689-1725) for one accumulation group: p_losses -> backward per loss ->
     opt.step() (clip, Adam, zero_grad, EMA).  diffusion_or_fn: an object with the reference's ResidualDiffusion attributes, or a
     free model_fn(x_in, [time0, time1]) -> list of (B, 1, H, W) together with schedule, objective and loss_type.  batch:
@@ -963,10 +1068,17 @@ def train_step(diffusion_or_fn, opt, batch, t=None, noise=None, slice_seeds=None
     micro-batches of gradient_accumulate_every, each loss scaled by one over their number.  A micro-batch may also be a StoreBatch
     (one, or a list of them), whose t and slice_seeds may stay on the host.  t, noise and slice_seeds belong to the
     micro-batch (lists of them for several); t defaults to torch.randint(0, T, (B,)) as the reference draws it.  `step` keys the
-    noise together with slice_seeds.  Returns the losses, one device tensor per U-Net, summed over the micro-batches."""
+    noise together with slice_seeds.  Returns the losses, one device tensor per U-Net, summed over the micro-batches.
+    reducer (a GradReducer over opt; None: a single process, the path above): data-parallel training.  `batch` then holds this
+    rank's micro-batches of the step, the a-th of them being global micro-batch a W + rank of len(batch) W (dp_micro: the caller
+    draws its indices, t and seeds under that number); each loss is scaled by one over len(batch) W, and reducer.reduce() follows
+    every micro-batch's backward passes.  The gradients opt.step() sees and the losses returned are then, on every rank, bit for
+    bit those of a single process over all len(batch) W micro-batches."""
     fn = "train_step"
     if not isinstance(opt, ClipAdamEMA):
         raise RuntimeError(f"{fn}: opt must be a ClipAdamEMA (got {type(opt).__name__})")
+    if reducer is not None and (not isinstance(reducer, GradReducer) or reducer.opt is not opt):
+        raise RuntimeError(f"{fn}: reducer must be a GradReducer over opt (got {type(reducer).__name__})")
     single = isinstance(batch, StoreBatch)
     if single:
         batch = [batch]
@@ -990,6 +1102,7 @@ def train_step(diffusion_or_fn, opt, batch, t=None, noise=None, slice_seeds=None
         return None if v is None else v[i]
 
     total = None
+    n_micro = len(groups) * (1 if reducer is None else reducer.world)
     for i, imgs in enumerate(groups):
         ti = pick(t, i)
         if ti is None and isinstance(imgs, StoreBatch):
@@ -999,10 +1112,13 @@ def train_step(diffusion_or_fn, opt, batch, t=None, noise=None, slice_seeds=None
                 raise RuntimeError(f"{fn}: a micro-batch must be [x_start, x_input] on the GPU (there is no CPU path)")
             ti = torch.randint(0, ac.numel(), (imgs[0].shape[0],), device=imgs[0].device).long()
         losses = p_losses_fn(model_fn, imgs, ti, schedule, objective, loss_type, pick(noise, i), pick(slice_seeds, i), step,
-                             1.0 / len(groups), normalize)
+                             1.0 / n_micro, normalize)
         for loss in losses:
             loss.backward()
         det = [loss.detach() for loss in losses]
+        if reducer is not None:
+            reducer.reduce(det, first=i == 0, last=i == len(groups) - 1)
+            continue
         total = det if total is None else [a + b for a, b in zip(total, det)]
     opt.step()
-    return total
+    return total if reducer is None else reducer.losses()

@@ -3,6 +3,10 @@ its own x_input / x_T / noise, src/DADiff.py:1276-1365; GroupNorm / LayerNorm ar
 the RN50 BatchNorm runs in eval mode), so a volume shards over ranks by slice index with NO
 collective on the data path.  The only exchange is one all-gather (RCCL over xGMI on GPUs,
 gloo in the CPU tests) that reassembles the output volume.
+
+Data-parallel training (Trainer(data_parallel=True)) exchanges more: all_gather_flat gathers every rank's flat gradient buffer
+once per micro-batch, for diffusion_train.GradReducer to add the rows in rank order; broadcast_tensors and gather_int64 carry
+rank 0's model at set-up and the replicas' fingerprints.
 """
 import torch
 
@@ -83,3 +87,73 @@ def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampl
         outs.append(diffusion.sample([x], batch_size=e - s, noise=nz, slice_seeds=seeds, **(sampler_kwargs or {}))[-1])
     local = torch.cat(outs, 0) if outs else ldct.new_zeros((0,) + tuple(ldct.shape[1:])).to(dev)
     return gather_volume(local, world, n)
+
+
+# ---- data-parallel training: the exchanges of diffusion_train.GradReducer and of Trainer(data_parallel=True) ----------------------
+_STAGE = {}      # (dtype, numel, world) -> (pinned send buffer, pinned receive buffer): the host staging of a non-nccl group
+
+
+def _backend(group):
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        raise RuntimeError("parallel: torch.distributed is not initialised (call init_process_group first)")
+    return dist.get_backend(group)
+
+
+def all_gather_flat(flat, out, group=None):
+    """out[r] = rank r's `flat`, on every rank: flat (N,) and out (W, N) dense, of one dtype and on one device, W the size of
+    `group` (None: the default group).  On an nccl group this is dist.all_gather_into_tensor on the device buffers (RCCL).  On
+    any other backend (gloo) device buffers are staged through pinned host memory -- down, all_gather, up, each waited for --
+    and host buffers are gathered as they are.  Rows arrive in rank order whatever the backend: what a receiver does with them
+    (diffusion_train's ordered sum) does not depend on how they travelled.  Returns out."""
+    import torch.distributed as dist
+    fn = "all_gather_flat"
+    backend = _backend(group)
+    W = dist.get_world_size(group)
+    if not isinstance(flat, torch.Tensor) or not isinstance(out, torch.Tensor):
+        raise RuntimeError(f"{fn}: flat and out must be tensors (got {type(flat).__name__}, {type(out).__name__})")
+    if flat.dim() != 1 or tuple(out.shape) != (W, flat.numel()) or flat.dtype != out.dtype or flat.device != out.device or \
+            not flat.is_contiguous() or not out.is_contiguous():
+        raise RuntimeError(f"{fn}: inconsistent arguments flat{tuple(flat.shape)} {flat.dtype} on {flat.device}, out"
+                           f"{tuple(out.shape)} {out.dtype} on {out.device} (flat (N,), out ({W}, N), dense, one dtype and device)")
+    if backend == "nccl":
+        if not flat.is_cuda:
+            raise RuntimeError(f"{fn}: an nccl group gathers device buffers (flat lives on {flat.device})")
+        dist.all_gather_into_tensor(out.view(-1), flat, group=group)
+        return out
+    if not flat.is_cuda:
+        dist.all_gather([out[r] for r in range(W)], flat, group=group)
+        return out
+    key = (flat.dtype, flat.numel(), W)
+    if key not in _STAGE:
+        _STAGE[key] = (torch.empty(flat.numel(), dtype=flat.dtype).pin_memory(),
+                       torch.empty(W, flat.numel(), dtype=flat.dtype).pin_memory())
+    send, recv = _STAGE[key]
+    send.copy_(flat)                                   # waits for the stream: the buffer is whole before it travels
+    dist.all_gather([recv[r] for r in range(W)], send, group=group)
+    out.copy_(recv)                                    # a blocking copy: recv is free again when this returns
+    return out
+
+
+def broadcast_tensors(tensors, src=0, group=None):
+    """every tensor of `tensors` takes rank `src`'s values, in place: on the device over nccl, through the host otherwise"""
+    import torch.distributed as dist
+    backend = _backend(group)
+    with torch.no_grad():
+        for t in tensors:
+            if backend == "nccl" or not t.is_cuda:
+                dist.broadcast(t, src, group=group)
+            else:
+                h = t.detach().cpu()
+                dist.broadcast(h, src, group=group)
+                t.copy_(h)
+
+
+def gather_int64(value, device, group=None):
+    """[rank 0's value, rank 1's, ...] of one int64 per rank, on every rank (all_gather_flat on `device` for nccl, on the host
+    otherwise)"""
+    import torch.distributed as dist
+    W = dist.get_world_size(group)
+    dev = device if _backend(group) == "nccl" else torch.device("cpu")
+    mine = torch.tensor([int(value)], dtype=torch.int64, device=dev)
+    return all_gather_flat(mine, torch.empty(W, 1, dtype=torch.int64, device=dev), group).view(-1).cpu().tolist()

@@ -755,6 +755,22 @@ int fd_opt_radam_ema_f32(const int64_t *chunks, const int64_t *tensors, const in
                          double lr, double beta1, double beta2, double eps, int ema_mode, double ema_decay, int zero_grad,
                          int skip_nonfinite, void *stream);
 
+/* ---- the gradient sum of data-parallel training (fd_grad_sum.hip; diffusion_train.GradReducer) -----------------
+ * fp32, the same in both builds of the library.  Deterministic: plain adds in rank order, no fmaf, no atomics.  Both work over the
+ * optimiser's tables above (chunks, tensors) and offs [nt] int64: tensor i lives at [offs[i], offs[i] + numel_i) of a flat buffer,
+ * offs = cumsum(numel rounded up to 4), P their total; a flat buffer has N = P + fd_grads_tail_floats() floats, the tail behind the
+ * gradients.  Flat buffers are 16-byte aligned; the gradient side takes 16-byte accesses where the tensor's flag allows.
+ * fd_grads_pack_f32: flat[offs[i] + k] = g_i[k] (zeros for a tensor without a gradient, zeros in the padding), flat[P + e] =
+ *   tail[e] for e < ntail and 0 behind; with `zero`, every g read is then set to 0.
+ * fd_grads_rank_sum_f32: recv [W][N], acc [N]; per element v = first ? 0 : acc[i], then v = v + recv[r][i] for r = 0 .. W - 1 in
+ *   that order (W <= 64).  If `last`, v goes to the gradient of every tensor that has one (the others are not touched), otherwise
+ *   to acc.  The tail's sum always goes to acc[P ..]. */
+int fd_grads_tail_floats(void);
+int fd_grads_pack_f32(const int64_t *chunks, const int64_t *tensors, const int64_t *offs, int nchunk, float *flat, int64_t P,
+                      const float *tail, int ntail, int zero, void *stream);
+int fd_grads_rank_sum_f32(const int64_t *chunks, const int64_t *tensors, const int64_t *offs, int nchunk, const float *recv, int W,
+                          int64_t N, float *acc, int64_t P, int first, int last, void *stream);
+
 /* ---- what a held-out evaluation reads off a model output (fd_validate.hip) -------------------------------------
  * fd_val_items_f32: items [B][2], from one pass over pred, target (and x_input, x_start) [B][npix] and two small sums, without
  *   a gradient.  items[b][0] = mean_i(|pred - target| or (pred - target)^2) (loss_type 1 = l1, 2 = l2): its mean over b is the
