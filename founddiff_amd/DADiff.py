@@ -526,8 +526,8 @@ class ResidualDiffusion(nn.Module):
     def _hs(self):
         if self._host_sched is None:
             self._host_sched = {k: getattr(self, k).detach().cpu() for k in
-                                ("alphas_cumsum", "betas_cumsum", "posterior_mean_coef1", "posterior_mean_coef2",
-                                 "posterior_mean_coef3", "posterior_log_variance_clipped")}
+                                ("alphas_cumsum", "betas_cumsum", "one_minus_alphas_cumsum", "posterior_mean_coef1",
+                                 "posterior_mean_coef2", "posterior_mean_coef3", "posterior_log_variance_clipped")}
         return self._host_sched
 
     def _eng(self):
@@ -558,9 +558,68 @@ class ResidualDiffusion(nn.Module):
     def _is_shipped(self):
         return self._plan() == (0, True, False, 0) and not self.input_condition
 
+    def _captured_plan(self):
+        """Every plan of _plan() samples on captured loops and device tables unless the model takes a third input plane."""
+        return not self.input_condition
+
+    def _obj_loop(self, last, step_noise):
+        """Does this call of a plan other than the shipped one run on the captured loops (_obj_ddim / _obj_ancestral)?  The
+        eager _generic_loop keeps trajectories (last=False), a step_noise callable and the 3-plane models."""
+        return bool(last) and step_noise is None and self._captured_plan() and not self._is_shipped()
+
+    def _group_rows(self):
+        """Slices per consecutive group of sample(): streams x max_sub_batch, halved for a plan that runs two engines per stream
+        (each then holds max_sub_batch // 2 slices, so a call's workspace stays what max_sub_batch promises) and kept a
+        multiple of `streams`."""
+        grp = self.streams * self.max_sub_batch
+        _, r0, r1, _ = self._plan()
+        if r0 and r1:
+            grp //= 2
+            grp = max(grp - grp % self.streams, self.streams)
+        return grp
+
     def _engines(self):
+        """The engines of this plan's U-Nets in the slot of the running sub-batch (slot 0 outside _sample_concurrent)."""
         mode, r0, r1, _ = self._plan()
-        return ([self.model.unet0.engine()] if r0 else []) + ([self.model.unet1.engine()] if r1 else [])
+        return ([self.model.unet0.engine(slot=self._slot)] if r0 else []) + ([self.model.unet1.engine(slot=self._slot)] if r1 else [])
+
+    # ---- the step tables of the captured loops of every plan: pure host functions of the schedule (tests/test_obj_loop_cpu.py)
+    def _obj_time_tables(self):
+        """(times0, times1): (T,) fp32 CPU tables of the two U-Nets' time inputs, or None where the plan does not run that U-Net --
+        entry t is what _outputs feeds at step t."""
+        _, r0, r1, tsel0 = self._plan()
+        hs, T = self._hs(), self.num_timesteps
+        t0 = ((hs["alphas_cumsum"] if tsel0 == 0 else hs["betas_cumsum"]) * T).float().contiguous() if r0 else None
+        t1 = (hs["betas_cumsum"] * T).float().contiguous() if r1 else None
+        return t0, t1
+
+    def _obj_anc_table(self):
+        """(T, 8) fp32 CPU: row t = {ac, bc, omac, c1, c2, c3, logvar, 0}, the row _par builds for p_sample at step t."""
+        hs = self._hs()
+        cols = [hs[k].float() for k in ("alphas_cumsum", "betas_cumsum", "one_minus_alphas_cumsum", "posterior_mean_coef1",
+                                         "posterior_mean_coef2", "posterior_mean_coef3", "posterior_log_variance_clipped")]
+        return torch.stack(cols + [torch.zeros_like(cols[0])], 1).contiguous()
+
+    def _ddim_pairs(self):
+        times = list(reversed(torch.linspace(-1, self.num_timesteps - 1, steps=self.sampling_timesteps + 1).int().tolist()))
+        return list(zip(times[:-1], times[1:]))
+
+    def _obj_ddim_table(self, B):
+        """((S, B, 8) parameter rows, (S, B) time inputs of unet0 or None, of unet1 or None), fp32 CPU: step i of the DDIM loop as
+        _generic_loop runs it -- {ac, bc, omac, alpha, 0, 0, 0, last} of _par and the time inputs of _outputs."""
+        hs = self._hs()
+        acs = hs["alphas_cumsum"]
+        t0, t1 = self._obj_time_tables()
+        pairs = self._ddim_pairs()
+        par = torch.zeros(len(pairs), B, 8, dtype=torch.float32)
+        for i, (time, time_next) in enumerate(pairs):
+            lastf = time_next < 0
+            par[i, :, 0], par[i, :, 1], par[i, :, 2] = acs[time], hs["betas_cumsum"][time], hs["one_minus_alphas_cumsum"][time]
+            par[i, :, 3] = 0.0 if lastf else float(acs[time] - acs[time_next])
+            par[i, :, 7] = float(lastf)
+        idx = torch.tensor([t for t, _ in pairs], dtype=torch.long)
+        rows = lambda tab: None if tab is None else tab[idx][:, None].expand(len(pairs), B).contiguous()
+        return par.contiguous(), rows(t0), rows(t1)
 
     def _encode_all(self, x_in, cond=None):
         """The conditioning of every engine in use: the tower on x_in, or the preset rows `cond` -- one (prompt_emb, local_all)
@@ -822,11 +881,17 @@ class ResidualDiffusion(nn.Module):
         tests feed the reference's noise this way; one eager step at a time).  Without `step_noise` the step noise is
         the per-slice keyed stream of fd_sched.hip -- a function of (slice_seeds[b], t, pixel) only, so a slice's
         result does not depend on its batch, rank or stream -- and the loop runs from device tables: chunks of steps
-        are captured in a HIP graph and replayed (no host work per step)."""
+        are captured in a HIP graph and replayed (no host work per step).  That holds for every plan of _plan() -- the other
+        objectives and the two-U-Net model run _obj_ancestral: fd_obj_begin, one forward per U-Net, fd_res_step_obj_keyed --
+        when last=True.  Trajectories (last=False) of those plans, a `step_noise` callable and the 3-plane input_condition
+        models run the eager _generic_loop, whose step noise without `step_noise` is torch.randn on the device."""
         if self.input_condition:
             self._set_cond2(x_input[1])
         x_input = x_input[0].contiguous().float()
         if not self._is_shipped():
+            if self._obj_loop(last, step_noise):
+                noise, seeds = self._noise_and_seeds("loop", shape, x_input.device, noise, slice_seeds)
+                return self._obj_ancestral(x_input, shape, noise, seeds, _cond)
             return self._generic_loop(x_input, shape, last, noise, step_noise, ddim=False, cond=_cond)
         x_in, img, mo, time_buf = self._loop_buffers(x_input, shape)
         eng = self._eng()
@@ -939,6 +1004,8 @@ class ResidualDiffusion(nn.Module):
             self._set_cond2(x_input[1])
         x_input = x_input[0].contiguous().float()
         if not self._is_shipped():
+            if self._obj_loop(last, None):
+                return self._obj_ddim(x_input, shape, noise, _cond)
             return self._generic_loop(x_input, shape, last, noise, None, ddim=True, cond=_cond)
         x_in, img, mo, time_buf = self._loop_buffers(x_input, shape)
         eng = self._eng()
@@ -1012,9 +1079,140 @@ class ResidualDiffusion(nn.Module):
             run_steps(lambda e: self._step_forward(x_in, img, time_buf, mo, e, tail_of=None if e is eng else eng))
         return self._finish(input_add_noise, img, img_list, last)
 
+    # ---- the captured loops of every plan other than the shipped one
+    def _obj_buffers(self, x_input, shape, cond):
+        """The persistent loop buffers of this plan on the engines of the running slot, x_in loaded and the conditioning of every
+        engine in place: (engines, mode, x_in, img, (o0, o1) as the step kernels take them, ((engine, time buffer, output buffer)
+        of unet0, the same of unet1)) -- None where the plan does not run that U-Net."""
+        mode, r0, r1, _ = self._plan()
+        engines = self._engines()
+        own = engines[0]                                          # holds what the U-Nets share, and the loop's graph
+        x_in = own._b("obj_xin", shape, torch.float32)
+        x_in.copy_(x_input)
+        img = own._b("obj_img", shape, torch.float32)
+        self._encode_all(x_in, cond)
+        e0 = engines[0] if r0 else None
+        e1 = engines[-1] if r1 else None
+        out0 = e0._b("obj_out", shape, torch.float32) if e0 else None
+        out1 = e1._b("obj_out", shape, torch.float32) if e1 else None
+        tb0 = e0._b("obj_time", (shape[0],), torch.float32) if e0 else None
+        tb1 = e1._b("obj_time", (shape[0],), torch.float32) if e1 else None
+        # the single U-Net of 'pred_noise' predicts the noise: its output is the kernels' o1
+        outs = (None, out0) if (mode == 1 and r0) else (out0, out1)
+        return engines, mode, x_in, img, outs, ((e0, tb0, out0), (e1, tb1, out1))
+
+    def _obj_key(self, engines, shape):
+        return (tuple(shape), self._plan(), self.num_timesteps) + tuple((e.mode, e.gen) for e in engines)
+
+    def _obj_ddim(self, x_input, shape, noise, cond=None):
+        """ddim_sample(last=True) of a plan other than the shipped one: per step one forward per U-Net of the plan, one after the
+        other on the same stream, into its own output buffer, and fd_res_step_obj(step = 1) in place on img; the S x B parameter
+        rows and time inputs are uploaded before the loop.  use_graph: the whole loop is ONE graph of the plan's first engine
+        (kind "obj_ddim"); otherwise the same launches run eagerly -- the same bits, and those of _generic_loop's last image."""
+        engines, mode, x_in, img, (o0, o1), nets = self._obj_buffers(x_input, shape, cond)
+        own = engines[0]
+        B, S = shape[0], self.sampling_timesteps
+        npix = img[0].numel()
+        par, tt0, tt1 = self._obj_ddim_table(B)
+        gpar = own._b("obj_ddim_par", (S, B, 8), torch.float32)
+        gpar.copy_(par)
+        tabs = []
+        for (e, _, out), tt in zip(nets, (tt0, tt1)):
+            if e is not None:
+                gt = e._b("obj_ddim_time", (S, B), torch.float32)
+                gt.copy_(tt)
+                tabs.append((e, gt, out))
+        if noise is None:
+            noise = torch.randn(shape, device=x_in.device)
+        input_add_noise = self._x_T(x_in, noise, img)
+
+        def run():
+            for i in range(S):
+                for e, gt, out in tabs:
+                    e.forward(img, x_in, gt[i], out=out)
+                L.call("fd_res_step_obj", mode, 1, _p(o0), _p(o1), _p(img), _p(x_in), None, _p(gpar[i]), None, None, None,
+                       _p(img), B, npix, _stream(img))
+
+        if self.use_graph:
+            def warm():
+                for e, gt, out in tabs:
+                    e.forward(img, x_in, gt[0], out=out)
+
+            def record(capture):
+                start = img.clone()
+                g = capture(run)
+                img.copy_(start)                                   # capture does not execute: restore x_T
+                return g
+            own.captured("obj_ddim", self._obj_key(engines, shape) + (S,), warm, record).replay()
+        else:
+            run()
+        return self._finish(input_add_noise, img, [], True)
+
+    def _obj_ancestral(self, x_input, shape, noise, seeds, cond=None):
+        """p_sample_loop(last=True) of a plan other than the shipped one, step noise keyed by `seeds`: T steps of fd_obj_begin
+        (t <- t - 1 on the device, both time inputs) -> one forward per U-Net of the plan, one after the other on the same stream
+        -> fd_res_step_obj_keyed (row t of the (T, 8) table, keyed noise, in place on img).  use_graph: replays of one captured
+        chunk of G steps (kind "obj_anc", _ancestral_keyed's rule for G); otherwise the same three launches eagerly, one step at
+        a time -- the same bits.  There is no precision tail: _anc_max_chunks simply stops after that many chunks."""
+        engines, mode, x_in, img, (o0, o1), nets = self._obj_buffers(x_input, shape, cond)
+        own = engines[0]
+        T, B = self.num_timesteps, shape[0]
+        npix = img[0].numel()
+        t_dev = own._b("obj_t", (1,), torch.int32)
+        gpar, gse = own._b("obj_anc_par", (T, 8), torch.float32), own._b("obj_seeds", (B,), torch.int64)
+        gpar.copy_(self._obj_anc_table())
+        gse.copy_(seeds)
+        runs, gts = [], [None, None]
+        for i, ((e, tb, out), tt) in enumerate(zip(nets, self._obj_time_tables())):
+            if e is not None:
+                gts[i] = e._b("obj_anc_time", (T,), torch.float32)
+                gts[i].copy_(tt)
+                tb.zero_()
+                runs.append((e, tb, out))
+        (_, tb0, _), (_, tb1, _) = nets
+        gt0, gt1 = gts
+        input_add_noise = self._x_T(x_in, noise, img)
+        t_dev.fill_(T)
+
+        def one():
+            L.call("fd_obj_begin", _p(t_dev), _p(gt0), _p(gt1), _p(tb0), _p(tb1), B, T, _stream(img))
+            for e, tb, out in runs:
+                e.forward(img, x_in, tb, out=out)
+            L.call("fd_res_step_obj_keyed", mode, _p(o0), _p(o1), _p(img), _p(x_in), _p(gpar), _p(t_dev), _p(gse), _p(img),
+                   B, npix, T, _stream(img))
+
+        G = max([g for g in range(8, 65) if T % g == 0] or [40])
+        reps, rem = T // G, T % G
+        lim = getattr(self, "_anc_max_chunks", None)
+        if lim:
+            reps, rem = min(reps, int(lim)), 0
+        if self.use_graph:
+            def warm():
+                for e, tb, out in runs:
+                    e.forward(img, x_in, tb, out=out)
+
+            def record(capture):
+                start, t0 = img.clone(), t_dev.clone()
+                g = capture(lambda: [one() for _ in range(G)])
+                img.copy_(start)                                  # capture does not execute: restore x_T and the step counter
+                t_dev.copy_(t0)
+                return g
+            gm = own.captured("obj_anc", self._obj_key(engines, shape) + (G,), warm, record) if reps > 0 else None
+            for _ in range(rem):
+                one()
+            for _ in range(reps):
+                gm.replay()
+        else:
+            for _ in range(rem + reps * G):
+                one()
+        self._anc_steps_run = rem + reps * G
+        return self._finish(input_add_noise, img, [], True)
+
     def _generic_loop(self, x_in, shape, last, noise, step_noise, ddim, cond=None):
-        """p_sample_loop / ddim_sample for the objectives other than 'pred_res' and for the dual-UNet
-        model: eager UNet forwards (one or two per step) + one fd_res_step_obj launch per step."""
+        """The eager form of p_sample_loop / ddim_sample for the plans other than the shipped one: eager UNet forwards (one or two
+        per step, slot 0's engines) + one fd_res_step_obj launch per step, torch.randn step noise unless `step_noise` gives it.
+        It serves what the captured loops (_obj_ddim / _obj_ancestral) do not: trajectories (last=False), a step_noise callable
+        (the parity tests feed the reference's noise this way) and the 3-plane input_condition models."""
         self._encode_all(x_in, cond)
         B = shape[0]
         if noise is None:
@@ -1123,13 +1321,12 @@ class ResidualDiffusion(nn.Module):
                 L.call("fd_rows_repeat_f32", _p(e.local_all), _p(la[c0 * K:]), nb, K, e.loc_total, s)
         samples = torch.empty((B, K) + tuple(x01.shape[1:]), device=x01.device, dtype=torch.float32)
         flat = samples.view((R,) + tuple(x01.shape[1:]))
-        keyed_steps = not self._is_shipped() and not self.is_ddim_sampling      # _generic_loop's ancestral steps draw from torch
-        for lo, hi in ensemble_passes(B, K, self.streams * self.max_sub_batch):
+        # every plan's ancestral steps take the keyed stream of `sd` inside its captured loop: no step_noise callable
+        for lo, hi in ensemble_passes(B, K, self._group_rows()):
             sl = slice(lo, hi)
             size = (hi - lo,) + tuple(x01.shape[1:])
             sd = seeds[sl].contiguous()
-            step_noise = (lambda t, sd=sd, size=size: self._keyed_noise(sd, t, size)) if keyed_steps else None
-            out = self._sample([x_rows[sl]], hi - lo, True, self._keyed_noise(sd, self.X_T_STEP, size), step_noise, sd,
+            out = self._sample([x_rows[sl]], hi - lo, True, self._keyed_noise(sd, self.X_T_STEP, size), None, sd,
                                cond=self._cond_rows(cond, sl))
             flat[sl].copy_(out[-1])
         return samples
@@ -1160,7 +1357,8 @@ class ResidualDiffusion(nn.Module):
         sample() under the seed tiling.tile_seeds(slice_seeds, my * mx)[b, iy * mx + ix] (tile 0 keeps the slice's seed: a one-tile
         plan is sample() of the slice under that x_T); the rows run slice-major in passes of at most streams x max_sub_batch
         through the paths of sample().  The ancestral sampler's STEP noise is the keyed stream of the tile's own seed (the
-        graph-captured loop), so overlapping tiles see different step noise in their common pixels and the blend averages them.
+        graph-captured loop of every plan, the two-U-Net and pred_noise models included), so overlapping tiles see different step
+        noise in their common pixels and the blend averages them.
         The final image is the weighted mean of the tiles' final images, weights tiling.tile_weights (fd_tiles_blend_f32): a
         pixel under one tile is that tile's value bit for bit.  Nothing returned depends on B or on the cut into passes.
         condition="tile": the DA-CLIP tower runs on every tile, which is what crop training saw.  "slice": it runs once per slice
@@ -1248,14 +1446,11 @@ class ResidualDiffusion(nn.Module):
         else:
             x_rows = self._tile_gather(x01, plan)                  # plain rows of _sample, which normalises them itself
         tiles = torch.empty((R, 1, th, tw), device=x01.device, dtype=torch.float32)
-        keyed_steps = not self._is_shipped() and not self.is_ddim_sampling      # _generic_loop's ancestral steps draw from torch
-        for lo, hi in tile_passes(B, my, mx, self.streams * self.max_sub_batch, self.streams):
+        for lo, hi in tile_passes(B, my, mx, self._group_rows(), self.streams):
             sl = slice(lo, hi)
-            size = (hi - lo, 1, th, tw)
             sd = seeds[sl].contiguous()
-            step_noise = (lambda t, sd=sd, size=size: self._keyed_noise(sd, t, size)) if keyed_steps else None
             pre = {} if cond is None else {"cond": self._cond_rows(cond, sl)}
-            out = self._sample([x_rows[sl]], hi - lo, True, nz_rows[sl], step_noise, sd, **pre)
+            out = self._sample([x_rows[sl]], hi - lo, True, nz_rows[sl], None, sd, **pre)
             tiles[sl].copy_(out[-1])
         return tiles
 
@@ -1267,8 +1462,9 @@ class ResidualDiffusion(nn.Module):
         # twice that in the fp32 modes) and a sample() keeps `streams` engines plus their tail engines alive.  Batches beyond
         # streams x max_sub_batch slices run as consecutive groups of that size on the same engines: a slice's result does not
         # depend on its batch, so the output is the same bits; the workspace stays that of one group whatever the batch.
-        grp = self.streams * self.max_sub_batch
-        if (self._is_shipped() and last and step_noise is None and not self.input_condition and x_input[0].shape[0] > grp
+        # A plan with two engines per stream halves the group (_group_rows): each engine then holds max_sub_batch // 2 slices.
+        grp = self._group_rows()
+        if (self._captured_plan() and last and step_noise is None and x_input[0].shape[0] > grp
                 and x_input[0].shape[0] % self.streams == 0):
             dev = x_input[0].device
             batch_size = x_input[0].shape[0]
@@ -1288,7 +1484,10 @@ class ResidualDiffusion(nn.Module):
         batch_size, channels, h, w = x_input[0].shape
         size = (batch_size, channels, h, w)
         # two concurrent sub-batches: DDIM, and the ancestral sampler when its step noise is the keyed stream
-        nsl = self.streams if (self._is_shipped() and last and batch_size >= 8 and batch_size % self.streams == 0 and
+        # (a two-engine plan also goes there with fewer than 8 slices when one engine could not hold them within its half of
+        # max_sub_batch: the groups of a split of such a plan are that small when max_sub_batch is)
+        big = batch_size >= 8 or (self._group_rows() < self.streams * self.max_sub_batch and batch_size > self.max_sub_batch // 2)
+        nsl = self.streams if (self._captured_plan() and last and big and batch_size % self.streams == 0 and
                                (self.is_ddim_sampling or step_noise is None)) else 1
         path = "concurrent" if nsl > 1 else "ddim" if self.is_ddim_sampling else "ancestral"
         noise, seeds = self._noise_and_seeds(path, size, x_input[0].device, noise, slice_seeds)

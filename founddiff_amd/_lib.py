@@ -157,6 +157,8 @@ SIGNATURES = {
     "fd_keyed_normal": (i32, [vp, i32, vp, i32, i64, vp]),
     "fd_ancestral_begin": (i32, [vp, vp, vp, i32, vp]),
     "fd_res_posterior_step_keyed": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, vp]),
+    "fd_obj_begin": (i32, [vp, vp, vp, vp, vp, i32, i32, vp]),
+    "fd_res_step_obj_keyed": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp]),
     "fd_gn_film_silu_apply": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, i64, i32, i32, vp]),
     "fd_chan_ln": (i32, [i32, vp, vp, vp, vp, i64, i32, vp]),
     "fd_linear_attention": (i32, [i32, vp, i32, i64, i32, vp, vp, vp, vp, i32, vp]),

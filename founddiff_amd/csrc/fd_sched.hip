@@ -68,6 +68,95 @@ __global__ void res_posterior_keyed_kernel(const float *__restrict__ mo, const f
     }
 }
 
+// The objective-general twins (src/DADiff.py:1168-1207 + 1142-1151, 1226-1229): every objective of model_predictions and the
+// two-U-Net model, one or two U-Net time inputs per step, the eight step parameters from ONE device table row.
+
+// start of a step: t <- max(t - 1, 0) (held below T), time0[b] <- times0[t], time1[b] <- times1[t]; a NULL output is not written
+__global__ void obj_begin_kernel(int *t_dev, const float *__restrict__ times0, const float *__restrict__ times1,
+                                 float *__restrict__ time0, float *__restrict__ time1, int B, int T) {
+    const int t = min(max(*t_dev - 1, 0), T - 1);
+    __syncthreads();
+    if (threadIdx.x == 0) *t_dev = t;
+    if (time0) {
+        const float v = times0[t];
+        for (int b = threadIdx.x; b < B; b += blockDim.x) time0[b] = v;
+    }
+    if (time1) {
+        const float v = times1[t];
+        for (int b = threadIdx.x; b < B; b += blockDim.x) time1[b] = v;
+    }
+}
+
+struct obj_row { float a, bb, oma, c1, c2, c3, sd; };
+
+// one pixel: predictions of res_step_obj_kernel's `mode`, then its step == 2 update.  The fused multiply-adds are written out and
+// the compiler forms none of its own: the 16-byte and the one-pixel form of the kernel round alike, so a slice's bits do not depend
+// on the alignment of its buffers.
+template <int MODE>
+__device__ __forceinline__ float obj_pixel(const obj_row &r, float o0, float o1, float x, float xi, float z) {
+#pragma clang fp contract(off)
+    float pr, xs;
+    if (MODE == 0) {
+        pr = clamp1s(o0);
+        xs = clamp1s(xi - pr);
+    } else if (MODE == 1) {
+        xs = clamp1s(fmaf(-r.bb, o1, fmaf(-r.a, xi, x)) / r.oma);
+        pr = clamp1s(xi - xs);
+    } else if (MODE == 2) {
+        pr = clamp1s(o0);
+        xs = clamp1s(fmaf(-r.bb, o1, fmaf(-r.a, pr, x)));
+    } else {
+        pr = clamp1s(xi - o0);
+        xs = clamp1s(o0);
+    }
+    return fmaf(r.sd, z, fmaf(r.c3, xs, fmaf(r.c2, pr, r.c1 * x)));
+}
+
+// xt / out may be the same buffer: no __restrict__ on them; a thread reads its four pixels before it writes them.  A mode reads
+// only the streams its formulas name (modes 0, 3: no o1 -- the update takes no predicted noise --, mode 1: no o0, mode 2: no
+// x_in).  VEC: npix % 4 == 0 and every pointer 16-byte aligned -- one 16-byte access per stream and group; otherwise the same
+// pixels per lane, one at a time, ragged last group.
+template <int MODE, bool VEC>
+__global__ void res_step_obj_keyed_kernel(const float *__restrict__ o0, const float *__restrict__ o1, const float *xt,
+                                          const float *__restrict__ xin, const float *__restrict__ par_table,
+                                          const int *__restrict__ t_dev, const int64_t *__restrict__ seeds, float *out,
+                                          int64_t npix, int T) {
+    constexpr bool R0 = MODE != 1, R1 = MODE == 1 || MODE == 2, RI = MODE != 2;
+    const int b = blockIdx.y;
+    const int t = min(max(*t_dev, 0), T - 1);
+    const float *p = par_table + (int64_t)t * 8;
+    obj_row r;
+    r.a = p[0]; r.bb = p[1]; r.oma = p[2]; r.c1 = p[3]; r.c2 = p[4]; r.c3 = p[5];
+    r.sd = t > 0 ? expf(0.5f * p[6]) : 0.f;                                  // no noise at t = 0 (src/DADiff.py:1228)
+    const uint64_t seed = (uint64_t)seeds[b];
+    const int64_t ng = (npix + 3) / 4, base = (int64_t)b * npix;
+    for (int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; g < ng; g += (int64_t)gridDim.x * blockDim.x) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (t > 0) keyed_normal4(seed, (uint32_t)t, (uint32_t)g, z);
+        const int64_t j = base + 4 * g;
+        if (VEC) {
+            const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 v0 = R0 ? *reinterpret_cast<const float4 *>(o0 + j) : zero;
+            const float4 v1 = R1 ? *reinterpret_cast<const float4 *>(o1 + j) : zero;
+            const float4 vx = *reinterpret_cast<const float4 *>(xt + j);
+            const float4 vi = RI ? *reinterpret_cast<const float4 *>(xin + j) : zero;
+            float4 w;
+            w.x = obj_pixel<MODE>(r, v0.x, v1.x, vx.x, vi.x, z[0]);
+            w.y = obj_pixel<MODE>(r, v0.y, v1.y, vx.y, vi.y, z[1]);
+            w.z = obj_pixel<MODE>(r, v0.z, v1.z, vx.z, vi.z, z[2]);
+            w.w = obj_pixel<MODE>(r, v0.w, v1.w, vx.w, vi.w, z[3]);
+            *reinterpret_cast<float4 *>(out + j) = w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (4 * g + e < npix)
+                    out[j + e] = obj_pixel<MODE>(r, R0 ? o0[j + e] : 0.f, R1 ? o1[j + e] : 0.f, xt[j + e], RI ? xin[j + e] : 0.f, z[e]);
+        }
+    }
+}
+
+inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
 inline int g4(int64_t npix) { int64_t b = ((npix + 3) / 4 + 255) / 256; return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b)); }
 
 }  // namespace
@@ -94,5 +183,47 @@ extern "C" int fd_res_posterior_step_keyed(const float *model_out, const float *
     hipLaunchKernelGGL(res_posterior_keyed_kernel, dim3(g4(npix), B), dim3(256), 0, (hipStream_t)stream, model_out, x_t,
                        x_in, coef_table, t_dev, seeds, img_out, x_start_out, npix);
     FD_LAUNCH_OK("fd_res_posterior_step_keyed");
+    return FD_OK;
+}
+
+extern "C" int fd_obj_begin(int *t_dev, const float *times0, const float *times1, float *time0, float *time1, int B, int T,
+                            void *stream) {
+    FD_REQUIRE(t_dev && B > 0 && T > 0, "fd_obj_begin: bad args");
+    FD_REQUIRE((!time0 || times0) && (!time1 || times1), "fd_obj_begin: a time output without its table");
+    hipLaunchKernelGGL(obj_begin_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, t_dev, times0, times1, time0, time1, B, T);
+    FD_LAUNCH_OK("fd_obj_begin");
+    return FD_OK;
+}
+
+namespace {
+template <int MODE>
+void launch_obj_keyed(const float *o0, const float *o1, const float *x_t, const float *x_in, const float *par_table,
+                      const int *t_dev, const int64_t *seeds, float *img_out, int B, int64_t npix, int T, hipStream_t s) {
+    const bool vec = npix % 4 == 0 && al16(x_t) && al16(img_out) && (MODE == 1 || al16(o0)) && ((MODE != 1 && MODE != 2) || al16(o1)) &&
+                     (MODE == 2 || al16(x_in));
+    if (vec)
+        hipLaunchKernelGGL((res_step_obj_keyed_kernel<MODE, true>), dim3(g4(npix), B), dim3(256), 0, s, o0, o1, x_t, x_in,
+                           par_table, t_dev, seeds, img_out, npix, T);
+    else
+        hipLaunchKernelGGL((res_step_obj_keyed_kernel<MODE, false>), dim3(g4(npix), B), dim3(256), 0, s, o0, o1, x_t, x_in,
+                           par_table, t_dev, seeds, img_out, npix, T);
+}
+}  // namespace
+
+extern "C" int fd_res_step_obj_keyed(int mode, const float *o0, const float *o1, const float *x_t, const float *x_in,
+                                     const float *par_table, const int *t_dev, const int64_t *seeds, float *img_out, int B,
+                                     int64_t npix, int T, void *stream) {
+    FD_REQUIRE(mode >= 0 && mode <= 3, "fd_res_step_obj_keyed: bad mode %d", mode);
+    FD_REQUIRE(x_t && par_table && t_dev && seeds && img_out, "fd_res_step_obj_keyed: null pointer");
+    FD_REQUIRE((mode == 1 || o0) && ((mode != 1 && mode != 2) || o1) && (mode == 2 || x_in), "fd_res_step_obj_keyed: mode %d needs o0=%p o1=%p x_in=%p",
+               mode, (const void *)o0, (const void *)o1, (const void *)x_in);
+    FD_REQUIRE(B > 0 && B <= 65535 && T > 0 && npix > 0, "fd_res_step_obj_keyed: bad sizes B=%d T=%d", B, T);
+    FD_REQUIRE(npix < (1ll << 33), "fd_res_step_obj_keyed: image too large for the 32-bit pixel-group counter");
+    hipStream_t s = (hipStream_t)stream;
+    if (mode == 0) launch_obj_keyed<0>(o0, o1, x_t, x_in, par_table, t_dev, seeds, img_out, B, npix, T, s);
+    else if (mode == 1) launch_obj_keyed<1>(o0, o1, x_t, x_in, par_table, t_dev, seeds, img_out, B, npix, T, s);
+    else if (mode == 2) launch_obj_keyed<2>(o0, o1, x_t, x_in, par_table, t_dev, seeds, img_out, B, npix, T, s);
+    else launch_obj_keyed<3>(o0, o1, x_t, x_in, par_table, t_dev, seeds, img_out, B, npix, T, s);
+    FD_LAUNCH_OK("fd_res_step_obj_keyed");
     return FD_OK;
 }

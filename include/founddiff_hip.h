@@ -678,6 +678,30 @@ int fd_ancestral_begin(int *t_dev, const float *times, float *time_buf, int B, v
 int fd_res_posterior_step_keyed(const float *model_out, const float *x_t, const float *x_in,
                                 const float *coef_table, const int *t_dev, const int64_t *seeds,
                                 float *img_out, float *x_start_out, int B, int64_t npix, void *stream);
+/* ---- the same two for every objective of model_predictions and the two-U-Net model (fd_sched.hip), fp32
+ * The ancestral step of fd_res_step_obj (step == 2, modes 0-3 as above) with nothing of the step on the host:
+ *   fd_obj_begin            t = *t_dev = min(max(*t_dev - 1, 0), T - 1);  time0[b] = times0[t], time1[b] = times1[t]  (b < B)
+ *                           times0 / times1: device tables [T] of the two U-Nets' time inputs (alphas_cumsum * T or
+ *                           betas_cumsum * T for unet0, betas_cumsum * T for unet1).  time0 or time1 may be NULL -- the plan
+ *                           does not run that U-Net -- and is then left alone (its table may be NULL too).
+ *   fd_res_step_obj_keyed   t = *t_dev (held in [0, T)); par_table [T][8], row t = {ac, bc, omac, c1, c2, c3, logvar, 0}
+ *                           (alphas_cumsum[t], betas_cumsum[t], one_minus_alphas_cumsum[t], posterior_mean_coef1..3[t],
+ *                           posterior_log_variance_clipped[t]), the same row for every slice;
+ *                             mode 0: pred_res = clamp(o0), x_start = clamp(x_in - pred_res)
+ *                                  1: x_start = clamp((x_t - ac x_in - bc o1) / omac), pred_res = clamp(x_in - x_start)
+ *                                  2: pred_res = clamp(o0), x_start = clamp(x_t - ac pred_res - bc o1)
+ *                                  3: pred_res = clamp(x_in - o0), x_start = clamp(o0)
+ *                             img_out = c1 x_t + c2 pred_res + c3 x_start + exp(logvar / 2) noise, noise(b, t, pixel) the keyed
+ *                           stream of seeds[b] above, none at t = 0.  Writes img_out only; img_out == x_t updates in place.
+ *                           A mode reads only the streams its formulas name (o0 may be NULL in mode 1, o1 in modes 0 and 3 -- the
+ *                           update takes no predicted noise --, x_in in mode 2).  16-byte accesses when npix % 4 == 0 and every
+ *                           pointer is 16-byte aligned; the scalar form has the same bits.
+ * Both read the step from DEVICE memory: begin -> U-Net forward(s) -> step captures into one HIP graph, G steps at a time.  */
+int fd_obj_begin(int *t_dev, const float *times0, const float *times1, float *time0, float *time1, int B, int T,
+                 void *stream);
+int fd_res_step_obj_keyed(int mode, const float *o0, const float *o1, const float *x_t, const float *x_in,
+                          const float *par_table, const int *t_dev, const int64_t *seeds, float *img_out, int B,
+                          int64_t npix, int T, void *stream);
 /* ---- vanilla DDPM U-Net extras (src/denoising_diffusion_pytorch.py) -----------------------
  * fd_gn_film_silu_apply: silu(GN(h)*(1+scale[b]) + shift[b])   Block w/ scale_shift, 190-199, 213-221
  * fd_chan_ln:            LN over channels * g (+ res)           LayerNorm/PreNorm/Residual, 95-101,127-146
