@@ -62,6 +62,7 @@ SIGNATURES = {
     "fd_conv2d": (i32, [C.POINTER(ConvParams), vp]),
     "fd_conv_prologue_ok": (i32, [C.POINTER(ConvParams)]),
     "fd_conv_kernel_id": (i32, [C.POINTER(ConvParams)]),
+    "fd_conv_form": (i32, [C.POINTER(ConvParams)]),
     "fd_conv_fp8_ok": (i32, [C.POINTER(ConvParams)]),
     "fd_gn_finalize": (i32, [vp, i32, i32, i32, i32, i64, f32, vp, vp]),
     "fd_gn_silu_apply": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, vp]),

@@ -132,6 +132,22 @@ __device__ __forceinline__ void fd_gn_silu_add8(float (&val)[8], const float (&h
         val[2 * j + 1] += r.y;
     }
 }
+// The same arithmetic, operation for operation, with the statistics given per channel (8 channels may span GroupNorm groups): the
+// LDS-staged epilogue of fd_conv.hip.  It restated the formula as (h - mean) * rstd * gamma + beta, which rounds differently, so the
+// pointwise fast path (direct epilogue, the function above) and the general loader (staged epilogue) disagreed in the last bit of a
+// few stored elements per 10^5 on the same problem (tests/test_gpu_conv_forms.py).
+__device__ __forceinline__ void fd_gn_silu_add8(float (&val)[8], const float (&h)[8], const float (&mean)[8], const float (&rstd)[8],
+                                                const float (&gamma)[8], const float (&beta)[8]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const f32x2 rs = f32x2{rstd[2 * j], rstd[2 * j + 1]};
+        const f32x2 nm = f32x2{-mean[2 * j], -mean[2 * j + 1]} * rs;
+        const f32x2 t = f32x2{h[2 * j], h[2 * j + 1]} * rs + nm;
+        const f32x2 r = fd_silu2(t * f32x2{gamma[2 * j], gamma[2 * j + 1]} + f32x2{beta[2 * j], beta[2 * j + 1]});
+        val[2 * j] += r.x;
+        val[2 * j + 1] += r.y;
+    }
+}
 __device__ __forceinline__ float fd_softplus(float x) { return x > 20.0f ? x : log1pf(__expf(x)); }
 // softplus without libm: for x < -4 the series e - e^2/2 + e^3/3 of log1p(e), e = exp(x) < 0.0184
 // (truncation < 3e-8 absolute, ~1.5e-6 relative); else log(1 + e) with 1 + e >= 1.018 so the

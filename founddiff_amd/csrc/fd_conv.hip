@@ -494,9 +494,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_kernel(const fd_conv_
 #pragma unroll
                     for (int e = 0; e < 8; ++e) hv[e] = (n0 + e < p.Cout) ? ld1(hp + e) : 0.f;
                 }
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    val[e] += fd_silu((hv[e] - gmean[e]) * grstd[e] * gam[e] + bet[e]);
+                fd_gn_silu_add8(val, hv, gmean, grstd, gam, bet);      // the direct epilogue's arithmetic: PW promises the same bits
             }
             if (p.stats_partial) {
 #pragma unroll
@@ -686,6 +684,25 @@ extern "C" int fd_conv_kernel_id(const fd_conv_params *pp) {
     return (tall ? 0 : 2) + (wide ? 0 : 1);
 }
 
+// pointwise fast path (bf16) of the implicit-GEMM kernel: same tiles, same K order, same results -- only the address math differs
+static bool conv_pw_ok(const fd_conv_params &p) {
+    return p.dtype == FD_BF16 && p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad_h == 0 && p.pad_w == 0 &&
+           !p.upsample && p.ndir == 1 && p.OH == p.H && p.OW == p.W && (p.c0 + p.c1) % 64 == 0 &&
+           p.c0 % 64 == 0 && (int64_t)p.Cout * (p.c0 + p.c1) < (1ll << 31) &&
+           // its epilogue stores 8-channel vectors straight from the accumulators
+           !p.stats_partial && p.Cout % 8 == 0 && p.ldo % 8 == 0 && p.offo % 8 == 0 &&
+           (!p.res || (p.ld_res % 8 == 0 && p.off_res % 8 == 0)) && (!p.bias || ((uintptr_t)p.bias & 15) == 0) &&
+           (p.epilogue != FD_EPI_SILU_SPLIT || p.epi_split % 8 == 0) &&
+           (p.epilogue != FD_EPI_GNSILU_ADD || (p.gn_groups > 0 && (p.Cout / p.gn_groups) % 8 == 0));
+}
+
+// The whole form fd_conv2d launches for `p` (host only): fd_conv_kernel_id | pw << 8, pw = 1 when an implicit-GEMM tile (ids 0 .. 6)
+// runs with the pointwise loader.  The tests pin both (tests/conv_cases.py).
+extern "C" int fd_conv_form(const fd_conv_params *pp) {
+    const int kid = fd_conv_kernel_id(pp);
+    return kid | ((kid <= 6 && conv_pw_ok(*pp)) ? 1 << 8 : 0);
+}
+
 extern "C" int fd_conv2d(const fd_conv_params *pp, void *stream) {
     const fd_conv_params &p = *pp;
     const int CH = p.dtype == FD_BF16 ? 8 : 4;
@@ -734,15 +751,7 @@ extern "C" int fd_conv2d(const fd_conv_params *pp, void *stream) {
     const int BMs[7] = {128, 128, 64, 64, 128, 256, 128}, BNs[7] = {128, 64, 128, 64, 256, 256, 32};
     dim3 grid(cdiv((int64_t)p.OH * p.OW, BMs[kid]), cdiv(p.Cout, BNs[kid]), p.B * p.ndir), block(kid == 4 || kid == 5 ? 512 : 256);
     hipStream_t s = (hipStream_t)stream;
-    // pointwise fast path (bf16): same tiles, same K order, same results -- only the address math differs
-    const bool pw = p.dtype == FD_BF16 && p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad_h == 0 && p.pad_w == 0 &&
-                    !p.upsample && p.ndir == 1 && p.OH == p.H && p.OW == p.W && (p.c0 + p.c1) % 64 == 0 &&
-                    p.c0 % 64 == 0 && (int64_t)p.Cout * (p.c0 + p.c1) < (1ll << 31) &&
-                    // its epilogue stores 8-channel vectors straight from the accumulators
-                    !p.stats_partial && p.Cout % 8 == 0 && p.ldo % 8 == 0 && p.offo % 8 == 0 &&
-                    (!p.res || (p.ld_res % 8 == 0 && p.off_res % 8 == 0)) && (!p.bias || ((uintptr_t)p.bias & 15) == 0) &&
-                    (p.epilogue != FD_EPI_SILU_SPLIT || p.epi_split % 8 == 0) &&
-                    (p.epilogue != FD_EPI_GNSILU_ADD || (p.Cout / p.gn_groups) % 8 == 0);
+    const bool pw = conv_pw_ok(p);
 #define FD_CONV_LAUNCH(T_, BM_, BN_, WM_, WN_, PW_) \
     hipLaunchKernelGGL((conv_igemm_kernel<T_, BM_, BN_, WM_, WN_, PW_>), grid, block, 0, s, p)
 #define FD_CONV_DISPATCH(T_, PW_)                                     \

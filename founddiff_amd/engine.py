@@ -416,7 +416,8 @@ class DAEngine:
              ln_ld=0, ln_z=None, ln_ldz=0, ln_offz=0, probe=False, fin=None, zre=None):
         """One fd_conv2d launch.  `probe=True` only asks the library whether this conv can take the
         fused LayerNorm prologue (bf16 streaming row-GEMM path) and launches nothing; `probe="kid"`
-        returns fd_conv_kernel_id (tests pin which kernel a shape exercises)."""
+        returns fd_conv_kernel_id (tests pin which kernel a shape exercises), `probe="form"` fd_conv_form (the id and
+        whether the pointwise loader runs)."""
         def ptr(v):
             if v is None:
                 return None
@@ -484,6 +485,8 @@ class DAEngine:
                 p.upsample = 2
         if probe == "kid":          # which kernel would run (include/founddiff_hip.h: fd_conv_kernel_id)
             return int(self.hip.lib().fd_conv_kernel_id(C.byref(p)))
+        if probe == "form":         # ... and with which loader: kid | pw << 8 (fd_conv_form)
+            return int(self.hip.lib().fd_conv_form(C.byref(p)))
         if probe:
             return bool(self.hip.lib().fd_conv_prologue_ok(C.byref(p)))
         self.hip.call("fd_conv2d", C.byref(p), self.stream)

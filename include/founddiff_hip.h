@@ -178,6 +178,9 @@ int fd_conv_mtiles(int OH, int OW);         /* number of m-tiles per image (for 
  * <128,128>, <128,64>, <64,128>, <64,64>, <128,256>, <256,256>, <128,32> (profiling / roofline
  * bookkeeping; ids 4 and 5 depend on the batch size but give bitwise identical outputs)      */
 int fd_conv_kernel_id(const fd_conv_params *p);
+/* fd_conv_kernel_id(p) | pw << 8: pw = 1 when an implicit-GEMM tile (ids 0..6) runs with the bf16 pointwise loader (1x1, stride 1,
+ * Cin and c0 multiples of 64, 8-channel-aligned output, no GroupNorm sums) instead of the general gather.  Host only.       */
+int fd_conv_form(const fd_conv_params *p);
 int fd_conv2d(const fd_conv_params *p, void *stream);
 
 /* GroupNorm statistics from the conv's partial sums -> mean_rstd [B][G][2] (nn.GroupNorm,
