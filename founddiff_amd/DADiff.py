@@ -16,6 +16,7 @@ around `diffusion_train.ClipRAdamEMA` on request: `UnetRes.trainable()` and `Tra
 """
 import copy
 import ctypes as C
+import functools
 import math
 import os
 import random
@@ -79,6 +80,22 @@ def _affine(x, a, b):
     out = torch.empty_like(x)
     L.call("fd_affine_f32", _p(x), a, b, _p(out), x.numel(), _stream(x))
     return out
+
+
+def _fuse_keyword(fn):
+    """sample_tiled's keyword-only `fuse`: "final" (the default) or "step".  It is taken here, in front of the method, and handed to
+    it as self._tile_fuse for the length of the call, so that the method keeps the parameter list tests/test_tiling_cpu.py pins
+    (inspect.signature follows __wrapped__ to it and therefore does NOT show `fuse`: the docstring is where it is documented)."""
+    @functools.wraps(fn)
+    def sample_tiled(self, *args, fuse="final", **kw):
+        if fuse not in ("final", "step"):
+            raise RuntimeError(f"sample_tiled: fuse must be 'final' or 'step' (got {fuse!r})")
+        self._tile_fuse = fuse
+        try:
+            return fn(self, *args, **kw)
+        finally:
+            self._tile_fuse = "final"
+    return sample_tiled
 
 
 class _ParamTree(nn.Module):
@@ -1345,6 +1362,7 @@ class ResidualDiffusion(nn.Module):
         return plan
 
     @torch.no_grad()
+    @_fuse_keyword
     def sample_tiled(self, x_input, tile, overlap=0, slice_seeds=None, condition="tile"):
         """x_input = [ldct (B,1,H,W) in [0,1]] sampled as overlapping tiles of `tile` = th or (th, tw) pixels, `overlap` (an int or
         a pair, at most tile // 2) pixels apart from full tiles (tiling.tile_plan: the last tile of an axis is shifted back to end
@@ -1363,8 +1381,23 @@ class ResidualDiffusion(nn.Module):
         pixel under one tile is that tile's value bit for bit.  Nothing returned depends on B or on the cut into passes.
         condition="tile": the DA-CLIP tower runs on every tile, which is what crop training saw.  "slice": it runs once per slice
         on the whole slice (Unet.tower_engine) and every tile of the slice takes those conditioning rows.
-        Not built: blending inside the loop (per-step fusion of the tiles), tiled ensembles, tiles larger than the slice,
-        last=False, input_condition=True."""
+        `fuse` is a further, keyword-only argument (taken by _fuse_keyword in front of this method; an unknown value raises).
+        fuse="final" (the default) is all of the above: every tile runs its own trajectory and the final images are blended once.
+        fuse="step" fuses the tiles at EVERY step instead: the slice has one state x_t, held as tile rows that agree bit for bit
+        in the common pixels of overlapping tiles.  Per step the forwards of all tile rows run into output buffers, in equal
+        sub-batches of at most max_sub_batch rows per engine (half of it for a two-U-Net plan), each under its own conditioning
+        rows (computed once before the loop, for both values of `condition`), and ONE launch of fd_tiles_step_ddim_f32 /
+        fd_tiles_step_keyed_f32 blends the tiles' raw outputs per pixel (the weights and arithmetic of fd_tiles_blend_f32) and
+        applies the scheduler update to every row in place; the ancestral step noise is the keyed stream of the SLICE seed at the
+        slice pixel, the same for every covering tile (tile_seeds are not used).  It is one trajectory of the whole slice under a
+        windowed model: the final image is assembled from the rows on the last step, every pixel being every covering tile's
+        value, so there is no seam and no mean of different denoisings or noise realisations.  A one-tile plan is sample() of the
+        two-U-Net and pred_noise plans bit for bit; the first returned image is that of fuse="final".  Every plan of _plan()
+        runs, the shipped one as mode 0, on both samplers (_anc_max_chunks bounds the ancestral one as in _obj_ancestral), on one
+        stream with slot 0's engines, eagerly: no captured graph, no second stream, and no precision tail for any plan -- a bf16
+        fused run of the shipped plan does not get final_fp32_steps.  Nothing returned depends on B or on max_sub_batch.
+        Not built: tiled ensembles, tiles larger than the slice (padded tiles), last=False, input_condition=True; for
+        fuse="step" also a captured graph or a second stream, a precision tail, and per-tile seeds."""
         fn = "sample_tiled"
         if self.input_condition:
             raise RuntimeError(f"{fn}: input_condition=True is not built (one input plane per slice)")
@@ -1394,6 +1427,8 @@ class ResidualDiffusion(nn.Module):
         field = self._keyed_noise(seeds.to(x01.device), self.X_T_STEP, tuple(x01.shape))
         x_T = torch.empty_like(x01)
         L.call("fd_axpy_f32", _p(normalize_to_neg_one_to_one(x01)), _p(field), math.sqrt(self.sum_scale), _p(x_T), x_T.numel(), s)
+        if self._tile_fuse == "step":
+            return [unnormalize_to_zero_to_one(x_T), self._tiled_fused(x01, field, seeds.to(x01.device), plan, condition)]
         tiles = self._tile_rows(x01, field, rows, plan, condition)
         if self.model.unet0.kernel_precision == "fp16" and self.check_fp16_range and not bool(torch.isfinite(tiles).all()):
             if self.model.unet0.precision != "auto":              # sample()'s rule, applied to the tiles
@@ -1418,31 +1453,123 @@ class ResidualDiffusion(nn.Module):
         L.call("fd_tiles_gather_f32", _p(src), _p(dst), _p(ys), _p(xs), B, H, W, th, tw, my, mx, x4, _stream(src))
         return dst
 
+    def _tile_cond_slice(self, x_n, T):
+        """condition="slice": the conditioning rows of the B x T tile rows of the slices x_n (in [-1, 1]), one (prompt_emb,
+        local_all) pair per engine of _engines().  The tower runs once per slice on the whole slice, at most max_sub_batch slices
+        at a time, on a tower-only engine per U-Net in use; the engine of the tiles turns its outputs into conditioning rows,
+        repeated for the slice's T tiles."""
+        B, s = x_n.shape[0], _stream(x_n)
+        engines = self._engines()
+        _, r0, r1, _ = self._plan()
+        unets = ([self.model.unet0] if r0 else []) + ([self.model.unet1] if r1 else [])
+        cond = [(e._b("til_prompt", (B * T, e.time_dim), torch.float32), e._b("til_local", (B * T, e.loc_total), torch.float32))
+                for e in engines]
+        for c0 in range(0, B, self.max_sub_batch):
+            nb = min(self.max_sub_batch, B - c0)
+            for u, e, (pe, la) in zip(unets, engines, cond):
+                e.condition_from(*u.tower_engine(e.mode).encode_dose(x_n[c0:c0 + nb]))
+                L.call("fd_rows_repeat_f32", _p(e.prompt_emb), _p(pe[c0 * T:]), nb, T, e.time_dim, s)
+                L.call("fd_rows_repeat_f32", _p(e.local_all), _p(la[c0 * T:]), nb, T, e.loc_total, s)
+        return cond
+
+    def _tiled_fused(self, x01, field, seeds, plan, condition):
+        """The final image (B,1,H,W), in [0, 1] units, of sample_tiled(fuse="step"); seeds (B,) int64 on the device.  The fp16
+        range check and the precision='auto' fallback are sample()'s, applied to that image."""
+        out = self._tiled_fused_loop(x01, field, seeds, plan, condition)
+        if self.model.unet0.kernel_precision == "fp16" and self.check_fp16_range and not bool(torch.isfinite(out).all()):
+            if self.model.unet0.precision != "auto":
+                raise L.FoundDiffHipError(
+                    "precision='fp16': a sampled image is not finite -- an activation of this checkpoint left IEEE binary16's "
+                    "range (65504).  Use precision='bf16' (same speed, fp32's range, 8 significand bits), 'auto' or 'fp32s'.")
+            import warnings
+            warnings.warn("founddiff_amd: precision='auto': this checkpoint's activations leave IEEE binary16's range; "
+                          "this and every later sample() of the model run on the bfloat16 kernels")
+            for u in (getattr(self.model, "unet0", None), getattr(self.model, "unet1", None)):
+                if u is not None:
+                    u._auto_bf16 = True
+            out = self._tiled_fused_loop(x01, field, seeds, plan, condition)
+        return out
+
+    def _tiled_fused_loop(self, x01, field, seeds, plan, condition):
+        """One trajectory of the slices as R = B my mx tile rows (sample_tiled's docstring).  Per step: [fd_obj_begin on the
+        ancestral sampler,] per U-Net of the plan and per sub-batch load_condition + forward into the rows of o0 / o1, then one
+        fd_tiles_step_* launch over all R rows in place on img, which also writes the slice image on the last step."""
+        ys, xs, wy, wx, my, mx, x4, th, tw = plan
+        B, _, H, W = x01.shape
+        Tl, dev, s = my * mx, x01.device, _stream(x01)
+        R = B * Tl
+        mode, r0, r1, _ = self._plan()
+        engines = self._engines()
+        x_n = normalize_to_neg_one_to_one(x01)
+        x_in = self._tile_gather(x_n, plan)
+        img = torch.empty_like(x_in)
+        L.call("fd_axpy_f32", _p(x_in), _p(self._tile_gather(field, plan)), math.sqrt(self.sum_scale), _p(img), img.numel(), s)   # _x_T
+        per = self.max_sub_batch // 2 if (r0 and r1) else self.max_sub_batch
+        passes = tile_passes(B, my, mx, max(1, per))
+        nmax = max(hi - lo for lo, hi in passes)
+        # conditioning rows of every tile row, once: the tower on every tile, or on the whole slices
+        if condition == "slice":
+            cond = self._tile_cond_slice(x_n, Tl)
+        else:
+            cond = [(e._b("til_prompt", (R, e.time_dim), torch.float32), e._b("til_local", (R, e.loc_total), torch.float32))
+                    for e in engines]
+            for lo, hi in passes:
+                for e, (pe, la) in zip(engines, cond):
+                    e.encode_condition(x_in[lo:hi])
+                    pe[lo:hi].copy_(e.prompt_emb)
+                    la[lo:hi].copy_(e.local_all)
+        outs = [torch.empty_like(x_in) for _ in engines]
+        # the single U-Net of 'pred_noise' predicts the noise: its output is the kernels' o1
+        o0 = outs[0] if (r0 and mode != 1) else None
+        o1 = outs[-1] if (r1 or mode == 1) else None
+        final = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
+        geom = (_p(wy), _p(wx), _p(ys), _p(xs), B, H, W, th, tw, my, mx, x4)
+
+        def forwards(times):
+            for e, o, tb, c in zip(engines, outs, times, cond):
+                for lo, hi in passes:
+                    e.load_condition(c[0][lo:hi], c[1][lo:hi])
+                    e.forward(img[lo:hi], x_in[lo:hi], tb[:hi - lo], out=o[lo:hi])
+
+        if self.is_ddim_sampling:
+            S = self.sampling_timesteps
+            par, tt0, tt1 = self._obj_ddim_table(nmax)
+            gpar = par[:, 0].contiguous().to(dev)                  # (S, 8): all rows of a step share the parameters
+            gts = [tt.to(dev) for tt in (tt0, tt1) if tt is not None]
+            for i in range(S):
+                forwards([gt[i] for gt in gts])
+                L.call("fd_tiles_step_ddim_f32", mode, _p(o0), _p(o1), _p(img), _p(x_in), _p(gpar[i]), *geom, _p(img),
+                       _p(final) if i == S - 1 else None, s)
+        else:
+            T = self.num_timesteps
+            t_dev = torch.full((1,), T, device=dev, dtype=torch.int32)
+            gpar = self._obj_anc_table().to(dev)
+            tabs = [None if tt is None else tt.to(dev) for tt in self._obj_time_tables()]
+            bufs = [None if tt is None else torch.zeros(nmax, device=dev, dtype=torch.float32) for tt in tabs]
+            G = max([g for g in range(8, 65) if T % g == 0] or [40])          # _obj_ancestral's chunks, for _anc_max_chunks
+            steps = T
+            lim = getattr(self, "_anc_max_chunks", None)
+            if lim:
+                steps = min(T // G, int(lim)) * G
+            for i in range(steps):
+                L.call("fd_obj_begin", _p(t_dev), _p(tabs[0]), _p(tabs[1]), _p(bufs[0]), _p(bufs[1]), nmax, T, s)
+                forwards([b for b in bufs if b is not None])
+                L.call("fd_tiles_step_keyed_f32", mode, _p(o0), _p(o1), _p(img), _p(x_in), _p(gpar), _p(t_dev), _p(seeds), *geom,
+                       _p(img), _p(final) if i == steps - 1 else None, T, s)
+            self._anc_steps_run = steps
+        return unnormalize_to_zero_to_one(final)
+
     def _tile_rows(self, x01, field, seeds, plan, condition):
         """The B my mx final tile images (R,1,th,tw) of sample_tiled, in [0, 1] units; seeds (R,) int64 on the device."""
         my, mx, th, tw = plan[4], plan[5], plan[7], plan[8]
         B, T = x01.shape[0], my * mx
         R = B * T
-        s = _stream(x01)
         nz_rows = self._tile_gather(field, plan)
         cond = None
         if condition == "slice":
-            # the tower: once per slice on the whole slice, at most max_sub_batch slices at a time, on a tower-only engine per
-            # U-Net in use; the engine of the tiles turns its outputs into conditioning rows, repeated for the slice's tiles.  The
-            # rows of a preset are already in [-1, 1] (_sample)
-            x_n = normalize_to_neg_one_to_one(x01)
+            x_n = normalize_to_neg_one_to_one(x01)                 # the rows of a preset are already in [-1, 1] (_sample)
             x_rows = self._tile_gather(x_n, plan)
-            engines = self._engines()
-            _, r0, r1, _ = self._plan()
-            unets = ([self.model.unet0] if r0 else []) + ([self.model.unet1] if r1 else [])
-            cond = [(e._b("til_prompt", (R, e.time_dim), torch.float32), e._b("til_local", (R, e.loc_total), torch.float32))
-                    for e in engines]
-            for c0 in range(0, B, self.max_sub_batch):
-                nb = min(self.max_sub_batch, B - c0)
-                for u, e, (pe, la) in zip(unets, engines, cond):
-                    e.condition_from(*u.tower_engine(e.mode).encode_dose(x_n[c0:c0 + nb]))
-                    L.call("fd_rows_repeat_f32", _p(e.prompt_emb), _p(pe[c0 * T:]), nb, T, e.time_dim, s)
-                    L.call("fd_rows_repeat_f32", _p(e.local_all), _p(la[c0 * T:]), nb, T, e.loc_total, s)
+            cond = self._tile_cond_slice(x_n, T)
         else:
             x_rows = self._tile_gather(x01, plan)                  # plain rows of _sample, which normalises them itself
         tiles = torch.empty((R, 1, th, tw), device=x01.device, dtype=torch.float32)
@@ -2152,7 +2279,7 @@ class Trainer(object):
 
     @torch.no_grad()
     def test(self, sample=False, last=True, FID=False, batch_size=1, n_samples=1, ensemble_seed=0, tile=None, overlap=0,
-             tile_condition="tile"):
+             tile_condition="tile", tile_fuse="final"):
         """Evaluation loop of src/DADiff.py:1817-1966: init() the schedule, denoise every slice,
         PSNR/SSIM/RMSE vs NDCT (on device), np.save each output in [0,1], per-anatomy / per-dose means.
         `batch_size` > 1 batches independent slices (the reference uses 1).  `sample=True` keeps the
@@ -2162,8 +2289,8 @@ class Trainer(object):
         `ensemble_seed` + its dataset index; the metrics and the saved image are those of the ensemble mean, and outside
         training the per-pixel standard deviation is saved beside it as `<name>_std.npy`.
         `tile` (an int or (th, tw); None: whole slices, as ever): every slice is sampled as overlapping tiles
-        (ResidualDiffusion.sample_tiled with `overlap` and condition=`tile_condition`) under the slice seed `ensemble_seed` + its
-        dataset index; the metrics and the saved image are those of the blended slice.  Ensembles of tiled samples
+        (ResidualDiffusion.sample_tiled with `overlap`, condition=`tile_condition` and fuse=`tile_fuse`) under the slice seed
+        `ensemble_seed` + its dataset index; the metrics and the saved image are those of the blended slice.  Ensembles of tiled samples
         (n_samples > 1) and last=False are not built and raise."""
         if int(n_samples) < 1:
             raise RuntimeError(f"Trainer.test: n_samples must be at least 1 (got {n_samples})")
@@ -2184,7 +2311,7 @@ class Trainer(object):
             if batch_size == 1 and int(n_samples) == 1 and tile is None:      # (an ensemble is a batch of replicas, a tiled slice
                 for u in unets:                                           # a batch of tiles: the default kernel set)
                     u.low_latency = True
-            tiled = None if tile is None else (tile, overlap, tile_condition)
+            tiled = None if tile is None else (tile, overlap, tile_condition, tile_fuse)
             return self._test(sample, last, FID, batch_size, int(n_samples), int(ensemble_seed), tiled)
         finally:
             for u, v in zip(unets, saved):
@@ -2222,7 +2349,8 @@ class Trainer(object):
                 ens = model.sample_ensemble(xs, n_samples, slice_seeds=[ensemble_seed + i for i in idx])
                 y_pred, y_std = ens.mean, ens.std
             elif tiled is not None:
-                outs = model.sample_tiled(xs, tiled[0], tiled[1], slice_seeds=[ensemble_seed + i for i in idx], condition=tiled[2])
+                outs = model.sample_tiled(xs, tiled[0], tiled[1], slice_seeds=[ensemble_seed + i for i in idx], condition=tiled[2],
+                                          fuse=tiled[3])
                 all_images_list = [y] + xs + list(outs)
                 y_pred = outs[-1]
             elif sample:

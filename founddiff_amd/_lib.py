@@ -188,6 +188,10 @@ SIGNATURES = {
     "fd_ensemble_stats_f32": (i32, [vp, vp, vp, vp, vp, i32, i32, i64, vp]),
     "fd_tiles_gather_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "fd_tiles_blend_f32": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    # (mode, o0, o1, x_t, x_in, par[, t_dev, slice_seeds], wy, wx, ys, xs, B, H, W, th, tw, my, mx, xs_mult4, img_out, slice_out[, T])
+    "fd_tiles_step_ddim_f32": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "fd_tiles_step_keyed_f32": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp,
+                                      i32, vp]),
     "fd_store_gather_f32": (i32, [vp, vp, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "fd_res_qsample_store_f32": (i32, [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32,
                                        i32, vp]),

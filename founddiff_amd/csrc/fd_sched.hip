@@ -13,6 +13,7 @@
 // coefficients from a device table, so a chunk of steps can be captured in one HIP graph and replayed.
 #include "fd_common.h"
 #include "fd_keyed_noise.h"
+#include "fd_obj_pixel.h"
 
 namespace {
 
@@ -87,31 +88,9 @@ __global__ void obj_begin_kernel(int *t_dev, const float *__restrict__ times0, c
     }
 }
 
-struct obj_row { float a, bb, oma, c1, c2, c3, sd; };
-
-// one pixel: predictions of res_step_obj_kernel's `mode`, then its step == 2 update.  The fused multiply-adds are written out and
-// the compiler forms none of its own: the 16-byte and the one-pixel form of the kernel round alike, so a slice's bits do not depend
-// on the alignment of its buffers.
-template <int MODE>
-__device__ __forceinline__ float obj_pixel(const obj_row &r, float o0, float o1, float x, float xi, float z) {
-#pragma clang fp contract(off)
-    float pr, xs;
-    if (MODE == 0) {
-        pr = clamp1s(o0);
-        xs = clamp1s(xi - pr);
-    } else if (MODE == 1) {
-        xs = clamp1s(fmaf(-r.bb, o1, fmaf(-r.a, xi, x)) / r.oma);
-        pr = clamp1s(xi - xs);
-    } else if (MODE == 2) {
-        pr = clamp1s(o0);
-        xs = clamp1s(fmaf(-r.bb, o1, fmaf(-r.a, pr, x)));
-    } else {
-        pr = clamp1s(xi - o0);
-        xs = clamp1s(o0);
-    }
-    return fmaf(r.sd, z, fmaf(r.c3, xs, fmaf(r.c2, pr, r.c1 * x)));
-}
-
+// one pixel: obj_pixel<MODE> of fd_obj_pixel.h, the predictions of res_step_obj_kernel's `mode`, then its step == 2 update; the
+// 16-byte and the one-pixel form of the kernel round alike, so a slice's bits do not depend on the alignment of its buffers.
+//
 // xt / out may be the same buffer: no __restrict__ on them; a thread reads its four pixels before it writes them.  A mode reads
 // only the streams its formulas name (modes 0, 3: no o1 -- the update takes no predicted noise --, mode 1: no o0, mode 2: no
 // x_in).  VEC: npix % 4 == 0 and every pointer 16-byte aligned -- one 16-byte access per stream and group; otherwise the same

@@ -44,7 +44,7 @@ def gather_volume(local, world, n_total=None):
 
 
 def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampler_kwargs=None, n_samples=1, tile=None,
-                  overlap=0):
+                  overlap=0, tile_fuse="final"):
     """Denoise a whole volume ldct (N,1,H,W in [0,1], same tensor on every rank) with `diffusion`
     (a founddiff_amd.DADiff.ResidualDiffusion living on this rank's device).  x_T noise is keyed
     by the GLOBAL slice index, and so is the ancestral sampler's per-step noise (`slice_seeds`:
@@ -53,9 +53,9 @@ def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampl
     `n_samples` > 1: every slice is an ensemble of that many realisations (sample_ensemble) whose replica seeds derive from
     `noise_seed` + the GLOBAL slice index; returns (mean, std), two (N,1,H,W) volumes, on every rank.  `sampler_kwargs` are
     sample()'s and do not reach it.
-    `tile` (an int or (th, tw); None: whole slices): every slice is sampled as overlapping tiles (sample_tiled with `overlap`)
-    under the slice seed `noise_seed` + its GLOBAL index; every row is keyed, so the volume is the same on any `world` and for
-    any `batch`.  Together with n_samples > 1 it raises: tiled ensembles are not built."""
+    `tile` (an int or (th, tw); None: whole slices): every slice is sampled as overlapping tiles (sample_tiled with `overlap` and
+    fuse=`tile_fuse`) under the slice seed `noise_seed` + its GLOBAL index; every row is keyed, so the volume is the same on any
+    `world` and for any `batch`.  Together with n_samples > 1 it raises: tiled ensembles are not built."""
     n = ldct.shape[0]
     lo, hi = shard_range(n, world, rank)
     dev = next(diffusion.parameters()).device
@@ -63,7 +63,8 @@ def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampl
         if int(n_samples) > 1:
             raise RuntimeError(f"sample_volume: tile={tile!r} with n_samples={n_samples}: ensembles of tiled samples are not built")
         outs = [diffusion.sample_tiled([ldct[s:min(s + batch, hi)].to(dev)], tile, overlap,
-                                       slice_seeds=torch.arange(s, min(s + batch, hi), dtype=torch.int64) + int(noise_seed))[-1]
+                                       slice_seeds=torch.arange(s, min(s + batch, hi), dtype=torch.int64) + int(noise_seed),
+                                       fuse=tile_fuse)[-1]
                 for s in range(lo, hi, batch)]
         local = torch.cat(outs, 0) if outs else ldct.new_zeros((0,) + tuple(ldct.shape[1:])).to(dev)
         return gather_volume(local, world, n)

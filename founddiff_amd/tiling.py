@@ -54,6 +54,17 @@ def tile_weights(origins, n, tile):
     return w.astype(np.float32)
 
 
+def tile_owner(ys, xs, H, W, th, tw):
+    """(H, W) int64: per pixel the first tile that covers it in row-major tile order, iy * len(xs) + ix with iy ascending, then ix
+    (-1 where none does) -- the tile whose lane writes the slice pixel in csrc/fd_tiles_step.hip."""
+    ys, xs = np.asarray(ys, dtype=np.int64).reshape(-1), np.asarray(xs, dtype=np.int64).reshape(-1)
+    owner = np.full((int(H), int(W)), -1, dtype=np.int64)
+    for iy in range(len(ys) - 1, -1, -1):                      # descending, so that the first cover is written last
+        for ix in range(len(xs) - 1, -1, -1):
+            owner[ys[iy]:ys[iy] + th, xs[ix]:xs[ix] + tw] = iy * len(xs) + ix
+    return owner
+
+
 def tile_seeds(slice_seeds, n_tiles):
     """(B, n_tiles) int64: tile 0 keeps the slice's seed s (a one-tile plan is the sample of `slice_seeds`), tile j >= 1 gets
     splitmix64(s ^ (j * 0xA0761D6478BD642F mod 2^64)) >> 2."""

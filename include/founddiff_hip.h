@@ -840,6 +840,31 @@ int fd_tiles_gather_f32(const float *src, float *dst, const int *ys, const int *
                         int mx, int xs_mult4, void *stream);
 int fd_tiles_blend_f32(const float *tiles, const float *wy, const float *wx, const int *ys, const int *xs, float *out, int B,
                        int H, int W, int th, int tw, int my, int mx, int xs_mult4, void *stream);
+/* ---- one sampler step of a slice held as tiles, the tiles' model outputs blended per pixel first (fd_tiles_step.hip;
+ * ResidualDiffusion.sample_tiled(fuse="step")).  fp32, the same in both builds; no atomics, no workspace.  The plan and weight
+ * arguments and the shape limits are fd_tiles_blend_f32's; o0, o1, x_t, x_in, img_out are [B my mx][th tw] in tile-row order.  A
+ * lane owns 4 consecutive pixels of one tile row and, for its pixel (y, x) of slice b,
+ *   blends  each stream the mode reads over the covering tiles in row-major tile order with fd_tiles_blend_f32's arithmetic
+ *           (modes 0 and 3 read o0, mode 1 o1, mode 2 both; x_in may be NULL in mode 2),
+ *   updates with the blended outputs, its own x_t and its own x_in:
+ *           fd_tiles_step_ddim_f32   fd_res_step_obj's step 1 without noise; par (DEVICE, 8 floats, shared by all rows) =
+ *                                    {ac, bc, omac, alpha, -, -, -, last}: last != 0 ? x_start : x_t - alpha pred_res
+ *           fd_tiles_step_keyed_f32  fd_res_step_obj_keyed's update, row t = *t_dev (held in [0, T)) of par_table [T][8]; the noise
+ *                                    is that of the SLICE pixel, element (y W + x) % 4 of the keyed stream's group (y W + x) / 4
+ *                                    under slice_seeds[b] ([B]: one seed per slice) -- fd_keyed_normal's field over the slice --
+ *                                    so overlapping tiles receive the same noise; none at t = 0,
+ *   writes  img_out (which may be x_t: a lane reads other tiles' o0 / o1 only) and, where slice_out ([B][H W], may be NULL) is
+ *           given and its tile is the first of the covering tiles in that order, the slice pixel.
+ * Rows gathered from slice-level x_t and x_in (fd_tiles_gather_f32) leave the step with equal bits in the common pixels of
+ * overlapping tiles; a one-tile plan has the bits of fd_res_step_obj / fd_res_step_obj_keyed.  16-byte accesses when xs_mult4,
+ * W % 4 == 0, tw % 4 == 0 and every pointer in use is 16-byte aligned; the scalar form has the same bits. */
+int fd_tiles_step_ddim_f32(int mode, const float *o0, const float *o1, const float *x_t, const float *x_in, const float *par,
+                           const float *wy, const float *wx, const int *ys, const int *xs, int B, int H, int W, int th, int tw,
+                           int my, int mx, int xs_mult4, float *img_out, float *slice_out, void *stream);
+int fd_tiles_step_keyed_f32(int mode, const float *o0, const float *o1, const float *x_t, const float *x_in,
+                            const float *par_table, const int *t_dev, const int64_t *slice_seeds, const float *wy, const float *wx,
+                            const int *ys, const int *xs, int B, int H, int W, int th, int tw, int my, int mx, int xs_mult4,
+                            float *img_out, float *slice_out, int T, void *stream);
 
 /* ---- a training batch from a slice store on the device (fd_train_data.hip; data/pdf_dataset.py:521-545) -------
  * nd [n_nd][H][W], ld [n_ld][H][W] fp32 in [0, 1].  Item b of the batch is the pair nd[nd_slot[b]], ld[ld_slot[b]] (int64 [B],
