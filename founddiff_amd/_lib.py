@@ -63,6 +63,7 @@ SIGNATURES = {
     "fd_conv_prologue_ok": (i32, [C.POINTER(ConvParams)]),
     "fd_conv_kernel_id": (i32, [C.POINTER(ConvParams)]),
     "fd_conv_form": (i32, [C.POINTER(ConvParams)]),
+    "fd_gemm_rows_form": (i32, [C.POINTER(ConvParams), C.POINTER(i32)]),
     "fd_conv_fp8_ok": (i32, [C.POINTER(ConvParams)]),
     "fd_gn_finalize": (i32, [vp, i32, i32, i32, i32, i64, f32, vp, vp]),
     "fd_gn_silu_apply": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, vp]),
@@ -206,6 +207,18 @@ SIGNATURES = {
     "fd_final_conv1_bwd_f32": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i64, i32, vp]),
     "fd_half_format": (i32, []),
 }
+
+# fd_gemm_rows_form's answer, in its field order (include/founddiff_hip.h)
+ROWS_FORM_FIELDS = ("kid", "KS", "PRO", "EPI", "NT", "S", "wtiles", "gx", "lds", "zre")
+
+
+def rows_form(lib, p):
+    """the streaming row-GEMM's launch plan for the ConvParams `p` as a dict, or None when `p` does not run there (host only)"""
+    form = (i32 * len(ROWS_FORM_FIELDS))()
+    if not lib.fd_gemm_rows_form(C.byref(p), form):
+        return None
+    return dict(zip(ROWS_FORM_FIELDS, (int(v) for v in form)))
+
 
 class FoundDiffHipError(RuntimeError):
     pass

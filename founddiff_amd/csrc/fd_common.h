@@ -333,3 +333,16 @@ int fd_dev(int id);            // fd_small.hip: the table, filled from the envir
 static inline size_t fd_occ_pad(int id) { return (size_t)fd_dev(id) * 1024; }
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// What the streaming row-GEMM launches for one fd_conv_params (fd_gemm_rows.hip, fd_gemm_rows32.hip): decided in ONE place per file
+// (rows_plan / rows32_plan), launched from it, and reported by fd_gemm_rows_form in this field order (include/founddiff_hip.h).
+// KS, PRO, EPI, NT, S are the template arguments of the kernel (PRO = 3: a z-recompute kernel, named by zre).
+struct fd_rows_plan {
+    int kid;        // 10: 16-bit storage, 17: fp32 storage with split-bf16 contractions
+    int KS, PRO, EPI, NT, S;
+    int wtiles;     // wave tiles per image: cdiv(H * W, 16 * S)
+    int gx;         // grid x (grid y = B): persistent workgroups per image
+    int lds;        // dynamic LDS bytes
+    int zre;        // 0: none; 1: gemm_rows_zre_kernel<4, 256, true>; 2: gemm_rows_zre_kernel<8, 512, false>; 3: gemm_rows32_zre_kernel<256>
+};
+#define FD_ROWS_FORM_FIELDS 10

@@ -499,12 +499,25 @@ void launch_rows_nt(const fd_conv_params &p, dim3 grid, size_t lds, int wtiles, 
     hipLaunchKernelGGL((gemm_rows_kernel<KS, PRO, EPI, NT>), grid, dim3(NT), lds, s, p, wtiles, RS);
 }
 
+// false: the plan names an instantiation that was not compiled (the fits_* rules) -- nothing is launched
 template <int KS, int PRO, int EPI>
-void launch_rows(const fd_conv_params &p, int nt, dim3 grid, size_t lds, int wtiles, int RS, hipStream_t s) {
-    if (nt == 256) launch_rows_nt<KS, PRO, EPI, 256>(p, grid, lds, wtiles, RS, s);
-    else if (nt == 512) {
-        if constexpr (fits_512(KS, PRO)) launch_rows_nt<KS, PRO, EPI, 512>(p, grid, lds, wtiles, RS, s);
-    } else if constexpr (fits_768(KS, PRO)) launch_rows_nt<KS, PRO, EPI, 768>(p, grid, lds, wtiles, RS, s);
+bool launch_rows(const fd_conv_params &p, int nt, dim3 grid, size_t lds, int wtiles, int RS, hipStream_t s) {
+    if (nt == 256) {
+        launch_rows_nt<KS, PRO, EPI, 256>(p, grid, lds, wtiles, RS, s);
+        return true;
+    }
+    if (nt == 512) {
+        if constexpr (fits_512(KS, PRO)) {
+            launch_rows_nt<KS, PRO, EPI, 512>(p, grid, lds, wtiles, RS, s);
+            return true;
+        }
+    } else if (nt == 768) {
+        if constexpr (fits_768(KS, PRO)) {
+            launch_rows_nt<KS, PRO, EPI, 768>(p, grid, lds, wtiles, RS, s);
+            return true;
+        }
+    }
+    return false;
 }
 
 }  // namespace
@@ -550,9 +563,15 @@ extern "C" int fd_conv_prologue_ok(const fd_conv_params *pp) {
 
 constexpr int ZRE8_NT = 512;
 
-int fd_gemm_rows_launch(const fd_conv_params &p, hipStream_t s) {
-    if (p.dtype == FD_F32) return fd_gemm_rows32_launch(p, s);
+int fd_gemm_rows32_plan(const fd_conv_params &p, fd_rows_plan &q);
+
+// The one place where the kernel, its workgroup size and the grid of a launch are decided (host only: no device is touched).
+// 0: `p` has no row-GEMM kernel.
+static int rows_plan(const fd_conv_params &p, fd_rows_plan &q) {
+    if (p.dtype == FD_F32) return fd_gemm_rows32_plan(p, q);
     const int K = p.c0 + p.c1, KS = K / 32, RS = row_stride(K);
+    if (KS != 1 && KS != 2 && KS != 3 && KS != 4 && KS != 6 && KS != 8) return 0;
+    if (p.epilogue < FD_EPI_NONE || p.epilogue > FD_EPI_GNSILU_ADD_FINAL) return 0;
     const int64_t hw = (int64_t)p.H * p.W;
     const int px = KS <= 2 ? 32 : 16;      // pixels per wave iteration (see template parameter S)
     const bool zre = p.prologue == FD_PRO_LN_GATE_ZRE;
@@ -562,7 +581,7 @@ int fd_gemm_rows_launch(const fd_conv_params &p, hipStream_t s) {
     int per_cu = (int)(150 * 1024 / lds);
     // (round 4: 3 persistent workgroups per CU instead of 4 once the batch fills the chip: -0.1..-0.3 % per batch-8 forward,
     //  2: +0.8 %; 4 for small batches: +0.7 ms per 50-step slice at batch 1 otherwise.  The grid size does not touch the
-    //  results: every pixel row is computed by itself)
+    //  results: every pixel row is computed by itself -- tests/test_gpu_rows_forms.py compares the bits)
     const int pcmax = fd_dev(FD_DEV_ROWS_PER_CU_MAX);    // development
     const int pclim = pcmax > 0 ? pcmax : (p.B >= 4 ? 3 : 4);
     if (per_cu > pclim) per_cu = pclim;
@@ -575,11 +594,41 @@ int fd_gemm_rows_launch(const fd_conv_params &p, hipStream_t s) {
     int gx = (256 * ((cap > 0 && per_cu > cap) ? cap : per_cu) + p.B - 1) / p.B;
     const int need = (wtiles + nt / 64 - 1) / (nt / 64);
     if (gx > need) gx = need;
-    dim3 grid(gx, p.B);
-    if (zre) {
+    q.kid = 10;
+    q.KS = KS;
+    q.PRO = p.prologue;
+    q.EPI = p.epilogue;
+    q.NT = nt;
+    q.S = zre ? 1 : px / 16;
+    q.wtiles = wtiles;
+    q.gx = gx;
+    q.lds = (int)lds;
+    q.zre = zre ? (K == 128 ? 1 : 2) : 0;
+    return 1;
+}
+
+// form[FD_ROWS_FORM_FIELDS] = the fields of fd_rows_plan in their order; 1 when `p` runs on the row-GEMM, 0 (form untouched) otherwise
+extern "C" int fd_gemm_rows_form(const fd_conv_params *pp, int *form) {
+    fd_rows_plan q;
+    if (!pp || !form || !fd_conv_prologue_ok(pp) || !rows_plan(*pp, q)) return 0;
+    const int f[FD_ROWS_FORM_FIELDS] = {q.kid, q.KS, q.PRO, q.EPI, q.NT, q.S, q.wtiles, q.gx, q.lds, q.zre};
+    for (int i = 0; i < FD_ROWS_FORM_FIELDS; ++i) form[i] = f[i];
+    return 1;
+}
+
+// 0: launched; -1: no kernel for `p` (fd_conv2d raises)
+int fd_gemm_rows_launch(const fd_conv_params &p, hipStream_t s) {
+    if (p.dtype == FD_F32) return fd_gemm_rows32_launch(p, s);
+    fd_rows_plan q;
+    if (!rows_plan(p, q)) return -1;
+    const int KS = q.KS, nt = q.NT, wtiles = q.wtiles, RS = row_stride(32 * KS);
+    const size_t lds = (size_t)q.lds;
+    dim3 grid(q.gx, p.B);
+    if (q.zre) {
         const bool nopf = fd_dev(FD_DEV_ZRE_NOPF);      // development
-        if (K == 128 && nopf) hipLaunchKernelGGL((gemm_rows_zre_kernel<4, 256, false>), grid, dim3(256), lds, s, p, wtiles);
-        else if (K == 128) hipLaunchKernelGGL((gemm_rows_zre_kernel<4, 256, true>), grid, dim3(256), lds, s, p, wtiles);
+        if (q.zre == 1 && nt != 256) return -1;
+        if (q.zre == 1 && nopf) hipLaunchKernelGGL((gemm_rows_zre_kernel<4, 256, false>), grid, dim3(256), lds, s, p, wtiles);
+        else if (q.zre == 1) hipLaunchKernelGGL((gemm_rows_zre_kernel<4, 256, true>), grid, dim3(256), lds, s, p, wtiles);
         else {
             // K = 256: 64 KB of out_proj + 64 KB of W_z rows -- one workgroup per CU, so its waves are the CU's waves
             (void)hipFuncSetAttribute((const void *)gemm_rows_zre_kernel<8, ZRE8_NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -587,7 +636,8 @@ int fd_gemm_rows_launch(const fd_conv_params &p, hipStream_t s) {
         }
         return 0;
     }
-#define FD_GR(KS_, PRO_, EPI_) launch_rows<KS_, PRO_, EPI_>(p, nt, grid, lds, wtiles, RS, s)
+    bool ok = false;
+#define FD_GR(KS_, PRO_, EPI_) ok = launch_rows<KS_, PRO_, EPI_>(p, nt, grid, lds, wtiles, RS, s)
 #define FD_GR_K(PRO_, EPI_)                            \
     switch (KS) {                                      \
     case 1: FD_GR(1, PRO_, EPI_); break;               \
@@ -616,5 +666,5 @@ int fd_gemm_rows_launch(const fd_conv_params &p, hipStream_t s) {
     }
 #undef FD_GR_K
 #undef FD_GR
-    return 0;
+    return ok ? 0 : -1;
 }

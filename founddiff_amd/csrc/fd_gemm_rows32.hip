@@ -399,17 +399,22 @@ size_t rows32_lds(const fd_conv_params &p) {
     return 2 * (size_t)p.Cout * row_stride32(K) + 3 * (size_t)K * sizeof(float);
 }
 
+// false: the plan names a workgroup size that was not compiled -- nothing is launched
 template <int KS, int PRO, int EPI>
-void launch_rows32(const fd_conv_params &p, int nt, dim3 grid, size_t lds, int wtiles, int RS, hipStream_t s) {
+bool launch_rows32(const fd_conv_params &p, int nt, dim3 grid, size_t lds, int wtiles, int RS, hipStream_t s) {
     if (nt == 256) {
         if (lds > 64 * 1024)
             (void)hipFuncSetAttribute((const void *)gemm_rows32_kernel<KS, PRO, EPI, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((gemm_rows32_kernel<KS, PRO, EPI, 256>), grid, dim3(256), lds, s, p, wtiles, RS);
-    } else {
+        return true;
+    }
+    if (nt == 512) {
         if (lds > 64 * 1024)
             (void)hipFuncSetAttribute((const void *)gemm_rows32_kernel<KS, PRO, EPI, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((gemm_rows32_kernel<KS, PRO, EPI, 512>), grid, dim3(512), lds, s, p, wtiles, RS);
+        return true;
     }
+    return false;
 }
 
 }  // namespace
@@ -451,8 +456,12 @@ int fd_rows32_ok(const fd_conv_params &p) {
     return 1;
 }
 
-int fd_gemm_rows32_launch(const fd_conv_params &p, hipStream_t s) {
-    const int K = p.c0 + p.c1, KS = K / 32, RS = row_stride32(K);
+// The one place where the kernel, its workgroup size and the grid of an fp32-storage launch are decided (host only).
+// 0: `p` has no kernel here.
+int fd_gemm_rows32_plan(const fd_conv_params &p, fd_rows_plan &q) {
+    const int K = p.c0 + p.c1, KS = K / 32;
+    if (KS != 1 && KS != 2 && KS != 3 && KS != 4 && KS != 6 && KS != 8) return 0;
+    if (p.epilogue < FD_EPI_NONE || p.epilogue > FD_EPI_GNSILU_ADD_FINAL) return 0;
     const int64_t hw = (int64_t)p.H * p.W;
     const int wtiles = (int)((hw + 15) / 16);
     const size_t lds = rows32_lds(p);
@@ -465,14 +474,35 @@ int fd_gemm_rows32_launch(const fd_conv_params &p, hipStream_t s) {
     int gx = (256 * per_cu + p.B - 1) / p.B;
     const int need = (wtiles + nt / 64 - 1) / (nt / 64);
     if (gx > need) gx = need;
-    dim3 grid(gx, p.B);
-    if (p.prologue == FD_PRO_LN_GATE_ZRE) {
+    q.kid = 17;
+    q.KS = KS;
+    q.PRO = p.prologue;
+    q.EPI = p.epilogue;
+    q.NT = nt;
+    q.S = 1;
+    q.wtiles = wtiles;
+    q.gx = gx;
+    q.lds = (int)lds;
+    q.zre = p.prologue == FD_PRO_LN_GATE_ZRE ? 3 : 0;
+    return 1;
+}
+
+// 0: launched; -1: no kernel for `p` (fd_conv2d raises)
+int fd_gemm_rows32_launch(const fd_conv_params &p, hipStream_t s) {
+    fd_rows_plan q;
+    if (!fd_gemm_rows32_plan(p, q)) return -1;
+    const int KS = q.KS, nt = q.NT, wtiles = q.wtiles, RS = row_stride32(32 * KS);
+    const size_t lds = (size_t)q.lds;
+    dim3 grid(q.gx, p.B);
+    if (q.zre) {
+        if (nt != 256) return -1;
         if (lds > 64 * 1024)
             (void)hipFuncSetAttribute((const void *)gemm_rows32_zre_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((gemm_rows32_zre_kernel<256>), grid, dim3(256), lds, s, p, wtiles);
         return 0;
     }
-#define FD_GR(KS_, PRO_, EPI_) launch_rows32<KS_, PRO_, EPI_>(p, nt, grid, lds, wtiles, RS, s)
+    bool ok = false;
+#define FD_GR(KS_, PRO_, EPI_) ok = launch_rows32<KS_, PRO_, EPI_>(p, nt, grid, lds, wtiles, RS, s)
 #define FD_GR_K(PRO_, EPI_)                            \
     switch (KS) {                                      \
     case 1: FD_GR(1, PRO_, EPI_); break;               \
@@ -501,5 +531,5 @@ int fd_gemm_rows32_launch(const fd_conv_params &p, hipStream_t s) {
     }
 #undef FD_GR_K
 #undef FD_GR
-    return 0;
+    return ok ? 0 : -1;
 }

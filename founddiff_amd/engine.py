@@ -417,7 +417,8 @@ class DAEngine:
         """One fd_conv2d launch.  `probe=True` only asks the library whether this conv can take the
         fused LayerNorm prologue (bf16 streaming row-GEMM path) and launches nothing; `probe="kid"`
         returns fd_conv_kernel_id (tests pin which kernel a shape exercises), `probe="form"` fd_conv_form (the id and
-        whether the pointwise loader runs)."""
+        whether the pointwise loader runs), `probe="rows"` the streaming row-GEMM's launch plan (fd_gemm_rows_form as a dict:
+        kernel instantiation, workgroup size, grid), None when the conv does not run there."""
         def ptr(v):
             if v is None:
                 return None
@@ -487,6 +488,8 @@ class DAEngine:
             return int(self.hip.lib().fd_conv_kernel_id(C.byref(p)))
         if probe == "form":         # ... and with which loader: kid | pw << 8 (fd_conv_form)
             return int(self.hip.lib().fd_conv_form(C.byref(p)))
+        if probe == "rows":         # the row-GEMM's plan (fd_gemm_rows_form)
+            return L.rows_form(self.hip.lib(), p)
         if probe:
             return bool(self.hip.lib().fd_conv_prologue_ok(C.byref(p)))
         self.hip.call("fd_conv2d", C.byref(p), self.stream)

@@ -181,6 +181,18 @@ int fd_conv_kernel_id(const fd_conv_params *p);
 /* fd_conv_kernel_id(p) | pw << 8: pw = 1 when an implicit-GEMM tile (ids 0..6) runs with the bf16 pointwise loader (1x1, stride 1,
  * Cin and c0 multiples of 64, 8-channel-aligned output, no GroupNorm sums) instead of the general gather.  Host only.       */
 int fd_conv_form(const fd_conv_params *p);
+/* The launch plan of the streaming row-GEMM (fd_conv_kernel_id 10 and 17) for p.  Host only: touches no device.  Returns 1 and fills
+ * form[0 .. 9] when p runs there (fd_conv_prologue_ok), 0 (form untouched) otherwise.  Field order:
+ *   [0] kernel id: 10 = 16-bit storage, 17 = fp32 storage with split-bf16 contractions
+ *   [1] KS = Cin / 32   [2] PRO = p.prologue (3: a z-recompute kernel, see [9])   [3] EPI = p.epilogue
+ *   [4] NT: threads per workgroup, 256 / 512 / 768 from the LDS bytes of the weight image and the register budget of (KS, PRO)
+ *   [5] S: 16-pixel subtiles per wave iteration (2 for Cin <= 64 in 16-bit storage, else 1)
+ *   [6] wtiles = ceil(H * W / (16 S)): wave tiles per image   [7] grid x (grid y = B); wave w of workgroup x walks the tiles
+ *       x * NT/64 + w, + grid x * NT/64, ...   [8] dynamic LDS bytes
+ *   [9] z-recompute kernel: 0 none, 1 = 16-bit Cin 128, 2 = 16-bit Cin 256, 3 = fp32 storage Cin 128
+ * fd_conv2d launches exactly this plan, and fails (rather than launch nothing) if no kernel was compiled for it.
+ * FD_EPI_GNSILU_ADD_FINAL stores nothing through p.out: the block output exists only inside the fin_w dot product.            */
+int fd_gemm_rows_form(const fd_conv_params *p, int *form);
 int fd_conv2d(const fd_conv_params *p, void *stream);
 
 /* GroupNorm statistics from the conv's partial sums -> mean_rstd [B][G][2] (nn.GroupNorm,

@@ -7,8 +7,9 @@ of its coverage list.  The reference is conv_cases.conv_reference: explicit gath
 Which test pins which id of fd_conv_kernel_id (probe="kid" / "form" / True before the launch it compares with a reference):
   0, 1, 2, 3, 4, 5, 6   test_conv_form here (fd_conv_form: the id and the loader), every one in all four element forms
   5, 7                  test_gpu_kernels.py::test_pointwise_gemm_256_tile; 7 also test_gpu_round6.py::test_pointwise_gemm_gate_table_batch_groups
-  10                    test_gpu_kernels.py::test_row_gemm_fused_prologues, test_row_gemm_final_conv_ddim_epilogue (fd_conv_prologue_ok)
-  17                    test_gpu_round6.py::test_row_gemm_fp32_storage_split_bf16
+  10, 17                test_gpu_rows_forms.py::test_rows_form (fd_gemm_rows_form: every instantiation, workgroup size and tile walk of both)
+  10                    also test_gpu_kernels.py::test_row_gemm_fused_prologues, test_row_gemm_final_conv_ddim_epilogue (fd_conv_prologue_ok)
+  17                    also test_gpu_round6.py::test_row_gemm_fp32_storage_split_bf16
   11                    test_gpu_kernels.py::test_conv3x3_halo, test_conv3x3_weights_in_registers (its 128-channel twin)
   12                    test_gpu_kernels.py::test_conv3x3_fp8_weights
   13                    test_gpu_kernels.py::test_conv3x3_weights_in_registers
