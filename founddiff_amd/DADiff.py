@@ -595,10 +595,22 @@ class ResidualDiffusion(nn.Module):
             grp = max(grp - grp % self.streams, self.streams)
         return grp
 
+    def _plan_unets(self):
+        """The U-Nets this plan evaluates, unet0 first."""
+        _, r0, r1, _ = self._plan()
+        return ([self.model.unet0] if r0 else []) + ([self.model.unet1] if r1 else [])
+
     def _engines(self):
         """The engines of this plan's U-Nets in the slot of the running sub-batch (slot 0 outside _sample_concurrent)."""
+        return [u.engine(slot=self._slot) for u in self._plan_unets()]
+
+    def _o01(self, outs):
+        """(o0, o1) as the step kernels (fd_res_step_obj*, fd_tiles_step_*) take them, from the raw outputs of _plan_unets() in
+        that order.  The single U-Net of 'pred_noise' predicts the noise: its output is the kernels' o1."""
         mode, r0, r1, _ = self._plan()
-        return ([self.model.unet0.engine(slot=self._slot)] if r0 else []) + ([self.model.unet1.engine(slot=self._slot)] if r1 else [])
+        if mode == 1 and r0:
+            return None, outs[0]
+        return outs[0] if r0 else None, outs[-1] if r1 else None
 
     # ---- the step tables of the captured loops of every plan: pure host functions of the schedule (tests/test_obj_loop_cpu.py)
     def _obj_time_tables(self):
@@ -621,21 +633,25 @@ class ResidualDiffusion(nn.Module):
         times = list(reversed(torch.linspace(-1, self.num_timesteps - 1, steps=self.sampling_timesteps + 1).int().tolist()))
         return list(zip(times[:-1], times[1:]))
 
+    def _ddim_steps(self):
+        """[(time, alpha, last)]: the steps of every DDIM loop -- the timestep, the alpha increment of its update, the last-step flag."""
+        acs = self._hs()["alphas_cumsum"]
+        return [(time, 0.0 if time_next < 0 else float(acs[time] - acs[time_next]), time_next < 0)
+                for time, time_next in self._ddim_pairs()]
+
     def _obj_ddim_table(self, B):
         """((S, B, 8) parameter rows, (S, B) time inputs of unet0 or None, of unet1 or None), fp32 CPU: step i of the DDIM loop as
         _generic_loop runs it -- {ac, bc, omac, alpha, 0, 0, 0, last} of _par and the time inputs of _outputs."""
         hs = self._hs()
-        acs = hs["alphas_cumsum"]
         t0, t1 = self._obj_time_tables()
-        pairs = self._ddim_pairs()
-        par = torch.zeros(len(pairs), B, 8, dtype=torch.float32)
-        for i, (time, time_next) in enumerate(pairs):
-            lastf = time_next < 0
-            par[i, :, 0], par[i, :, 1], par[i, :, 2] = acs[time], hs["betas_cumsum"][time], hs["one_minus_alphas_cumsum"][time]
-            par[i, :, 3] = 0.0 if lastf else float(acs[time] - acs[time_next])
+        steps = self._ddim_steps()
+        par = torch.zeros(len(steps), B, 8, dtype=torch.float32)
+        for i, (time, alpha, lastf) in enumerate(steps):
+            par[i, :, 0], par[i, :, 1], par[i, :, 2] = hs["alphas_cumsum"][time], hs["betas_cumsum"][time], hs["one_minus_alphas_cumsum"][time]
+            par[i, :, 3] = alpha
             par[i, :, 7] = float(lastf)
-        idx = torch.tensor([t for t, _ in pairs], dtype=torch.long)
-        rows = lambda tab: None if tab is None else tab[idx][:, None].expand(len(pairs), B).contiguous()
+        idx = torch.tensor([t for t, _, _ in steps], dtype=torch.long)
+        rows = lambda tab: None if tab is None else tab[idx][:, None].expand(len(steps), B).contiguous()
         return par.contiguous(), rows(t0), rows(t1)
 
     def _encode_all(self, x_in, cond=None):
@@ -657,15 +673,9 @@ class ResidualDiffusion(nn.Module):
         T = self.num_timesteps
         t0 = ((self.alphas_cumsum if tsel0 == 0 else self.betas_cumsum)[t_idx] * T).float().contiguous()
         t1 = (self.betas_cumsum[t_idx] * T).float().contiguous()
-        o0 = o1 = None
         c2 = self._xc2 if self.input_condition else None
-        if mode == 1 and r0:                    # single-UNet pred_noise: its output plays the role of o1
-            o1 = self.model.unet0.engine().forward(x, x_in, t0, x_cond2=c2).clone()
-        elif r0:
-            o0 = self.model.unet0.engine().forward(x, x_in, t0, x_cond2=c2).clone()
-        if r1:
-            o1 = self.model.unet1.engine().forward(x, x_in, t1, x_cond2=c2).clone()
-        return mode, o0, o1
+        times = ([t0] if r0 else []) + ([t1] if r1 else [])
+        return (mode,) + self._o01([u.engine().forward(x, x_in, t, x_cond2=c2).clone() for u, t in zip(self._plan_unets(), times)])
 
     def _set_cond2(self, x_input_condition):
         """third input plane (src/DADiff.py:1157-1158); already normalised by the caller / sample()."""
@@ -884,10 +894,14 @@ class ResidualDiffusion(nn.Module):
             noise = keyed(s) if s is not None else torch.randn(size, device=dev)
         return noise, s
 
-    def _x_T(self, x_in, noise, img):
-        """img <- x_T = x_in + sqrt(sum_scale) * noise; returns a copy of it, the first image of what a loop returns"""
+    def _x_T_into(self, x_in, noise, img):
+        """img <- x_T = x_in + sqrt(sum_scale) * noise"""
         L.call("fd_axpy_f32", _p(x_in), _p(noise.contiguous()), math.sqrt(self.sum_scale), _p(img), img.numel(), _stream(img))
-        return img.clone()
+        return img
+
+    def _x_T(self, x_in, noise, img):
+        """_x_T_into; returns a copy of x_T, the first image of what a loop returns"""
+        return self._x_T_into(x_in, noise, img).clone()
 
     def _finish(self, input_add_noise, img, img_list, last):
         return unnormalize_to_zero_to_one([input_add_noise, img.clone()] if last else [input_add_noise] + img_list)
@@ -912,10 +926,7 @@ class ResidualDiffusion(nn.Module):
             return self._generic_loop(x_input, shape, last, noise, step_noise, ddim=False, cond=_cond)
         x_in, img, mo, time_buf = self._loop_buffers(x_input, shape)
         eng = self._eng()
-        if _cond is None:
-            eng.encode_condition(x_in)
-        else:
-            eng.load_condition(*_cond[0])
+        self._encode_all(x_in, _cond)
         noise, seeds = self._noise_and_seeds("loop", shape, x_in.device, noise, slice_seeds, step_noise)
         input_add_noise = self._x_T(x_in, noise, img)
         hs = self._hs()
@@ -969,44 +980,63 @@ class ResidualDiffusion(nn.Module):
                    B, npix, _stream(img))
 
         K = max(0, min(int(K), T))                                # a tail longer than the loop is the whole loop
-        n_main = T - K
-        if not (self.use_graph and last):
-            for i in range(T):
-                one(eng if i < n_main else e32)
-                if not last:
-                    img_list.append(img.clone())
-            return
-        # G steps per captured chunk: the largest divisor of n_main in [8, 64]; when there is none (n_main prime or
-        # small) a fixed 40 with the n_main % 40 leftover steps run eagerly in front of the replays
-        G = max([g for g in range(8, 65) if n_main > 0 and n_main % g == 0] or [40])
-        key = (tuple(img.shape), eng.mode, eng.gen, G, K, e32.gen if e32 else 0, self.final_outer_levels, self.final_down_levels, T)
-        reps, rem = n_main // G, n_main % G
+        key = lambda G: (tuple(img.shape), eng.mode, eng.gen, G, K, e32.gen if e32 else 0, self.final_outer_levels,
+                         self.final_down_levels, T)
 
         def warm():
             eng.forward(img, x_in, time_buf, out=mo)
             if e32 is not None:
                 self._tail_forward(e32, eng, img, x_in, time_buf, mo)
+        self._anc_run(eng, "anc", key, warm, lambda: one(eng), img, t_dev, T - K, tail=lambda: one(e32), K=K,
+                      graph=self.use_graph and last, each=None if last else lambda: img_list.append(img.clone()))
 
-        def record(capture):
-            start, t0 = img.clone(), t_dev.clone()
-            gm = capture(lambda: [one(eng) for _ in range(G)]) if reps > 0 else None
-            gt = capture(lambda: [one(e32) for _ in range(K)]) if K > 0 else None
-            img.copy_(start)                                      # capture does not execute: restore x_T and the step counter
-            t_dev.copy_(t0)
-            return gm, gt
-        gm, gt = eng.captured("anc", key, warm, record)
-        lim = getattr(self, "_anc_max_chunks", None)          # bench.py's bounded leg: time a few chunks, not the volume
+    def _anc_chunks(self, n):
+        """(G, reps, rem): n ancestral steps as `rem` single steps in front of `reps` chunks of G.  G is the largest divisor of n
+        in [8, 64]; when there is none (n prime or small) a fixed 40, with n % 40 single steps.  _anc_max_chunks (bench.py's
+        bounded leg: time a few chunks, not the volume) keeps at most that many chunks and no single step."""
+        G = max([g for g in range(8, 65) if n > 0 and n % g == 0] or [40])
+        reps, rem = n // G, n % G
+        lim = getattr(self, "_anc_max_chunks", None)
         if lim:
             reps, rem = min(reps, int(lim)), 0
-        for _ in range(rem):
-            one(eng)
+        return G, reps, rem
+
+    @staticmethod
+    def _keeping(do, *state):
+        """do() with the tensors `state` as they were before it: a capture does not execute, and what it records must not be
+        left half-applied -- x_T, and the step counter of the ancestral loops, are put back."""
+        saved = [t.clone() for t in state]
+        res = do()
+        for t, t0 in zip(state, saved):
+            t.copy_(t0)
+        return res
+
+    def _anc_run(self, own, kind, key, warm, step, img, t_dev, n, tail=None, K=0, graph=True, each=None):
+        """The chunked ancestral loop of every plan: n main steps `step()` (_anc_chunks: single steps, then chunks of G) and K tail
+        steps `tail()`, the step counter t_dev running down on the device.  graph: a chunk is ONE graph of `own` under `kind` and
+        key(G), replayed; the K tail steps are a second graph of the same entry.  Otherwise every step runs eagerly, `each()` after
+        it.  Where _anc_max_chunks cut main steps off, the counter jumps to the tail.  Writes _anc_steps_run."""
+        G, reps, rem = self._anc_chunks(n)
+        done = rem + reps * G
+
+        def run(fn, count):
+            for _ in range(count):
+                fn()
+                if each is not None:
+                    each()
+        chunk, tail_k = (lambda: run(step, G)), (lambda: run(tail, K))
+        if graph and (reps > 0 or K > 0):
+            gm, gt = own.captured(kind, key(G), warm, lambda capture: self._keeping(
+                lambda: (capture(chunk) if reps > 0 else None, capture(tail_k) if K > 0 else None), img, t_dev))
+            chunk, tail_k = gm.replay if reps > 0 else None, gt.replay if K > 0 else None
+        run(step, rem)
         for _ in range(reps):
-            gm.replay()
-        if gt is not None:
-            if lim:
-                t_dev.fill_(K)                                # jump to the tail steps
-            gt.replay()
-        self._anc_steps_run = rem + reps * G + K
+            chunk()
+        if K > 0:
+            if done < n:
+                t_dev.fill_(K)                                    # jump to the tail steps
+            tail_k()
+        self._anc_steps_run = done + K
 
     @property
     def time_table(self):
@@ -1026,14 +1056,9 @@ class ResidualDiffusion(nn.Module):
             return self._generic_loop(x_input, shape, last, noise, None, ddim=True, cond=_cond)
         x_in, img, mo, time_buf = self._loop_buffers(x_input, shape)
         eng = self._eng()
-        if _cond is None:
-            eng.encode_condition(x_in)
-        else:
-            eng.load_condition(*_cond[0])
+        self._encode_all(x_in, _cond)
         T, S = self.num_timesteps, self.sampling_timesteps
-        times = torch.linspace(-1, T - 1, steps=S + 1)
-        times = list(reversed(times.int().tolist()))
-        time_pairs = list(zip(times[:-1], times[1:]))
+        steps = self._ddim_steps()
         if noise is None:
             noise = torch.randn(shape, device=x_in.device)
         input_add_noise = self._x_T(x_in, noise, img)
@@ -1050,9 +1075,7 @@ class ResidualDiffusion(nn.Module):
             per step."""
             if fold and self.time_table:
                 eng.time_cond_table()
-            for i, (time, time_next) in enumerate(time_pairs):
-                lastf = time_next < 0
-                alpha = 0.0 if lastf else float(acs[time] - acs[time_next])
+            for i, (time, alpha, lastf) in enumerate(steps):
                 if fold and self.time_table and i < S - K:
                     forward(eng, (alpha, lastf), i)
                     continue
@@ -1080,17 +1103,13 @@ class ResidualDiffusion(nn.Module):
 
             def warm():
                 if self.time_table:                                # (host -> device copy and buffers: before the capture)
-                    eng.time_table_prepare([acs[t] * T for t, _ in time_pairs], shape[0])
+                    eng.time_table_prepare([acs[t] * T for t, _, _ in steps], shape[0])
                     eng.time_cond_table()
                 for e in (eng, e32):
                     if e is not None:
                         fwd(e)
 
-            def record(capture):
-                start = img.clone()
-                g = capture(lambda: run_steps(fwd, fold=True))
-                img.copy_(start)                                   # capture does not execute: restore x_T
-                return g
+            record = lambda capture: self._keeping(lambda: capture(lambda: run_steps(fwd, fold=True)), img)
             eng.captured("ddim_loop", key, warm, record).replay()
         else:
             run_steps(lambda e: self._step_forward(x_in, img, time_buf, mo, e, tail_of=None if e is eng else eng))
@@ -1099,8 +1118,8 @@ class ResidualDiffusion(nn.Module):
     # ---- the captured loops of every plan other than the shipped one
     def _obj_buffers(self, x_input, shape, cond):
         """The persistent loop buffers of this plan on the engines of the running slot, x_in loaded and the conditioning of every
-        engine in place: (engines, mode, x_in, img, (o0, o1) as the step kernels take them, ((engine, time buffer, output buffer)
-        of unet0, the same of unet1)) -- None where the plan does not run that U-Net."""
+        engine in place: (engines, mode, x_in, img, (o0, o1) as the step kernels take them, [(engine, time buffer, output buffer)
+        of unet0, the same of unet1]) -- (None, None, None) where the plan does not run that U-Net."""
         mode, r0, r1, _ = self._plan()
         engines = self._engines()
         own = engines[0]                                          # holds what the U-Nets share, and the loop's graph
@@ -1108,15 +1127,9 @@ class ResidualDiffusion(nn.Module):
         x_in.copy_(x_input)
         img = own._b("obj_img", shape, torch.float32)
         self._encode_all(x_in, cond)
-        e0 = engines[0] if r0 else None
-        e1 = engines[-1] if r1 else None
-        out0 = e0._b("obj_out", shape, torch.float32) if e0 else None
-        out1 = e1._b("obj_out", shape, torch.float32) if e1 else None
-        tb0 = e0._b("obj_time", (shape[0],), torch.float32) if e0 else None
-        tb1 = e1._b("obj_time", (shape[0],), torch.float32) if e1 else None
-        # the single U-Net of 'pred_noise' predicts the noise: its output is the kernels' o1
-        outs = (None, out0) if (mode == 1 and r0) else (out0, out1)
-        return engines, mode, x_in, img, outs, ((e0, tb0, out0), (e1, tb1, out1))
+        nets = [(e, e._b("obj_time", (shape[0],), torch.float32), e._b("obj_out", shape, torch.float32)) if e else (None, None, None)
+                for e in (engines[0] if r0 else None, engines[-1] if r1 else None)]
+        return engines, mode, x_in, img, self._o01([out for _, _, out in nets if out is not None]), nets
 
     def _obj_key(self, engines, shape):
         return (tuple(shape), self._plan(), self.num_timesteps) + tuple((e.mode, e.gen) for e in engines)
@@ -1143,24 +1156,19 @@ class ResidualDiffusion(nn.Module):
             noise = torch.randn(shape, device=x_in.device)
         input_add_noise = self._x_T(x_in, noise, img)
 
+        def forwards(i):
+            for e, gt, out in tabs:
+                e.forward(img, x_in, gt[i], out=out)
+
         def run():
             for i in range(S):
-                for e, gt, out in tabs:
-                    e.forward(img, x_in, gt[i], out=out)
+                forwards(i)
                 L.call("fd_res_step_obj", mode, 1, _p(o0), _p(o1), _p(img), _p(x_in), None, _p(gpar[i]), None, None, None,
                        _p(img), B, npix, _stream(img))
 
         if self.use_graph:
-            def warm():
-                for e, gt, out in tabs:
-                    e.forward(img, x_in, gt[0], out=out)
-
-            def record(capture):
-                start = img.clone()
-                g = capture(run)
-                img.copy_(start)                                   # capture does not execute: restore x_T
-                return g
-            own.captured("obj_ddim", self._obj_key(engines, shape) + (S,), warm, record).replay()
+            own.captured("obj_ddim", self._obj_key(engines, shape) + (S,), lambda: forwards(0),
+                         lambda capture: self._keeping(lambda: capture(run), img)).replay()
         else:
             run()
         return self._finish(input_add_noise, img, [], True)
@@ -1169,8 +1177,8 @@ class ResidualDiffusion(nn.Module):
         """p_sample_loop(last=True) of a plan other than the shipped one, step noise keyed by `seeds`: T steps of fd_obj_begin
         (t <- t - 1 on the device, both time inputs) -> one forward per U-Net of the plan, one after the other on the same stream
         -> fd_res_step_obj_keyed (row t of the (T, 8) table, keyed noise, in place on img).  use_graph: replays of one captured
-        chunk of G steps (kind "obj_anc", _ancestral_keyed's rule for G); otherwise the same three launches eagerly, one step at
-        a time -- the same bits.  There is no precision tail: _anc_max_chunks simply stops after that many chunks."""
+        chunk of G steps (kind "obj_anc", _anc_run); otherwise the same three launches eagerly, one step at a time -- the same
+        bits.  There is no precision tail: _anc_max_chunks simply stops after that many chunks."""
         engines, mode, x_in, img, (o0, o1), nets = self._obj_buffers(x_input, shape, cond)
         own = engines[0]
         T, B = self.num_timesteps, shape[0]
@@ -1179,50 +1187,28 @@ class ResidualDiffusion(nn.Module):
         gpar, gse = own._b("obj_anc_par", (T, 8), torch.float32), own._b("obj_seeds", (B,), torch.int64)
         gpar.copy_(self._obj_anc_table())
         gse.copy_(seeds)
-        runs, gts = [], [None, None]
-        for i, ((e, tb, out), tt) in enumerate(zip(nets, self._obj_time_tables())):
+        gts = [None, None]
+        for i, ((e, tb, _), tt) in enumerate(zip(nets, self._obj_time_tables())):
             if e is not None:
                 gts[i] = e._b("obj_anc_time", (T,), torch.float32)
                 gts[i].copy_(tt)
                 tb.zero_()
-                runs.append((e, tb, out))
         (_, tb0, _), (_, tb1, _) = nets
-        gt0, gt1 = gts
         input_add_noise = self._x_T(x_in, noise, img)
         t_dev.fill_(T)
 
-        def one():
-            L.call("fd_obj_begin", _p(t_dev), _p(gt0), _p(gt1), _p(tb0), _p(tb1), B, T, _stream(img))
-            for e, tb, out in runs:
-                e.forward(img, x_in, tb, out=out)
-            L.call("fd_res_step_obj_keyed", mode, _p(o0), _p(o1), _p(img), _p(x_in), _p(gpar), _p(t_dev), _p(gse), _p(img),
-                   B, npix, T, _stream(img))
-
-        G = max([g for g in range(8, 65) if T % g == 0] or [40])
-        reps, rem = T // G, T % G
-        lim = getattr(self, "_anc_max_chunks", None)
-        if lim:
-            reps, rem = min(reps, int(lim)), 0
-        if self.use_graph:
-            def warm():
-                for e, tb, out in runs:
+        def forwards():
+            for e, tb, out in nets:
+                if e is not None:
                     e.forward(img, x_in, tb, out=out)
 
-            def record(capture):
-                start, t0 = img.clone(), t_dev.clone()
-                g = capture(lambda: [one() for _ in range(G)])
-                img.copy_(start)                                  # capture does not execute: restore x_T and the step counter
-                t_dev.copy_(t0)
-                return g
-            gm = own.captured("obj_anc", self._obj_key(engines, shape) + (G,), warm, record) if reps > 0 else None
-            for _ in range(rem):
-                one()
-            for _ in range(reps):
-                gm.replay()
-        else:
-            for _ in range(rem + reps * G):
-                one()
-        self._anc_steps_run = rem + reps * G
+        def one():
+            L.call("fd_obj_begin", _p(t_dev), _p(gts[0]), _p(gts[1]), _p(tb0), _p(tb1), B, T, _stream(img))
+            forwards()
+            L.call("fd_res_step_obj_keyed", mode, _p(o0), _p(o1), _p(img), _p(x_in), _p(gpar), _p(t_dev), _p(gse), _p(img),
+                   B, npix, T, _stream(img))
+        self._anc_run(own, "obj_anc", lambda G: self._obj_key(engines, shape) + (G,), forwards, one, img, t_dev, T,
+                      graph=self.use_graph)
         return self._finish(input_add_noise, img, [], True)
 
     def _generic_loop(self, x_in, shape, last, noise, step_noise, ddim, cond=None):
@@ -1236,21 +1222,15 @@ class ResidualDiffusion(nn.Module):
             noise = torch.randn(shape, device=x_in.device)
         img = torch.empty_like(x_in)
         input_add_noise = self._x_T(x_in, noise, img)
-        hs = self._hs()
-        T = self.num_timesteps
         img_list = []
         if ddim:
-            times = list(reversed(torch.linspace(-1, T - 1, steps=self.sampling_timesteps + 1).int().tolist()))
-            acs = hs["alphas_cumsum"]
-            for time, time_next in zip(times[:-1], times[1:]):
+            for time, alpha, lastf in self._ddim_steps():
                 t_idx = torch.full((B,), time, device=x_in.device, dtype=torch.long)
-                lastf = time_next < 0
-                alpha = 0.0 if lastf else float(acs[time] - acs[time_next])
                 img = self._step_obj(1, x_in, img, t_idx, None, k=(alpha, 0., 0., 0.), flag=float(lastf))[0]
                 if not last:
                     img_list.append(img.clone())
         else:
-            for t in reversed(range(0, T)):
+            for t in reversed(range(0, self.num_timesteps)):
                 nz = None
                 if t > 0:
                     nz = step_noise(t) if step_noise is not None else torch.randn(shape, device=x_in.device)
@@ -1265,22 +1245,28 @@ class ResidualDiffusion(nn.Module):
         `slice_seeds` (B int64): per-slice keys of the ancestral sampler's step noise (and of x_T when `noise` is not
         given) -- see p_sample_loop; founddiff_amd.parallel.sample_volume passes seed + GLOBAL slice index."""
         x_input = list(x_input)
-        res = self._sample(x_input, batch_size, last, noise, step_noise, slice_seeds)
-        if self.model.unet0.kernel_precision == "fp16" and self.check_fp16_range:
-            # binary16 ends at 65504: an activation beyond it is stored as infinity and reaches the image as NaN (the clamps of
-            # the scheduler kernels propagate NaN like torch.clamp).  One reduction + one host read per sample() call.
-            if not bool(torch.isfinite(res[-1]).all()):
-                if self.model.unet0.precision != "auto":
-                    raise L.FoundDiffHipError(
-                        "precision='fp16': the sampled image is not finite -- an activation of this checkpoint left IEEE binary16's "
-                        "range (65504).  Use precision='bf16' (same speed, fp32's range, 8 significand bits), 'auto' or 'fp32s'.")
-                import warnings
-                warnings.warn("founddiff_amd: precision='auto': this checkpoint's activations leave IEEE binary16's range; "
-                              "this and every later sample() of the model run on the bfloat16 kernels")
-                for u in (getattr(self.model, "unet0", None), getattr(self.model, "unet1", None)):
-                    if u is not None:
-                        u._auto_bf16 = True
-                res = self._sample(x_input, batch_size, last, noise, step_noise, slice_seeds)
+        return self._range_checked(lambda: self._sample(x_input, batch_size, last, noise, step_noise, slice_seeds),
+                                   "the sampled image", image=lambda res: res[-1])
+
+    def _range_checked(self, run, what, image=lambda res: res):
+        """run(), under the range check of the 'fp16' kernels.  binary16 ends at 65504: an activation beyond it is stored as
+        infinity and reaches the image as NaN (the clamps of the scheduler kernels propagate NaN like torch.clamp).  One reduction
+        + one host read of image(what run returned) per call: precision='fp16' raises, 'auto' moves the model to the bfloat16
+        kernels for good and runs once more."""
+        res = run()
+        if self.model.unet0.kernel_precision == "fp16" and self.check_fp16_range and not bool(torch.isfinite(image(res)).all()):
+            if self.model.unet0.precision != "auto":
+                raise L.FoundDiffHipError(
+                    f"precision='fp16': {what} is not finite -- an activation of this checkpoint "
+                    "left IEEE binary16's range (65504).  Use precision='bf16' (same speed, fp32's range, 8 significand bits), "
+                    "'auto' or 'fp32s'.")
+            import warnings
+            warnings.warn("founddiff_amd: precision='auto': this checkpoint's activations leave IEEE binary16's range; "
+                          "this and every later sample() of the model run on the bfloat16 kernels")
+            for u in (getattr(self.model, "unet0", None), getattr(self.model, "unet1", None)):
+                if u is not None:
+                    u._auto_bf16 = True
+            res = run()
         return res
 
     @torch.no_grad()
@@ -1301,19 +1287,7 @@ class ResidualDiffusion(nn.Module):
         B = x01.shape[0]
         seeds = self._slice_seeds(slice_seeds, B, "cpu")
         rows = torch.from_numpy(ensemble_seeds(seeds.numpy(), K).reshape(-1)).to(x01.device)
-        samples = self._ensemble_rows(x01, K, rows)
-        if self.model.unet0.kernel_precision == "fp16" and self.check_fp16_range and not bool(torch.isfinite(samples).all()):
-            if self.model.unet0.precision != "auto":              # sample()'s rule, applied to the replicas
-                raise L.FoundDiffHipError(
-                    "precision='fp16': a sampled image is not finite -- an activation of this checkpoint left IEEE binary16's "
-                    "range (65504).  Use precision='bf16' (same speed, fp32's range, 8 significand bits), 'auto' or 'fp32s'.")
-            import warnings
-            warnings.warn("founddiff_amd: precision='auto': this checkpoint's activations leave IEEE binary16's range; "
-                          "this and every later sample() of the model run on the bfloat16 kernels")
-            for u in (getattr(self.model, "unet0", None), getattr(self.model, "unet1", None)):
-                if u is not None:
-                    u._auto_bf16 = True
-            samples = self._ensemble_rows(x01, K, rows)
+        samples = self._range_checked(lambda: self._ensemble_rows(x01, K, rows), "a sampled image")
         mean, std, spread = ensemble_stats(samples)
         return EnsembleResult(mean, std, spread, samples if return_samples else None)
 
@@ -1321,21 +1295,10 @@ class ResidualDiffusion(nn.Module):
         """The B K final images (B,K,1,H,W) of sample_ensemble; seeds (B K,) int64 on the device, row b K + k."""
         B, npix = x01.shape[0], x01[0].numel()
         R = B * K
-        s = _stream(x01)
-        engines = self._engines()
         x_n = normalize_to_neg_one_to_one(x01)
-        x_rows = engines[0]._b("ens_xin", (R,) + tuple(x01.shape[1:]), torch.float32)
-        L.call("fd_rows_repeat_f32", _p(x_n), _p(x_rows), B, K, npix, s)
-        # the tower: once per slice, at most max_sub_batch slices at a time (its workspace grows with its batch), on every engine in
-        # use; a slice's rows, repeated for its replicas, stay in buffers of the engine that made them
-        cond = [(e._b("ens_prompt", (R, e.time_dim), torch.float32), e._b("ens_local", (R, e.loc_total), torch.float32))
-                for e in engines]
-        for c0 in range(0, B, self.max_sub_batch):
-            nb = min(self.max_sub_batch, B - c0)
-            for e, (pe, la) in zip(engines, cond):
-                e.encode_condition(x_n[c0:c0 + nb])
-                L.call("fd_rows_repeat_f32", _p(e.prompt_emb), _p(pe[c0 * K:]), nb, K, e.time_dim, s)
-                L.call("fd_rows_repeat_f32", _p(e.local_all), _p(la[c0 * K:]), nb, K, e.loc_total, s)
+        x_rows = self._engines()[0]._b("ens_xin", (R,) + tuple(x01.shape[1:]), torch.float32)
+        L.call("fd_rows_repeat_f32", _p(x_n), _p(x_rows), B, K, npix, _stream(x01))
+        cond = self._cond_repeated("ens", x_n, K, lambda u, e, x: e.encode_condition(x))
         samples = torch.empty((B, K) + tuple(x01.shape[1:]), device=x01.device, dtype=torch.float32)
         flat = samples.view((R,) + tuple(x01.shape[1:]))
         # every plan's ancestral steps take the keyed stream of `sd` inside its captured loop: no step_noise callable
@@ -1425,23 +1388,11 @@ class ResidualDiffusion(nn.Module):
         plan = (ys, xs, wy, wx, my, mx, x4, th, tw)
         s = _stream(x01)
         field = self._keyed_noise(seeds.to(x01.device), self.X_T_STEP, tuple(x01.shape))
-        x_T = torch.empty_like(x01)
-        L.call("fd_axpy_f32", _p(normalize_to_neg_one_to_one(x01)), _p(field), math.sqrt(self.sum_scale), _p(x_T), x_T.numel(), s)
+        x_T = self._x_T_into(normalize_to_neg_one_to_one(x01), field, torch.empty_like(x01))
         if self._tile_fuse == "step":
-            return [unnormalize_to_zero_to_one(x_T), self._tiled_fused(x01, field, seeds.to(x01.device), plan, condition)]
-        tiles = self._tile_rows(x01, field, rows, plan, condition)
-        if self.model.unet0.kernel_precision == "fp16" and self.check_fp16_range and not bool(torch.isfinite(tiles).all()):
-            if self.model.unet0.precision != "auto":              # sample()'s rule, applied to the tiles
-                raise L.FoundDiffHipError(
-                    "precision='fp16': a sampled image is not finite -- an activation of this checkpoint left IEEE binary16's "
-                    "range (65504).  Use precision='bf16' (same speed, fp32's range, 8 significand bits), 'auto' or 'fp32s'.")
-            import warnings
-            warnings.warn("founddiff_amd: precision='auto': this checkpoint's activations leave IEEE binary16's range; "
-                          "this and every later sample() of the model run on the bfloat16 kernels")
-            for u in (getattr(self.model, "unet0", None), getattr(self.model, "unet1", None)):
-                if u is not None:
-                    u._auto_bf16 = True
-            tiles = self._tile_rows(x01, field, rows, plan, condition)
+            return [unnormalize_to_zero_to_one(x_T), self._range_checked(
+                lambda: self._tiled_fused_loop(x01, field, seeds.to(x01.device), plan, condition), "a sampled image")]
+        tiles = self._range_checked(lambda: self._tile_rows(x01, field, rows, plan, condition), "a sampled image")
         out = torch.empty_like(x01)
         L.call("fd_tiles_blend_f32", _p(tiles), _p(wy), _p(wx), _p(ys), _p(xs), _p(out), B, H, W, th, tw, my, mx, x4, s)
         return [unnormalize_to_zero_to_one(x_T), out]
@@ -1453,42 +1404,30 @@ class ResidualDiffusion(nn.Module):
         L.call("fd_tiles_gather_f32", _p(src), _p(dst), _p(ys), _p(xs), B, H, W, th, tw, my, mx, x4, _stream(src))
         return dst
 
-    def _tile_cond_slice(self, x_n, T):
-        """condition="slice": the conditioning rows of the B x T tile rows of the slices x_n (in [-1, 1]), one (prompt_emb,
-        local_all) pair per engine of _engines().  The tower runs once per slice on the whole slice, at most max_sub_batch slices
-        at a time, on a tower-only engine per U-Net in use; the engine of the tiles turns its outputs into conditioning rows,
-        repeated for the slice's T tiles."""
+    def _cond_buffers(self, prefix, R):
+        """One (prompt_emb, local_all) pair of R conditioning rows per engine of _engines(), in buffers `prefix`_prompt /
+        `prefix`_local of the engine whose rows they are (_encode_all and _cond_rows take the list)."""
+        return [(e._b(prefix + "_prompt", (R, e.time_dim), torch.float32), e._b(prefix + "_local", (R, e.loc_total), torch.float32))
+                for e in self._engines()]
+
+    def _cond_repeated(self, prefix, x_n, n, encode):
+        """_cond_buffers of the B n rows in which every slice of x_n (in [-1, 1]) stands n times: encode(unet, engine, slices)
+        leaves the slices' conditioning in the engine, at most max_sub_batch slices at a time (the tower's workspace grows with its
+        batch), on every engine in use, and a slice's rows are repeated for its n rows (replicas, tiles)."""
         B, s = x_n.shape[0], _stream(x_n)
-        engines = self._engines()
-        _, r0, r1, _ = self._plan()
-        unets = ([self.model.unet0] if r0 else []) + ([self.model.unet1] if r1 else [])
-        cond = [(e._b("til_prompt", (B * T, e.time_dim), torch.float32), e._b("til_local", (B * T, e.loc_total), torch.float32))
-                for e in engines]
+        cond = self._cond_buffers(prefix, B * n)
         for c0 in range(0, B, self.max_sub_batch):
             nb = min(self.max_sub_batch, B - c0)
-            for u, e, (pe, la) in zip(unets, engines, cond):
-                e.condition_from(*u.tower_engine(e.mode).encode_dose(x_n[c0:c0 + nb]))
-                L.call("fd_rows_repeat_f32", _p(e.prompt_emb), _p(pe[c0 * T:]), nb, T, e.time_dim, s)
-                L.call("fd_rows_repeat_f32", _p(e.local_all), _p(la[c0 * T:]), nb, T, e.loc_total, s)
+            for u, e, (pe, la) in zip(self._plan_unets(), self._engines(), cond):
+                encode(u, e, x_n[c0:c0 + nb])
+                L.call("fd_rows_repeat_f32", _p(e.prompt_emb), _p(pe[c0 * n:]), nb, n, e.time_dim, s)
+                L.call("fd_rows_repeat_f32", _p(e.local_all), _p(la[c0 * n:]), nb, n, e.loc_total, s)
         return cond
 
-    def _tiled_fused(self, x01, field, seeds, plan, condition):
-        """The final image (B,1,H,W), in [0, 1] units, of sample_tiled(fuse="step"); seeds (B,) int64 on the device.  The fp16
-        range check and the precision='auto' fallback are sample()'s, applied to that image."""
-        out = self._tiled_fused_loop(x01, field, seeds, plan, condition)
-        if self.model.unet0.kernel_precision == "fp16" and self.check_fp16_range and not bool(torch.isfinite(out).all()):
-            if self.model.unet0.precision != "auto":
-                raise L.FoundDiffHipError(
-                    "precision='fp16': a sampled image is not finite -- an activation of this checkpoint left IEEE binary16's "
-                    "range (65504).  Use precision='bf16' (same speed, fp32's range, 8 significand bits), 'auto' or 'fp32s'.")
-            import warnings
-            warnings.warn("founddiff_amd: precision='auto': this checkpoint's activations leave IEEE binary16's range; "
-                          "this and every later sample() of the model run on the bfloat16 kernels")
-            for u in (getattr(self.model, "unet0", None), getattr(self.model, "unet1", None)):
-                if u is not None:
-                    u._auto_bf16 = True
-            out = self._tiled_fused_loop(x01, field, seeds, plan, condition)
-        return out
+    def _tile_cond_slice(self, x_n, T):
+        """condition="slice": the conditioning rows of the B x T tile rows of the slices x_n.  The tower runs once per slice on
+        the whole slice, on a tower-only engine per U-Net in use; the engine of the tiles turns its outputs into conditioning rows."""
+        return self._cond_repeated("til", x_n, T, lambda u, e, x: e.condition_from(*u.tower_engine(e.mode).encode_dose(x)))
 
     def _tiled_fused_loop(self, x01, field, seeds, plan, condition):
         """One trajectory of the slices as R = B my mx tile rows (sample_tiled's docstring).  Per step: [fd_obj_begin on the
@@ -1503,7 +1442,7 @@ class ResidualDiffusion(nn.Module):
         x_n = normalize_to_neg_one_to_one(x01)
         x_in = self._tile_gather(x_n, plan)
         img = torch.empty_like(x_in)
-        L.call("fd_axpy_f32", _p(x_in), _p(self._tile_gather(field, plan)), math.sqrt(self.sum_scale), _p(img), img.numel(), s)   # _x_T
+        self._x_T_into(x_in, self._tile_gather(field, plan), img)
         per = self.max_sub_batch // 2 if (r0 and r1) else self.max_sub_batch
         passes = tile_passes(B, my, mx, max(1, per))
         nmax = max(hi - lo for lo, hi in passes)
@@ -1511,17 +1450,14 @@ class ResidualDiffusion(nn.Module):
         if condition == "slice":
             cond = self._tile_cond_slice(x_n, Tl)
         else:
-            cond = [(e._b("til_prompt", (R, e.time_dim), torch.float32), e._b("til_local", (R, e.loc_total), torch.float32))
-                    for e in engines]
+            cond = self._cond_buffers("til", R)
             for lo, hi in passes:
                 for e, (pe, la) in zip(engines, cond):
                     e.encode_condition(x_in[lo:hi])
                     pe[lo:hi].copy_(e.prompt_emb)
                     la[lo:hi].copy_(e.local_all)
         outs = [torch.empty_like(x_in) for _ in engines]
-        # the single U-Net of 'pred_noise' predicts the noise: its output is the kernels' o1
-        o0 = outs[0] if (r0 and mode != 1) else None
-        o1 = outs[-1] if (r1 or mode == 1) else None
+        o0, o1 = self._o01(outs)
         final = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
         geom = (_p(wy), _p(wx), _p(ys), _p(xs), B, H, W, th, tw, my, mx, x4)
 
@@ -1546,11 +1482,8 @@ class ResidualDiffusion(nn.Module):
             gpar = self._obj_anc_table().to(dev)
             tabs = [None if tt is None else tt.to(dev) for tt in self._obj_time_tables()]
             bufs = [None if tt is None else torch.zeros(nmax, device=dev, dtype=torch.float32) for tt in tabs]
-            G = max([g for g in range(8, 65) if T % g == 0] or [40])          # _obj_ancestral's chunks, for _anc_max_chunks
-            steps = T
-            lim = getattr(self, "_anc_max_chunks", None)
-            if lim:
-                steps = min(T // G, int(lim)) * G
+            G, reps, rem = self._anc_chunks(T)                     # _obj_ancestral's steps under _anc_max_chunks
+            steps = rem + reps * G
             for i in range(steps):
                 L.call("fd_obj_begin", _p(t_dev), _p(tabs[0]), _p(tabs[1]), _p(bufs[0]), _p(bufs[1]), nmax, T, s)
                 forwards([b for b in bufs if b is not None])

@@ -1,0 +1,375 @@
+"""Characterization of the samplers' launch order, on the CPU: what ResidualDiffusion's loops -- sample, sample_ensemble,
+sample_tiled and the loops behind them -- ask of the kernels and of the engines, in order.  The library entry points (L.call), the
+engines (Unet.engine, Unet.tower_engine) and ensemble_stats are recording stubs; _p hands out the NAME of the buffer behind a pointer
+("unet0/bf16/0:loop_img", "+n" for a view n elements into it; a tensor no engine owns is "tmpK:shape", numbered by its first
+appearance in a launch), so a row says which buffer a launch reads and writes.  A row holds the entry point or engine method, the
+engine, the scalar arguments and those names; a forward also shows the first entry of its time input (the tables are host data, the
+stubs leave device-written buffers at zero).  engine.captured runs warm() between "warm{" and "}", record's capture(fn) runs fn
+between "capture{" and "}", and a replay is one row.  The last rows of a case are what it raised or warned, _auto_bf16, the shapes
+returned and the state the loops leave: _anc_steps_run and the step counters.  Runs of equal rows are folded: ["x", n, [rows]].
+
+tests/test_sample_launches_cpu.py compares the rows with tests/golden/sample_launches.json.  The golden pins behaviour, not
+correctness: it was recorded before the rules of the loops (range check, chunk rule, capture idiom, chunked ancestral driver, DDIM
+step list, row conditioning) were gathered into one definition each, on the commit "Row-GEMM: one launch plan, a host query for it,
+every form against fp64", and a change that is meant to alter the launches regenerates it, or the named cases alone, with
+
+    python tests/sample_launches.py --write [case ...]
+
+Four cases were recorded again with that gathering, and nothing else in them changed: "anc keyed T=6 trajectory", "anc keyed T=6
+no-graph", "anc keyed T=84 no-graph max-chunks" and "generic anc rn_res trajectory" are the eager form of the shipped ancestral
+loop (use_graph off, or last=False), which now runs under the driver of every ancestral loop: it writes _anc_steps_run, and it
+honours _anc_max_chunks, which it used to ignore (the third case: 40 main steps, the jump, the tail step, instead of all 84).
+"""
+import json
+import os
+import sys
+import warnings
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from founddiff_amd import DADiff                                       # noqa: E402
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "sample_launches.json")
+HW = 8
+TINY_CLIP = dict(layers=(2, 1, 1, 1), width=16, embed_dim=1024)
+PLANS = {   # name -> (num_unet, objective, test_res_or_noise)
+    "shipped": (1, "pred_res", "res"), "pred_noise": (1, "pred_noise", "noise"), "res_noise": (2, "pred_res_noise", "res_noise"),
+    "rn_res": (2, "pred_res_noise", "res"), "rn_noise": (2, "pred_res_noise", "noise"),
+}
+ENV = ("FOUNDDIFF_LOOP_GRAPH", "FOUNDDIFF_TAIL_EXACT")                 # read at call time by the loops: the cases run without them
+
+
+def _case(path, plan="shipped", **kw):
+    """S: sampling_timesteps (a DDIM case keeps the 1000-step schedule), T: the ancestral schedule cut to T steps.  The other keys
+    are attributes set on the sampler (use_graph, final_fp32_steps, final_outer_levels, _time_table, _anc_max_chunks,
+    max_sub_batch) or arguments of the call (last, noise, seeds, step_noise, K, fuse, condition, fail)."""
+    c = dict(path=path, plan=plan)
+    c.update(kw)
+    return c
+
+
+def _cases():
+    out = {}
+
+    def add(name, path, plan="shipped", **kw):
+        assert name not in out
+        out[name] = _case(path, plan, **kw)
+
+    # ---- shipped DDIM: the captured loop (hybrid tail, whole-step tail, time table, no tail) and the eager forms
+    add("ddim captured hybrid-tail", "sample", S=4, final_outer_levels=1)
+    add("ddim captured seeds", "sample", S=4, seeds=1)
+    add("ddim captured time-table", "sample", S=4, _time_table="1")
+    add("ddim captured no-tail", "sample", S=4, final_fp32_steps=0)
+    add("ddim eager step-graphs trajectory", "sample", S=4, last=0, final_outer_levels=1)
+    add("ddim eager no-graph", "sample", S=4, use_graph=0)
+    # ---- shipped ancestral, keyed noise.  T - K main steps: 83 (no divisor in [8, 64]: G = 40, reps 2, rem 3), 16 (G = 16, reps 1,
+    # rem 0), 5 (reps 0, rem 5), 9 with K = 0
+    add("anc keyed T=84", "sample", T=84, seeds=1, final_outer_levels=1)
+    add("anc keyed T=84 max-chunks", "sample", T=84, seeds=1, _anc_max_chunks=1, final_outer_levels=1)
+    add("anc keyed T=17 noise", "sample", T=17, noise=1)
+    add("anc keyed T=6", "sample", T=6, seeds=1, noise=1)
+    add("anc keyed T=9 no-tail", "sample", T=9, final_fp32_steps=0)
+    add("anc keyed T=6 trajectory", "sample", T=6, seeds=1, last=0)
+    add("anc keyed T=6 no-graph", "sample", T=6, seeds=1, use_graph=0)
+    add("anc keyed T=84 no-graph max-chunks", "sample", T=84, seeds=1, use_graph=0, _anc_max_chunks=1)
+    # ---- shipped ancestral, step_noise
+    add("anc step_noise T=5", "sample", T=5, step_noise=1, noise=1)
+    add("anc step_noise T=5 trajectory", "sample", T=5, step_noise=1, last=0)
+    add("anc step_noise T=5 no-graph", "sample", T=5, step_noise=1, use_graph=0)
+    # ---- the captured loops of the other plans.  T = 83: G = 40, reps 2, rem 3; 16: G = 16; 6: reps 0
+    for plan in ("pred_noise", "res_noise", "rn_res", "rn_noise"):
+        add(f"obj_ddim {plan}", "sample", plan, S=3)
+        add(f"obj_anc {plan} T=83", "sample", plan, T=83, seeds=1)
+        add(f"generic ddim {plan} trajectory", "sample", plan, S=3, last=0)
+        add(f"generic anc {plan} trajectory", "sample", plan, T=3, last=0)
+    add("obj_ddim res_noise no-graph", "sample", "res_noise", S=3, use_graph=0, noise=1)
+    add("obj_ddim pred_noise no-graph", "sample", "pred_noise", S=3, use_graph=0)
+    add("obj_anc res_noise T=16", "sample", "res_noise", T=16, noise=1)
+    add("obj_anc res_noise T=83 max-chunks", "sample", "res_noise", T=83, seeds=1, _anc_max_chunks=1)
+    add("obj_anc res_noise T=6", "sample", "res_noise", T=6, seeds=1)
+    add("obj_anc res_noise T=11 no-graph", "sample", "res_noise", T=11, seeds=1, use_graph=0)
+    add("obj_anc pred_noise T=83 no-graph max-chunks", "sample", "pred_noise", T=83, seeds=1, use_graph=0, _anc_max_chunks=1)
+    add("generic anc res_noise step_noise", "sample", "res_noise", T=3, step_noise=1)
+    # ---- ensembles: B = 2, K = 3.  max_sub_batch 4: one tower pass, row passes of 4 + 2; 1: two tower passes, six row passes
+    add("ensemble ddim msb=4", "ensemble", S=3, K=3, max_sub_batch=4)
+    add("ensemble ddim msb=1", "ensemble", S=3, K=3, max_sub_batch=1)
+    add("ensemble anc msb=4", "ensemble", T=9, K=3, max_sub_batch=4)
+    add("ensemble ddim res_noise msb=4", "ensemble", "res_noise", S=3, K=3, max_sub_batch=4)
+    add("ensemble anc res_noise msb=2", "ensemble", "res_noise", T=9, K=3, max_sub_batch=2)
+    # ---- tiles: 8 x 8 slices as 2 x 2 tiles of 6 pixels, 2 apart from full tiles; B = 2, so 8 rows in passes of 4 (2 for two U-Nets)
+    for fuse in ("final", "step"):
+        for cond in ("tile", "slice"):
+            add(f"tiled {fuse} {cond} ddim", "tiled", S=3, fuse=fuse, condition=cond, max_sub_batch=4)
+            add(f"tiled {fuse} {cond} anc", "tiled", T=9, fuse=fuse, condition=cond, max_sub_batch=4)
+            add(f"tiled {fuse} {cond} ddim res_noise", "tiled", "res_noise", S=3, fuse=fuse, condition=cond, max_sub_batch=4)
+            add(f"tiled {fuse} {cond} anc res_noise", "tiled", "res_noise", T=9, fuse=fuse, condition=cond, max_sub_batch=4)
+    add("tiled step tile anc pred_noise T=83 max-chunks", "tiled", "pred_noise", T=83, fuse="step", condition="tile",
+        max_sub_batch=4, _anc_max_chunks=1)
+    add("tiled step slice ddim msb=1", "tiled", S=3, fuse="step", condition="slice", max_sub_batch=1)
+    # ---- the fp16 range check of the four entry points: torch.isfinite fails once; 'fp16' raises, 'auto' falls back and re-runs
+    for prec in ("fp16", "auto"):
+        add(f"fallback sample {prec}", "sample", S=3, precision=prec, fail=1)
+        add(f"fallback ensemble {prec}", "ensemble", S=3, K=3, max_sub_batch=4, precision=prec, fail=1)
+        add(f"fallback tiled final {prec}", "tiled", S=3, fuse="final", condition="tile", max_sub_batch=4, precision=prec, fail=1)
+        add(f"fallback tiled step {prec}", "tiled", S=3, fuse="step", condition="tile", max_sub_batch=4, precision=prec, fail=1)
+    add("fp16 sample in range", "sample", S=3, precision="fp16")
+    add("fallback sample anc auto", "sample", "res_noise", T=9, precision="auto", fail=1)
+    return out
+
+
+CASES = _cases()
+
+
+class FakeGraph:
+    def __init__(self, rec, eng, n):
+        self.rec, self.eng, self.n = rec, eng, n
+
+    def replay(self):
+        self.rec.row("replay", self.eng.name, self.n)
+
+
+class FakeEngine:
+    """What the loops reach for on a DAEngine: named buffers, the conditioning, forwards, the graph cache."""
+    time_dim, loc_total, low_latency = 8, 12, False
+
+    def __init__(self, rec, name, mode, gen):
+        self.rec, self.name, self.mode, self.gen = rec, name, mode, gen
+        self.downs = [None, None]                                      # a two-level net
+        self.buf, self.graphs = {}, {}
+        self.prompt_emb = self.local_all = self.dose_emb = self.ctx_emb = None
+
+    def _b(self, name, shape, dtype=None):
+        key = (name, tuple(shape), dtype)
+        if key not in self.buf:
+            self.buf[key] = self.rec.named(torch.zeros(tuple(shape), dtype=dtype or torch.float32), f"{self.name}:{name}")
+        return self.buf[key]
+
+    def _cond(self, B):
+        self.prompt_emb = self._b("prompt_emb", (B, self.time_dim), torch.float32)
+        self.local_all = self._b("local_all", (B, self.loc_total), torch.float32)
+
+    def encode_dose(self, x):
+        self.rec.row("encode_dose", self.name, self.rec.p(x), list(x.shape))
+        return self._b("dose", (x.shape[0], 4), torch.float32), self._b("ctx", (x.shape[0], 4), torch.float32)
+
+    def encode_condition(self, x):
+        self.rec.row("encode_condition", self.name, self.rec.p(x), list(x.shape))
+        self._cond(x.shape[0])
+
+    def condition_from(self, dose, ctx):
+        self.rec.row("condition_from", self.name, self.rec.p(dose), self.rec.p(ctx), dose.shape[0])
+        self._cond(dose.shape[0])
+
+    def load_condition(self, prompt_emb, local_all):
+        self.rec.row("load_condition", self.name, self.rec.p(prompt_emb), self.rec.p(local_all), prompt_emb.shape[0])
+        self._cond(prompt_emb.shape[0])
+
+    def share_condition(self, other):
+        self.rec.row("share_condition", self.name, other.name)
+        self._cond(other.prompt_emb.shape[0])
+
+    def time_table_prepare(self, times, B):
+        self.rec.row("time_table_prepare", self.name, [float(t) for t in times], B)
+
+    def time_cond_table(self):
+        self.rec.row("time_cond_table", self.name)
+
+    def _fwd(self, what, x_t, x_in, time, out, *more):
+        p = self.rec.p
+        if out is None:
+            out = self._b("model_out", tuple(x_t.shape), torch.float32)
+        self.rec.row(what, self.name, p(x_t), p(x_in), p(time), float(time.reshape(-1)[0]), list(x_t.shape), p(out), *more)
+        return out
+
+    def forward(self, x_t, x_in, time, out=None, x_cond2=None, sched=None, step=None):
+        return self._fwd("forward", x_t, x_in, time, out, self.rec.p(x_cond2), None if sched is None else list(sched), step)
+
+    def forward_hybrid(self, inner, x_t, x_in, time, out=None, outer_levels=1, sched=None, down_levels=None):
+        return self._fwd("forward_hybrid", x_t, x_in, time, out, inner.name, outer_levels, None if sched is None else list(sched),
+                         down_levels)
+
+    def captured(self, kind, key, warm, record):
+        ent = self.graphs.get(kind)
+        hit = ent is not None and ent[0] == key
+        self.rec.row("captured", self.name, kind, json.loads(json.dumps(key)), "hit" if hit else "miss")
+        if hit:
+            return ent[1]
+        self.rec.row("warm{")
+        warm()
+        self.rec.row("}")
+
+        def capture(fn):
+            self.rec.graphs += 1
+            g = FakeGraph(self.rec, self, self.rec.graphs)
+            self.rec.row("capture{", g.n)
+            fn()
+            self.rec.row("}")
+            return g
+        self.graphs[kind] = (key, record(capture))
+        return self.graphs[kind][1]
+
+
+def fold(rows, longest=24):
+    """runs of equal blocks of up to `longest` rows -> ["x", n, block]; greedy, the block that covers most rows wins"""
+    out, i = [], 0
+    while i < len(rows):
+        best = (0, 0, 0)
+        for p in range(1, min(longest, (len(rows) - i) // 2) + 1):
+            n = 1
+            while rows[i + n * p:i + (n + 1) * p] == rows[i:i + p]:
+                n += 1
+            if n > 1 and n * p > best[0]:
+                best = (n * p, p, n)
+        if best[0]:
+            out.append(["x", best[2], rows[i:i + best[1]]])
+            i += best[0]
+        else:
+            out.append(rows[i])
+            i += 1
+    return out
+
+
+class Recorder:
+    def __init__(self):
+        self.nets = {}
+
+    # ---- names of buffers
+    def named(self, t, name):
+        st = t.untyped_storage()
+        self.spans.append((st.data_ptr(), st.nbytes(), name, t))       # (the reference keeps the address from being used again)
+        return t
+
+    def p(self, t):
+        if t is None:
+            return None
+        ptr = t.data_ptr()
+        for base, nbytes, name, _ in self.spans:
+            if base <= ptr < base + max(nbytes, 1):
+                off = (ptr - base) // t.element_size()
+                return name if off == 0 else f"{name}+{off}"
+        self.tmps += 1
+        self.named(t, f"tmp{self.tmps}:" + "x".join(str(int(d)) for d in t.shape))
+        return self.p(t)
+
+    def row(self, *r):
+        self.rows.append(list(r))
+
+    # ---- the stubs
+    def _call(self, name, *args):
+        self.row(name, *[a if isinstance(a, (str, int, float, type(None))) else repr(a) for a in args])
+
+    def _engine(self, unet, precision=None, slot=0):
+        prec = precision or unet.kernel_precision
+        which = "unet1" if unet is getattr(self.dif.model, "unet1", None) else "unet0"
+        name = f"{which}/{prec}/{slot}"
+        if name not in self.engines:
+            self.engines[name] = FakeEngine(self, name, prec, len(self.engines) + 1)
+        return self.engines[name]
+
+    def _isfinite(self, t):
+        if self.fail:
+            self.fail -= 1
+            return torch.zeros(())
+        return torch.ones(())                                          # (nothing is computed here: the images are uninitialised)
+
+    def _stats(self, samples):
+        self.row("ensemble_stats", list(samples.shape))
+        B, sh = samples.shape[0], tuple(samples.shape[2:])
+        return torch.zeros((B,) + sh), torch.zeros((B,) + sh), torch.zeros(B)
+
+    def _dif(self, c):
+        nu, obj, tst = PLANS[c["plan"]]
+        prec = c.get("precision", "bf16")
+        if (c["plan"], prec) not in self.nets:
+            self.nets[c["plan"], prec] = DADiff.UnetRes(dim=32, dim_mults=(1, 2), num_unet=nu, condition=True, objective=obj,
+                                                        test_res_or_noise=tst, clip_cfg=TINY_CLIP, precision=prec)
+        net = self.nets[c["plan"], prec]
+        for u in net._unets():
+            u._auto_bf16, u.low_latency = False, False
+        dif = DADiff.ResidualDiffusion(net, image_size=HW, timesteps=1000, sampling_timesteps=c.get("S", 1000), objective=obj,
+                                       loss_type="l2", condition=True, sum_scale=0.01, test_res_or_noise=tst,
+                                       use_graph=bool(c.get("use_graph", 1)), final_fp32_steps=c.get("final_fp32_steps", 1))
+        dif.final_outer_levels, dif.final_down_levels = c.get("final_outer_levels"), -1
+        dif.check_fp16_range, dif._time_table = True, c.get("_time_table", "auto")
+        dif.streams, dif.max_sub_batch = 1, c.get("max_sub_batch", 16)
+        if "_anc_max_chunks" in c:
+            dif._anc_max_chunks = c["_anc_max_chunks"]
+        if "T" in c:                                                   # the ancestral loops walk the whole schedule: cut it
+            for k in ("alphas_cumsum", "betas_cumsum", "one_minus_alphas_cumsum", "posterior_mean_coef1", "posterior_mean_coef2",
+                      "posterior_mean_coef3", "posterior_log_variance_clipped"):
+                setattr(dif, k, getattr(dif, k)[:c["T"]].clone())
+            dif.num_timesteps, dif._host_sched = c["T"], None
+        return dif
+
+    def run(self, c):
+        self.rows, self.spans, self.tmps, self.graphs, self.engines, self.fail = [], [], 0, 0, {}, int(c.get("fail", 0))
+        dif = self.dif = self._dif(c)
+        B = 2
+        shape = (B, 1, HW, HW)
+        x01 = self.named(torch.full(shape, 0.5), "arg:x")
+        noise = self.named(torch.zeros(shape), "arg:noise") if c.get("noise") else None
+        seeds = torch.tensor([11, 12], dtype=torch.int64) if c.get("seeds") else None
+        step_noise = (lambda t: self.named(torch.zeros(shape), f"arg:step_noise({t})")) if c.get("step_noise") else None
+        saved = (DADiff.L.call, DADiff._p, DADiff._stream, DADiff.ensemble_stats, DADiff.Unet.engine, DADiff.Unet.tower_engine,
+                 torch.isfinite)
+        env = {k: os.environ.pop(k) for k in ENV if k in os.environ}
+        DADiff.L.call, DADiff._p, DADiff._stream, DADiff.ensemble_stats = self._call, self.p, (lambda t: "s"), self._stats
+        rec = self
+        DADiff.Unet.engine = lambda u, precision=None, slot=0: rec._engine(u, precision, slot)
+        DADiff.Unet.tower_engine = lambda u, precision=None: rec._engine(u, precision, "tower")
+        torch.isfinite = self._isfinite
+        out = None
+        try:
+            with warnings.catch_warnings(record=True) as caught:
+                warnings.simplefilter("always")
+                torch.manual_seed(0)
+                try:
+                    if c["path"] == "sample":
+                        out = dif.sample([x01], batch_size=B, last=bool(c.get("last", 1)), noise=noise, step_noise=step_noise,
+                                         slice_seeds=seeds)
+                    elif c["path"] == "ensemble":
+                        res = dif.sample_ensemble([x01], c["K"], slice_seeds=seeds, return_samples=True)
+                        out = [res.mean, res.std, res.spread, res.samples]
+                    else:
+                        out = dif.sample_tiled([x01], 6, 2, slice_seeds=seeds, condition=c["condition"], fuse=c["fuse"])
+                except DADiff.L.FoundDiffHipError as e:
+                    self.row("raises", type(e).__name__, str(e))
+            for w in caught:
+                self.row("warns", str(w.message))
+        finally:
+            (DADiff.L.call, DADiff._p, DADiff._stream, DADiff.ensemble_stats, DADiff.Unet.engine, DADiff.Unet.tower_engine,
+             torch.isfinite) = saved
+            os.environ.update(env)
+        self.row("_auto_bf16", [bool(u._auto_bf16) for u in dif.model._unets()])
+        self.row("returns", None if out is None else [list(o.shape) for o in out])
+        counters = {f"{e.name}:{k[0]}": int(t) for e in self.engines.values() for k, t in e.buf.items() if k[0] in ("loop_t", "obj_t")}
+        self.row("state", getattr(dif, "_anc_steps_run", None), counters, getattr(dif, "_tile_fuse", None))
+        return fold(json.loads(json.dumps(self.rows)))
+
+
+def snapshot():
+    rec = Recorder()
+    return {name: rec.run(c) for name, c in CASES.items()}
+
+
+def write(path=GOLDEN, only=()):
+    """record every case, or only the named ones into the golden that is there"""
+    g = snapshot()
+    if only:
+        with open(path) as f:
+            old = json.load(f)
+        g = {k: g[k] if k in only else old[k] for k in g}
+    with open(path, "w") as f:
+        f.write("{\n" + ",\n".join(f' {json.dumps(k)}: {json.dumps(v, separators=(",", ":"))}' for k, v in g.items()) + "\n}\n")
+    return g
+
+
+if __name__ == "__main__":
+    if sys.argv[1:2] != ["--write"] or not set(sys.argv[2:]) <= set(CASES):
+        sys.exit("usage: python tests/sample_launches.py --write [case ...]")
+    g = write(only=sys.argv[2:])
+    print(f"{GOLDEN}: {len(g)} cases, {os.path.getsize(GOLDEN)} bytes")
