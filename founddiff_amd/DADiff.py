@@ -32,7 +32,7 @@ from . import diffusion_train as dt
 from .engine import DAEngine, _p
 from .ensemble import ensemble_passes, ensemble_seeds
 from .metrics import ensemble_stats
-from .tiling import tile_pair, tile_passes, tile_plan, tile_seeds, tile_weights
+from .tiling import tile_pair, tile_passes, tile_plan, tile_seeds, tile_weights, tiled_ensemble_seeds
 
 ModelResPrediction = namedtuple("ModelResPrediction", ["pred_res", "pred_noise", "pred_x_start"])
 # sample_ensemble: mean, std (B,1,H,W) in [0, 1] units, spread (B,), samples (B,K,1,H,W) or None
@@ -1270,19 +1270,33 @@ class ResidualDiffusion(nn.Module):
         return res
 
     @torch.no_grad()
-    def sample_ensemble(self, x_input, n_samples, slice_seeds=None, return_samples=False):
+    def sample_ensemble(self, x_input, n_samples, slice_seeds=None, return_samples=False, *, tile=None, overlap=0,
+                        tile_condition="tile", tile_fuse="final"):
         """K = n_samples keyed realisations of every slice of x_input = [ldct (B,1,H,W) in [0,1]], reduced on the device: an
         EnsembleResult of the per-pixel mean and sample standard deviation over a slice's K final images (both (B,1,H,W), in the
         [0, 1] units of sample()[-1]), spread (B,) = sqrt(mean over pixels of std^2), and the images themselves (B,K,1,H,W) when
         `return_samples`.  Replica k of slice b is the image sample([x[b:b+1]], slice_seeds=[ensemble_seeds(slice_seeds, K)[b, k]])
         returns, bit for bit: x_T -- and the step noise of the ancestral sampler -- is the keyed stream of the replica's seed on
         every path.  The DA-CLIP tower runs once per slice; the B K rows (slice-major) run in passes of at most streams x
-        max_sub_batch through the paths of sample(), and nothing returned depends on that cut or on B."""
+        max_sub_batch through the paths of sample(), and nothing returned depends on that cut or on B.
+        `tile` (keyword-only, with `overlap`, `tile_condition`, `tile_fuse`; None: all of the above, unchanged): every replica is
+        sampled as overlapping tiles.  Replica k of slice b is then, bit for bit, the final image of sample_tiled([x[b:b+1]],
+        tile, overlap, slice_seeds=[ensemble_seeds(slice_seeds, K)[b, k]], condition=tile_condition, fuse=tile_fuse), on both
+        samplers and for every plan; the result has the same shapes and units.  The rows are tiling.tiled_ensemble_seeds':
+        replica first, then tile, row ((b K + k) my + iy) mx + ix, at most 65535 of them.  The tower runs once per slice and tile
+        ("tile") or once per slice ("slice"), never per replica: a slice's T conditioning rows and input tiles are repeated for
+        its K replicas.  tile_fuse="final": one keyed x_T field per (slice, replica), gathered per tile; the B K T rows run
+        through the paths of sample() in tile_passes, and fd_tiles_ensemble_f32 takes their final images straight to mean, std
+        and spread (the K blended images are written only for `return_samples`) with the bits of fd_tiles_blend_f32 followed by
+        fd_ensemble_stats_f32.  tile_fuse="step": the fused loop of sample_tiled over the B K replicas as pseudo-slices, each
+        under its replica seed, then fd_ensemble_stats_f32.  Nothing returned depends on B, max_sub_batch, streams or the passes."""
         K = int(n_samples)
         if K < 1:
             raise RuntimeError(f"sample_ensemble: n_samples must be at least 1 (got {n_samples})")
         if self.input_condition:
             raise RuntimeError("sample_ensemble: input_condition=True is not built (one input plane per slice)")
+        if tile is not None:
+            return self._sample_ensemble_tiled(x_input, K, slice_seeds, return_samples, tile, overlap, tile_condition, tile_fuse)
         x01 = list(x_input)[0].contiguous().float()
         B = x01.shape[0]
         seeds = self._slice_seeds(slice_seeds, B, "cpu")
@@ -1311,6 +1325,58 @@ class ResidualDiffusion(nn.Module):
             flat[sl].copy_(out[-1])
         return samples
 
+    def _sample_ensemble_tiled(self, x_input, K, slice_seeds, return_samples, tile, overlap, condition, fuse):
+        """sample_ensemble(tile=...): see its docstring"""
+        fn = "sample_ensemble"
+        if fuse not in ("final", "step"):
+            raise RuntimeError(f"{fn}: tile_fuse must be 'final' or 'step' (got {fuse!r})")
+        x01, (th, tw), (oy, ox) = self._tiled_args(fn, x_input, tile, overlap, condition)
+        B, _, H, W = x01.shape
+        x01 = x01.contiguous().float()
+        dev, s = x01.device, _stream(x01)
+        seeds = self._slice_seeds(slice_seeds, B, "cpu")
+        ys, xs, wy, wx, my, mx, x4 = self._tile_plan(H, W, th, tw, oy, ox, dev)
+        T = my * mx
+        if B * K * T > 65535:
+            raise RuntimeError(f"{fn}: {B} slices x {K} replicas x {my} x {mx} tiles are more than 65535 rows: sample fewer "
+                               "slices per call")
+        plan = (ys, xs, wy, wx, my, mx, x4, th, tw)
+        rseeds = torch.from_numpy(ensemble_seeds(seeds.numpy(), K).reshape(-1)).to(dev)                    # (B K,): a replica's
+        rows = torch.from_numpy(tiled_ensemble_seeds(seeds.numpy(), K, T).reshape(-1)).to(dev)              # (B K T,): a tile row's
+        field = self._keyed_noise(rseeds, self.X_T_STEP, (B * K, 1, H, W))
+
+        def replica_rows():
+            x_n = normalize_to_neg_one_to_one(x01)
+            x_in = self._tile_gather(x_n, plan)
+            return self._rows_per_replica(x_in, self._tile_cond_rows(x_n, x_in, plan, condition), B, K)
+        if fuse == "step":
+            def fused():
+                x_rows, cond = replica_rows()
+                img = self._x_T_into(x_rows, self._tile_gather(field, plan), torch.empty_like(x_rows))
+                return self._tiled_fused_loop(x_rows, img, cond, rseeds, plan, (B * K, H, W))
+            samples = self._range_checked(fused, "a sampled image").view(B, K, 1, H, W)
+            mean, std, spread = ensemble_stats(samples)
+            return EnsembleResult(mean, std, spread, samples if return_samples else None)
+
+        def final_tiles():
+            x_rows, cond = replica_rows()
+            nz_rows = self._tile_gather(field, plan)
+            tiles = torch.empty((B * K * T, 1, th, tw), device=dev, dtype=torch.float32)
+            for lo, hi in tile_passes(B * K, my, mx, self._group_rows(), self.streams):
+                sl = slice(lo, hi)
+                out = self._sample([x_rows[sl]], hi - lo, True, nz_rows[sl], None, rows[sl].contiguous(),
+                                   cond=self._cond_rows(cond, sl))
+                tiles[sl].copy_(out[-1])
+            return tiles
+        tiles = self._range_checked(final_tiles, "a sampled image (a tile row of a replica)")
+        nblk = L.lib().fd_ensemble_nblk(H * W)
+        mean, std = torch.empty_like(x01), torch.empty_like(x01)
+        ws, spread = torch.empty(B * nblk, device=dev), torch.empty(B, device=dev)
+        samples = torch.empty((B, K, 1, H, W), device=dev, dtype=torch.float32) if return_samples else None
+        L.call("fd_tiles_ensemble_f32", _p(tiles), _p(wy), _p(wx), _p(ys), _p(xs), None if samples is None else _p(samples),
+               _p(mean), _p(std), _p(ws), _p(spread), B, K, H, W, th, tw, my, mx, x4, s)
+        return EnsembleResult(mean, std, spread, samples)
+
     # ---- a slice as overlapping tiles
     def _tile_plan(self, H, W, th, tw, oy, ox, dev):
         """The plan of tiling.py on the device, uploaded once per geometry: (ys, xs int32, wy, wx float32, my, mx, xs % 4 == 0)"""
@@ -1323,6 +1389,27 @@ class ResidualDiffusion(nn.Module):
             plan = cache[key] = (up(ys, np.int32), up(xs, np.int32), up(tile_weights(ys, H, th), np.float32),
                                  up(tile_weights(xs, W, tw), np.float32), len(ys), len(xs), int(bool((xs % 4 == 0).all())))
         return plan
+
+    def _tiled_args(self, fn, x_input, tile, overlap, condition):
+        """The argument checks of a tiled call `fn`: (x01 as given, (th, tw), (oy, ox))"""
+        if self.input_condition:
+            raise RuntimeError(f"{fn}: input_condition=True is not built (one input plane per slice)")
+        if condition not in ("tile", "slice"):
+            raise RuntimeError(f"{fn}: condition must be 'tile' or 'slice' (got {condition!r})")
+        (th, tw), (oy, ox) = tile_pair(fn, tile, "tile"), tile_pair(fn, overlap, "overlap")
+        x01 = list(x_input)[0]
+        if not torch.is_tensor(x01) or x01.dim() != 4 or x01.shape[1] != 1:
+            raise RuntimeError(f"{fn}: x_input must be [ldct (B,1,H,W)]")
+        B, _, H, W = x01.shape
+        div = 2 ** (len(self.model.unet0.dim_mults) - 1)
+        if th < 1 or tw < 1 or th % div or tw % div:
+            raise RuntimeError(f"{fn}: tile {th} x {tw} must be positive multiples of {div} (the U-Net has "
+                               f"{len(self.model.unet0.dim_mults)} levels)")
+        if th > H or tw > W:
+            raise RuntimeError(f"{fn}: tile {th} x {tw} is larger than the slice {H} x {W} (padded tiles are not built)")
+        if not (0 <= oy <= th // 2 and 0 <= ox <= tw // 2):
+            raise RuntimeError(f"{fn}: overlap {oy} x {ox} must lie in [0, tile // 2] = [0, {th // 2}] x [0, {tw // 2}]")
+        return x01, (th, tw), (oy, ox)
 
     @torch.no_grad()
     @_fuse_keyword
@@ -1359,26 +1446,13 @@ class ResidualDiffusion(nn.Module):
         runs, the shipped one as mode 0, on both samplers (_anc_max_chunks bounds the ancestral one as in _obj_ancestral), on one
         stream with slot 0's engines, eagerly: no captured graph, no second stream, and no precision tail for any plan -- a bf16
         fused run of the shipped plan does not get final_fp32_steps.  Nothing returned depends on B or on max_sub_batch.
-        Not built: tiled ensembles, tiles larger than the slice (padded tiles), last=False, input_condition=True; for
-        fuse="step" also a captured graph or a second stream, a precision tail, and per-tile seeds."""
+        Ensembles of tiled samples are sample_ensemble(tile=...).  Not built: tiles larger than the slice (padded tiles),
+        last=False, input_condition=True; for fuse="step" also a captured graph or a second stream, a precision tail, and
+        per-tile seeds."""
         fn = "sample_tiled"
-        if self.input_condition:
-            raise RuntimeError(f"{fn}: input_condition=True is not built (one input plane per slice)")
-        if condition not in ("tile", "slice"):
-            raise RuntimeError(f"{fn}: condition must be 'tile' or 'slice' (got {condition!r})")
-        (th, tw), (oy, ox) = tile_pair(fn, tile, "tile"), tile_pair(fn, overlap, "overlap")
-        x01 = list(x_input)[0]
-        if not torch.is_tensor(x01) or x01.dim() != 4 or x01.shape[1] != 1:
-            raise RuntimeError(f"{fn}: x_input must be [ldct (B,1,H,W)]")
+        # (unbound: the host-side checks run on any object that has input_condition, tests/test_tiled_fused_cpu.py)
+        x01, (th, tw), (oy, ox) = ResidualDiffusion._tiled_args(self, fn, x_input, tile, overlap, condition)
         B, _, H, W = x01.shape
-        div = 2 ** (len(self.model.unet0.dim_mults) - 1)
-        if th < 1 or tw < 1 or th % div or tw % div:
-            raise RuntimeError(f"{fn}: tile {th} x {tw} must be positive multiples of {div} (the U-Net has "
-                               f"{len(self.model.unet0.dim_mults)} levels)")
-        if th > H or tw > W:
-            raise RuntimeError(f"{fn}: tile {th} x {tw} is larger than the slice {H} x {W} (padded tiles are not built)")
-        if not (0 <= oy <= th // 2 and 0 <= ox <= tw // 2):
-            raise RuntimeError(f"{fn}: overlap {oy} x {ox} must lie in [0, tile // 2] = [0, {th // 2}] x [0, {tw // 2}]")
         x01 = x01.contiguous().float()
         seeds = self._slice_seeds(slice_seeds, B, "cpu")
         ys, xs, wy, wx, my, mx, x4 = self._tile_plan(H, W, th, tw, oy, ox, x01.device)
@@ -1390,8 +1464,13 @@ class ResidualDiffusion(nn.Module):
         field = self._keyed_noise(seeds.to(x01.device), self.X_T_STEP, tuple(x01.shape))
         x_T = self._x_T_into(normalize_to_neg_one_to_one(x01), field, torch.empty_like(x01))
         if self._tile_fuse == "step":
-            return [unnormalize_to_zero_to_one(x_T), self._range_checked(
-                lambda: self._tiled_fused_loop(x01, field, seeds.to(x01.device), plan, condition), "a sampled image")]
+            def fused():
+                x_n = normalize_to_neg_one_to_one(x01)
+                x_in = self._tile_gather(x_n, plan)
+                img = self._x_T_into(x_in, self._tile_gather(field, plan), torch.empty_like(x_in))
+                cond = self._tile_cond_rows(x_n, x_in, plan, condition)
+                return self._tiled_fused_loop(x_in, img, cond, seeds.to(x01.device), plan, (B, H, W))
+            return [unnormalize_to_zero_to_one(x_T), self._range_checked(fused, "a sampled image")]
         tiles = self._range_checked(lambda: self._tile_rows(x01, field, rows, plan, condition), "a sampled image")
         out = torch.empty_like(x01)
         L.call("fd_tiles_blend_f32", _p(tiles), _p(wy), _p(wx), _p(ys), _p(xs), _p(out), B, H, W, th, tw, my, mx, x4, s)
@@ -1429,33 +1508,53 @@ class ResidualDiffusion(nn.Module):
         the whole slice, on a tower-only engine per U-Net in use; the engine of the tiles turns its outputs into conditioning rows."""
         return self._cond_repeated("til", x_n, T, lambda u, e, x: e.condition_from(*u.tower_engine(e.mode).encode_dose(x)))
 
-    def _tiled_fused_loop(self, x01, field, seeds, plan, condition):
-        """One trajectory of the slices as R = B my mx tile rows (sample_tiled's docstring).  Per step: [fd_obj_begin on the
-        ancestral sampler,] per U-Net of the plan and per sub-batch load_condition + forward into the rows of o0 / o1, then one
-        fd_tiles_step_* launch over all R rows in place on img, which also writes the slice image on the last step."""
-        ys, xs, wy, wx, my, mx, x4, th, tw = plan
-        B, _, H, W = x01.shape
-        Tl, dev, s = my * mx, x01.device, _stream(x01)
-        R = B * Tl
-        mode, r0, r1, _ = self._plan()
-        engines = self._engines()
-        x_n = normalize_to_neg_one_to_one(x01)
-        x_in = self._tile_gather(x_n, plan)
-        img = torch.empty_like(x_in)
-        self._x_T_into(x_in, self._tile_gather(field, plan), img)
-        per = self.max_sub_batch // 2 if (r0 and r1) else self.max_sub_batch
-        passes = tile_passes(B, my, mx, max(1, per))
-        nmax = max(hi - lo for lo, hi in passes)
-        # conditioning rows of every tile row, once: the tower on every tile, or on the whole slices
+    def _fused_passes(self, B, my, mx):
+        """The sub-batches of the B my mx tile rows that one engine takes at a time outside _sample: at most max_sub_batch rows,
+        half of it for a two-U-Net plan."""
+        _, r0, r1, _ = self._plan()
+        return tile_passes(B, my, mx, max(1, self.max_sub_batch // 2 if (r0 and r1) else self.max_sub_batch))
+
+    def _tile_cond_rows(self, x_n, x_in, plan, condition):
+        """The conditioning rows of the B my mx tile rows x_in (R,1,th,tw) gathered from the slices x_n (both in [-1, 1]), one
+        (prompt_emb, local_all) pair per engine of _engines().  The tower runs once: on every tile (condition "tile", a
+        sub-batch of _fused_passes at a time), or on the whole slices."""
+        my, mx = plan[4], plan[5]
+        B = x_n.shape[0]
         if condition == "slice":
-            cond = self._tile_cond_slice(x_n, Tl)
-        else:
-            cond = self._cond_buffers("til", R)
-            for lo, hi in passes:
-                for e, (pe, la) in zip(engines, cond):
-                    e.encode_condition(x_in[lo:hi])
-                    pe[lo:hi].copy_(e.prompt_emb)
-                    la[lo:hi].copy_(e.local_all)
+            return self._tile_cond_slice(x_n, my * mx)
+        cond = self._cond_buffers("til", B * my * mx)
+        for lo, hi in self._fused_passes(B, my, mx):
+            for e, (pe, la) in zip(self._engines(), cond):
+                e.encode_condition(x_in[lo:hi])
+                pe[lo:hi].copy_(e.prompt_emb)
+                la[lo:hi].copy_(e.local_all)
+        return cond
+
+    def _rows_per_replica(self, x_in, cond, B, K):
+        """The input tiles and conditioning rows (_tile_cond_rows) of B slices, a slice's T rows repeated for its K replicas:
+        row (b K + k) T + j = row b T + j (fd_rows_repeat_f32 with a row length of T times a row's)."""
+        s = _stream(x_in)
+        x_rows = torch.empty((x_in.shape[0] * K,) + tuple(x_in.shape[1:]), device=x_in.device, dtype=torch.float32)
+        L.call("fd_rows_repeat_f32", _p(x_in), _p(x_rows), B, K, x_in.numel() // B, s)
+        rows = self._cond_buffers("tens", x_in.shape[0] * K)
+        for src, dst in zip(cond, rows):
+            for a, b in zip(src, dst):
+                L.call("fd_rows_repeat_f32", _p(a), _p(b), B, K, a.numel() // B, s)
+        return x_rows, rows
+
+    def _tiled_fused_loop(self, x_in, img, cond, seeds, plan, shape):
+        """One trajectory of B slices of H x W, shape = (B, H, W), as R = B my mx tile rows (sample_tiled's docstring), given the
+        rows' input tiles x_in, their x_T img (updated in place), their conditioning rows cond (_tile_cond_rows) and one seed
+        per slice: sample_tiled hands in its slices' rows, sample_ensemble those of its B K replicas.  Per step: [fd_obj_begin
+        on the ancestral sampler,] per U-Net of the plan and per sub-batch load_condition + forward into the rows of o0 / o1,
+        then one fd_tiles_step_* launch over all R rows in place on img, which also writes the slice image on the last step."""
+        ys, xs, wy, wx, my, mx, x4, th, tw = plan
+        B, H, W = shape
+        dev, s = x_in.device, _stream(x_in)
+        mode = self._plan()[0]
+        engines = self._engines()
+        passes = self._fused_passes(B, my, mx)
+        nmax = max(hi - lo for lo, hi in passes)
         outs = [torch.empty_like(x_in) for _ in engines]
         o0, o1 = self._o01(outs)
         final = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
@@ -2212,7 +2311,7 @@ class Trainer(object):
 
     @torch.no_grad()
     def test(self, sample=False, last=True, FID=False, batch_size=1, n_samples=1, ensemble_seed=0, tile=None, overlap=0,
-             tile_condition="tile", tile_fuse="final"):
+             tile_condition="tile", tile_fuse="final", tiled_ensemble=False):
         """Evaluation loop of src/DADiff.py:1817-1966: init() the schedule, denoise every slice,
         PSNR/SSIM/RMSE vs NDCT (on device), np.save each output in [0,1], per-anatomy / per-dose means.
         `batch_size` > 1 batches independent slices (the reference uses 1).  `sample=True` keeps the
@@ -2224,11 +2323,14 @@ class Trainer(object):
         `tile` (an int or (th, tw); None: whole slices, as ever): every slice is sampled as overlapping tiles
         (ResidualDiffusion.sample_tiled with `overlap`, condition=`tile_condition` and fuse=`tile_fuse`) under the slice seed
         `ensemble_seed` + its dataset index; the metrics and the saved image are those of the blended slice.  Ensembles of tiled samples
-        (n_samples > 1) and last=False are not built and raise."""
+        (n_samples > 1 with a tile) are opt-in: `tiled_ensemble=True` runs sample_ensemble(tile=...) under the same slice seeds and
+        scores and saves the ensemble mean and `<name>_std.npy` as above; without the switch the combination raises (the raising
+        default is pinned by tests).  last=False with a tile is not built and raises."""
         if int(n_samples) < 1:
             raise RuntimeError(f"Trainer.test: n_samples must be at least 1 (got {n_samples})")
-        if tile is not None and int(n_samples) > 1:
-            raise RuntimeError(f"Trainer.test: tile={tile!r} with n_samples={n_samples}: ensembles of tiled samples are not built")
+        if tile is not None and int(n_samples) > 1 and not tiled_ensemble:
+            raise RuntimeError(f"Trainer.test: tile={tile!r} with n_samples={n_samples}: ensembles of tiled samples are opt-in: "
+                               "pass tiled_ensemble=True (DESIGN.md section 8)")
         if tile is not None and not last:
             raise RuntimeError("Trainer.test: tile with last=False is not built (sample_tiled returns the final image)")
         # batch_size 1 is the reference's loop: one slice per sample() call -> the kernel set for a lone slice (DAEngine
@@ -2279,7 +2381,8 @@ class Trainer(object):
             xs = [torch.stack([it[k] for it in items]).to(self.device) for k in range(1, len(items[0]))]
             y_std = None
             if n_samples > 1:
-                ens = model.sample_ensemble(xs, n_samples, slice_seeds=[ensemble_seed + i for i in idx])
+                tkw = {} if tiled is None else dict(tile=tiled[0], overlap=tiled[1], tile_condition=tiled[2], tile_fuse=tiled[3])
+                ens = model.sample_ensemble(xs, n_samples, slice_seeds=[ensemble_seed + i for i in idx], **tkw)
                 y_pred, y_std = ens.mean, ens.std
             elif tiled is not None:
                 outs = model.sample_tiled(xs, tiled[0], tiled[1], slice_seeds=[ensemble_seed + i for i in idx], condition=tiled[2],

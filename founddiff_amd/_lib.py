@@ -193,6 +193,8 @@ SIGNATURES = {
     "fd_tiles_step_ddim_f32": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "fd_tiles_step_keyed_f32": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp,
                                       i32, vp]),
+    # (tiles, wy, wx, ys, xs, samples or None, mean, std, ws, spread, B, K, H, W, th, tw, my, mx, xs_mult4, stream)
+    "fd_tiles_ensemble_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "fd_store_gather_f32": (i32, [vp, vp, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "fd_res_qsample_store_f32": (i32, [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32,
                                        i32, vp]),

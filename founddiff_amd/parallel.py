@@ -44,7 +44,7 @@ def gather_volume(local, world, n_total=None):
 
 
 def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampler_kwargs=None, n_samples=1, tile=None,
-                  overlap=0, tile_fuse="final"):
+                  overlap=0, tile_fuse="final", tiled_ensemble=False):
     """Denoise a whole volume ldct (N,1,H,W in [0,1], same tensor on every rank) with `diffusion`
     (a founddiff_amd.DADiff.ResidualDiffusion living on this rank's device).  x_T noise is keyed
     by the GLOBAL slice index, and so is the ancestral sampler's per-step noise (`slice_seeds`:
@@ -55,13 +55,16 @@ def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampl
     sample()'s and do not reach it.
     `tile` (an int or (th, tw); None: whole slices): every slice is sampled as overlapping tiles (sample_tiled with `overlap` and
     fuse=`tile_fuse`) under the slice seed `noise_seed` + its GLOBAL index; every row is keyed, so the volume is the same on any
-    `world` and for any `batch`.  Together with n_samples > 1 it raises: tiled ensembles are not built."""
+    `world` and for any `batch`.  Together with n_samples > 1 it is opt-in: `tiled_ensemble=True` samples every slice as a tiled
+    ensemble (sample_ensemble(tile=...)) under the same seeds and returns (mean, std) as above, the same on any `world` and for
+    any `batch`; without the switch the combination raises (the raising default is pinned by tests)."""
     n = ldct.shape[0]
     lo, hi = shard_range(n, world, rank)
     dev = next(diffusion.parameters()).device
-    if tile is not None:
-        if int(n_samples) > 1:
-            raise RuntimeError(f"sample_volume: tile={tile!r} with n_samples={n_samples}: ensembles of tiled samples are not built")
+    if tile is not None and int(n_samples) > 1 and not tiled_ensemble:
+        raise RuntimeError(f"sample_volume: tile={tile!r} with n_samples={n_samples}: ensembles of tiled samples are opt-in: pass "
+                           "tiled_ensemble=True (DESIGN.md section 8)")
+    if tile is not None and int(n_samples) <= 1:
         outs = [diffusion.sample_tiled([ldct[s:min(s + batch, hi)].to(dev)], tile, overlap,
                                        slice_seeds=torch.arange(s, min(s + batch, hi), dtype=torch.int64) + int(noise_seed),
                                        fuse=tile_fuse)[-1]
@@ -69,11 +72,12 @@ def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampl
         local = torch.cat(outs, 0) if outs else ldct.new_zeros((0,) + tuple(ldct.shape[1:])).to(dev)
         return gather_volume(local, world, n)
     if int(n_samples) > 1:
+        tkw = {} if tile is None else dict(tile=tile, overlap=overlap, tile_fuse=tile_fuse)
         means, stds = [], []
         for s in range(lo, hi, batch):
             e = min(s + batch, hi)
             ens = diffusion.sample_ensemble([ldct[s:e].to(dev)], int(n_samples),
-                                            slice_seeds=torch.arange(s, e, dtype=torch.int64) + int(noise_seed))
+                                            slice_seeds=torch.arange(s, e, dtype=torch.int64) + int(noise_seed), **tkw)
             means.append(ens.mean)
             stds.append(ens.std)
         empty = ldct.new_zeros((0,) + tuple(ldct.shape[1:])).to(dev)

@@ -6,7 +6,7 @@ pixels and the last one is shifted back to end at the border, so it may overlap 
 """
 import numpy as np
 
-from .ensemble import SEED_LIMIT, _M64, ensemble_passes, splitmix64
+from .ensemble import SEED_LIMIT, _M64, ensemble_passes, ensemble_seeds, splitmix64
 
 _TILE = 0xA0761D6478BD642F             # odd, and not ensemble._REPLICA: tile j and replica j of a slice get different streams
 
@@ -80,6 +80,23 @@ def tile_seeds(slice_seeds, n_tiles):
         for j in range(1, n_tiles):
             out[b, j] = splitmix64(s ^ ((j * _TILE) & _M64)) >> 2
     return out
+
+
+def tiled_ensemble_seeds(slice_seeds, K, n_tiles):
+    """(B, K, n_tiles) int64, the seeds of a tiled ensemble (ResidualDiffusion.sample_ensemble(tile=...)): replica first, then tile,
+    tile_seeds(ensemble_seeds(slice_seeds, K).reshape(-1), n_tiles).  [b, 0, 0] is the slice's own seed and [:, k, :] is tile_seeds
+    of replica k's seed, so a replica is an ordinary sample_tiled call under its ensemble seed.  The rows lie slice-major, then
+    replica, then tile: row ((b K + k) my + iy) mx + ix."""
+    K, n_tiles = int(K), int(n_tiles)
+    if K < 1:
+        raise RuntimeError(f"tiled_ensemble_seeds: K must be at least 1 (got {K})")
+    if n_tiles < 1:
+        raise RuntimeError(f"tiled_ensemble_seeds: n_tiles must be at least 1 (got {n_tiles})")
+    seeds = [int(s) for s in np.asarray(slice_seeds).reshape(-1).tolist()]
+    for b, s in enumerate(seeds):
+        if not 0 <= s < SEED_LIMIT:
+            raise RuntimeError(f"tiled_ensemble_seeds: seed {s} of slice {b} is outside [0, 2^62)")
+    return tile_seeds(ensemble_seeds(seeds, K).reshape(-1), n_tiles).reshape(len(seeds), K, n_tiles)
 
 
 def tile_passes(B, my, mx, rows_max, multiple=1):

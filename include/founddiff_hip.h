@@ -877,6 +877,17 @@ int fd_tiles_step_keyed_f32(int mode, const float *o0, const float *o1, const fl
                             const float *par_table, const int *t_dev, const int64_t *slice_seeds, const float *wy, const float *wx,
                             const int *ys, const int *xs, int B, int H, int W, int th, int tw, int my, int mx, int xs_mult4,
                             float *img_out, float *slice_out, int T, void *stream);
+/* ---- the final tile images of K keyed realisations per slice, to the ensemble's statistics (fd_tiles_ensemble.hip;
+ * ResidualDiffusion.sample_ensemble(tile=...)).  fp32, the same in both builds; no atomics.  tiles [B K my mx][th tw], row
+ * ((b K + k) my + iy) mx + ix; the plan and weight arguments are fd_tiles_blend_f32's, the limit is B K my mx <= 65535, K >= 1.
+ * mean, std [B][H W], spread [B], ws: B * fd_ensemble_nblk(H W) floats; samples [B K][H W], or NULL: the K blended slice images
+ * are then not written (mean, std and spread are the same).  All four outputs have the bits of fd_tiles_blend_f32 over the B K
+ * pseudo-slices followed by fd_ensemble_stats_f32(B, K, H W): a slice's rows depend on K, H, W, the plan and its own tiles alone.
+ * 16-byte accesses when xs_mult4, W % 4 == 0, tw % 4 == 0 and tiles, wx, mean, std (and samples, if given) are 16-byte aligned;
+ * the scalar form has the same bits. */
+int fd_tiles_ensemble_f32(const float *tiles, const float *wy, const float *wx, const int *ys, const int *xs, float *samples,
+                          float *mean, float *std, float *ws, float *spread, int B, int K, int H, int W, int th, int tw, int my,
+                          int mx, int xs_mult4, void *stream);
 
 /* ---- a training batch from a slice store on the device (fd_train_data.hip; data/pdf_dataset.py:521-545) -------
  * nd [n_nd][H][W], ld [n_ld][H][W] fp32 in [0, 1].  Item b of the batch is the pair nd[nd_slot[b]], ld[ld_slot[b]] (int64 [B],
