@@ -30,13 +30,15 @@ from . import _lib as L
 from . import arch
 from . import diffusion_train as dt
 from .engine import DAEngine, _p
-from .ensemble import ensemble_passes, ensemble_seeds
-from .metrics import ensemble_stats
+from .ensemble import ensemble_passes, ensemble_seeds, quantile_suffix, quantile_table
+from .metrics import ensemble_quantiles, ensemble_stats, interval_coverage
 from .tiling import tile_pair, tile_passes, tile_plan, tile_seeds, tile_weights, tiled_ensemble_seeds
 
 ModelResPrediction = namedtuple("ModelResPrediction", ["pred_res", "pred_noise", "pred_x_start"])
 # sample_ensemble: mean, std (B,1,H,W) in [0, 1] units, spread (B,), samples (B,K,1,H,W) or None
 EnsembleResult = namedtuple("EnsembleResult", ["mean", "std", "spread", "samples"])
+# sample_ensemble(quantiles=levels): the same four, quantiles (B,Q,1,H,W) in the units of mean, levels the tuple of Q levels
+EnsembleQuantiles = namedtuple("EnsembleQuantiles", ["mean", "std", "spread", "samples", "quantiles", "levels"])
 
 
 def set_seed(SEED):
@@ -1271,7 +1273,7 @@ class ResidualDiffusion(nn.Module):
 
     @torch.no_grad()
     def sample_ensemble(self, x_input, n_samples, slice_seeds=None, return_samples=False, *, tile=None, overlap=0,
-                        tile_condition="tile", tile_fuse="final"):
+                        tile_condition="tile", tile_fuse="final", quantiles=None):
         """K = n_samples keyed realisations of every slice of x_input = [ldct (B,1,H,W) in [0,1]], reduced on the device: an
         EnsembleResult of the per-pixel mean and sample standard deviation over a slice's K final images (both (B,1,H,W), in the
         [0, 1] units of sample()[-1]), spread (B,) = sqrt(mean over pixels of std^2), and the images themselves (B,K,1,H,W) when
@@ -1289,12 +1291,24 @@ class ResidualDiffusion(nn.Module):
         through the paths of sample() in tile_passes, and fd_tiles_ensemble_f32 takes their final images straight to mean, std
         and spread (the K blended images are written only for `return_samples`) with the bits of fd_tiles_blend_f32 followed by
         fd_ensemble_stats_f32.  tile_fuse="step": the fused loop of sample_tiled over the B K replicas as pseudo-slices, each
-        under its replica seed, then fd_ensemble_stats_f32.  Nothing returned depends on B, max_sub_batch, streams or the passes."""
+        under its replica seed, then fd_ensemble_stats_f32.  Nothing returned depends on B, max_sub_batch, streams or the passes.
+        `quantiles` (keyword-only; None: all of the above, the same launches): a sequence of 1 to 8 levels in [0, 1].  The result
+        is then an EnsembleQuantiles, whose `quantiles` (B,Q,1,H,W) holds per pixel the levels of the slice's K final images in the
+        caller's order (metrics.ensemble_quantiles: the `linear` rule, fd_ensemble_order_f32 on the K images) and whose `levels` is
+        the tuple of levels; mean, std, spread and samples are what the call without `quantiles` returns, bit for bit.  On the
+        tile_fuse="final" path the K blended images are written for the order kernel and returned only under `return_samples`."""
         K = int(n_samples)
         if K < 1:
             raise RuntimeError(f"sample_ensemble: n_samples must be at least 1 (got {n_samples})")
         if self.input_condition:
             raise RuntimeError("sample_ensemble: input_condition=True is not built (one input plane per slice)")
+        if quantiles is not None:                                        # the levels are checked before any work
+            quantiles = tuple(float(q) for q in quantiles)
+            quantile_table(quantiles, K)
+            ens = self.sample_ensemble(x_input, K, slice_seeds, True, tile=tile, overlap=overlap, tile_condition=tile_condition,
+                                       tile_fuse=tile_fuse)
+            return EnsembleQuantiles(ens.mean, ens.std, ens.spread, ens.samples if return_samples else None,
+                                     ensemble_quantiles(ens.samples, quantiles), quantiles)
         if tile is not None:
             return self._sample_ensemble_tiled(x_input, K, slice_seeds, return_samples, tile, overlap, tile_condition, tile_fuse)
         x01 = list(x_input)[0].contiguous().float()
@@ -2311,7 +2325,7 @@ class Trainer(object):
 
     @torch.no_grad()
     def test(self, sample=False, last=True, FID=False, batch_size=1, n_samples=1, ensemble_seed=0, tile=None, overlap=0,
-             tile_condition="tile", tile_fuse="final", tiled_ensemble=False):
+             tile_condition="tile", tile_fuse="final", tiled_ensemble=False, *, quantiles=None, estimate="mean"):
         """Evaluation loop of src/DADiff.py:1817-1966: init() the schedule, denoise every slice,
         PSNR/SSIM/RMSE vs NDCT (on device), np.save each output in [0,1], per-anatomy / per-dose means.
         `batch_size` > 1 batches independent slices (the reference uses 1).  `sample=True` keeps the
@@ -2325,9 +2339,30 @@ class Trainer(object):
         `ensemble_seed` + its dataset index; the metrics and the saved image are those of the blended slice.  Ensembles of tiled samples
         (n_samples > 1 with a tile) are opt-in: `tiled_ensemble=True` runs sample_ensemble(tile=...) under the same slice seeds and
         scores and saves the ensemble mean and `<name>_std.npy` as above; without the switch the combination raises (the raising
-        default is pinned by tests).  last=False with a tile is not built and raises."""
+        default is pinned by tests).  last=False with a tile is not built and raises.
+        `quantiles` (keyword-only, with n_samples > 1): a sequence of levels in [0, 1]; outside training every level's map of
+        the ensemble (sample_ensemble(quantiles=...)) is saved beside the image as `<name>_qNNNN.npy`, NNNN the level in
+        per-mille (0.05: `_q0050`; levels that collide there raise), cropped like `_std`.  With at least two levels the share of
+        each slice's NDCT pixels inside [lowest level, highest level] (metrics.interval_coverage) goes to
+        `self.test_running_coverage`, and its mean is logged next to the nominal highest - lowest.
+        `estimate` (keyword-only): "mean", or "median" (n_samples > 1): the metrics and the saved image are those of the ensemble's
+        0.5 level, which joins the levels if it is not among them."""
         if int(n_samples) < 1:
             raise RuntimeError(f"Trainer.test: n_samples must be at least 1 (got {n_samples})")
+        if estimate not in ("mean", "median"):
+            raise RuntimeError(f"Trainer.test: estimate must be 'mean' or 'median' (got {estimate!r})")
+        if (quantiles is not None or estimate == "median") and int(n_samples) <= 1:
+            raise RuntimeError(f"Trainer.test: quantiles and estimate='median' need an ensemble, n_samples > 1 (got {n_samples})")
+        qplan = None
+        if quantiles is not None or estimate == "median":
+            # (levels handed to sample_ensemble, how many of them are the caller's, the estimate's index or None)
+            levels = tuple(float(q) for q in (() if quantiles is None else quantiles))
+            n_user = len(levels)
+            if estimate == "median" and 0.5 not in levels:
+                levels = levels + (0.5,)
+            quantile_table(levels, int(n_samples))
+            quantile_suffix(levels[:n_user])
+            qplan = (levels, n_user, levels.index(0.5) if estimate == "median" else None)
         if tile is not None and int(n_samples) > 1 and not tiled_ensemble:
             raise RuntimeError(f"Trainer.test: tile={tile!r} with n_samples={n_samples}: ensembles of tiled samples are opt-in: "
                                "pass tiled_ensemble=True (DESIGN.md section 8)")
@@ -2347,12 +2382,13 @@ class Trainer(object):
                 for u in unets:                                           # a batch of tiles: the default kernel set)
                     u.low_latency = True
             tiled = None if tile is None else (tile, overlap, tile_condition, tile_fuse)
-            return self._test(sample, last, FID, batch_size, int(n_samples), int(ensemble_seed), tiled)
+            return self._test(sample, last, FID, batch_size, int(n_samples), int(ensemble_seed), tiled, qplan)
         finally:
             for u, v in zip(unets, saved):
                 u.low_latency = v
 
-    def _test(self, sample, last, FID, batch_size, n_samples=1, ensemble_seed=0, tiled=None):
+    def _test(self, sample, last, FID, batch_size, n_samples=1, ensemble_seed=0, tiled=None, qplan=None):
+        """`qplan`: None, or test()'s (levels, how many of them are the caller's, the index of the estimate's level or None)"""
         from .metrics import compute_metrics
         model = self.ema.ema_model                   # inference uses the EMA weights (src/DADiff.py:1818-1822)
         model.init()
@@ -2373,17 +2409,32 @@ class Trainer(object):
             return None
         self.test_running_psnr, self.test_running_ssim, self.test_running_rmse = [], [], []
         self.test_image_names = []
+        q_names, q_cover = [], None
+        if qplan is not None:
+            self.test_running_coverage = []
+            q_names = quantile_suffix(qplan[0][:qplan[1]])
+            if qplan[1] >= 2:                                  # the interval [lowest level, highest level] of the caller's levels
+                user = list(qplan[0][:qplan[1]])
+                q_cover = (user.index(min(user)), user.index(max(user)))
         ds = self.sample_dataset
         for s in range(0, len(ds), batch_size):
             idx = list(range(s, min(s + batch_size, len(ds))))
             items = [ds[i] for i in idx]
             y = torch.stack([it[0] for it in items]).to(self.device)
             xs = [torch.stack([it[k] for it in items]).to(self.device) for k in range(1, len(items[0]))]
-            y_std = None
+            y_std = y_q = cover = None
             if n_samples > 1:
                 tkw = {} if tiled is None else dict(tile=tiled[0], overlap=tiled[1], tile_condition=tiled[2], tile_fuse=tiled[3])
+                if qplan is not None:
+                    tkw["quantiles"] = qplan[0]
                 ens = model.sample_ensemble(xs, n_samples, slice_seeds=[ensemble_seed + i for i in idx], **tkw)
                 y_pred, y_std = ens.mean, ens.std
+                if qplan is not None:
+                    y_q = ens.quantiles
+                    if qplan[2] is not None:                   # estimate="median": the 0.5 level is scored and saved
+                        y_pred = y_q[:, qplan[2]]
+                    if q_cover is not None and not sample:
+                        cover = interval_coverage(y_q[:, q_cover[0]], y_q[:, q_cover[1]], y)[1]
             elif tiled is not None:
                 outs = model.sample_tiled(xs, tiled[0], tiled[1], slice_seeds=[ensemble_seed + i for i in idx], condition=tiled[2],
                                           fuse=tiled[3])
@@ -2414,12 +2465,17 @@ class Trainer(object):
                     self.test_running_ssim.append(m[j, 1])
                     self.test_running_rmse.append(m[j, 2])
                     print("(psnr: %.4f, ssim: %.4f,rmse:.%.4f) " % (m[j, 0], m[j, 1], m[j, 2]))
+                    if cover is not None:
+                        self.test_running_coverage.append(float(cover[j]))
                 if not getattr(self.opt, "is_train", False) and not sample:
                     h, w = y_save.shape[-2:]
                     np.save(self.results_folder + "/" + file_name[:-4], y_save[j].detach().cpu().numpy().reshape(h, w))
                     if y_std is not None:                      # the spread of the ensemble, cropped like the image
                         np.save(self.results_folder + "/" + file_name[:-4] + "_std",
                                 y_std[j, :, :h, :w].detach().cpu().numpy().reshape(h, w))
+                    for qi, suffix in enumerate(q_names):      # the caller's levels, cropped like the image
+                        np.save(self.results_folder + "/" + file_name[:-4] + suffix,
+                                y_q[j, qi, :, :h, :w].detach().cpu().numpy().reshape(h, w))
                     print("test-save " + file_name)
         if sample:
             print("test end")
@@ -2427,6 +2483,10 @@ class Trainer(object):
         self.test_group_means = self._log_groups()
         self.train_logger.info("test_psnr: {:.4f}, test_ssim: {:.4f},test_rmse:{:.4f}".format(
             np.mean(self.test_running_psnr), np.mean(self.test_running_ssim), np.mean(self.test_running_rmse)))
+        if q_cover is not None:
+            self.train_logger.info("test_coverage: {:.4f} of the NDCT pixels inside [q{:g}, q{:g}] (nominal {:.4f})".format(
+                np.mean(self.test_running_coverage), qplan[0][q_cover[0]], qplan[0][q_cover[1]],
+                qplan[0][q_cover[1]] - qplan[0][q_cover[0]]))
         print("test end")
         return float(np.mean(self.test_running_psnr)), float(np.mean(self.test_running_ssim)), \
             float(np.mean(self.test_running_rmse))

@@ -187,6 +187,11 @@ SIGNATURES = {
     "fd_ensemble_nblk": (i32, [i64]),
     "fd_rows_repeat_f32": (i32, [vp, vp, i32, i32, i64, vp]),
     "fd_ensemble_stats_f32": (i32, [vp, vp, vp, vp, vp, i32, i32, i64, vp]),
+    # (samples, out, lo, hi, frac: host arrays of Q, B, K, Q, n, stream)
+    "fd_ensemble_order_f32": (i32, [vp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), i32, i32, i32, i64, vp]),
+    "fd_ensemble_coverage_nblk": (i32, [i64]),
+    # (lo_map, its batch stride, hi_map, its stride, target, its stride, ws, count, B, n, stream)
+    "fd_ensemble_coverage_f32": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, i32, i64, vp]),
     "fd_tiles_gather_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "fd_tiles_blend_f32": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     # (mode, o0, o1, x_t, x_in, par[, t_dev, slice_seeds], wy, wx, ys, xs, B, H, W, th, tw, my, mx, xs_mult4, img_out, slice_out[, T])

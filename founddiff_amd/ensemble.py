@@ -1,4 +1,5 @@
-"""Seeds and passes of an ensemble of K keyed realisations per slice (ResidualDiffusion.sample_ensemble).  Pure numpy, no GPU.
+"""Seeds, passes and quantile tables of an ensemble of K keyed realisations per slice (ResidualDiffusion.sample_ensemble).  Pure
+numpy, no GPU.
 
 A replica is an ordinary slice of the samplers with a seed of its own: x_T and the ancestral sampler's step noise are functions of
 (seed, step, pixel) alone (fd_keyed_normal), so replica k of a slice is the same image in any batch, on any rank and stream.
@@ -34,6 +35,38 @@ def ensemble_seeds(slice_seeds, K):
         for k in range(1, K):
             out[b, k] = splitmix64(s ^ ((k * _REPLICA) & _M64)) >> 2
     return out
+
+
+QUANTILE_LEVELS_MAX = 8                # levels per call of fd_ensemble_order_f32
+
+
+def quantile_table(levels, K):
+    """(lo, hi int32, frac float32), one entry per level in the caller's order: level q of K sorted values v_(0) <= ... <= v_(K-1) is
+    v_(lo) + frac (v_(hi) - v_(lo)), the `linear` rule of numpy.quantile / torch.quantile.  In float64 h = q (K - 1), an h within
+    1e-9 of an integer is that integer (0.1 * 10 is not 1), lo = floor(h), hi = min(lo + 1, K - 1), frac = float32(h - lo).
+    frac == 0 makes the level an exact selection: minimum, maximum, the median of an odd K, every level at K = 1."""
+    K = int(K)
+    if K < 1:
+        raise RuntimeError(f"quantile_table: K must be at least 1 (got {K})")
+    q = np.asarray(levels, dtype=np.float64).reshape(-1)
+    if not 1 <= q.size <= QUANTILE_LEVELS_MAX:
+        raise RuntimeError(f"quantile_table: 1 to {QUANTILE_LEVELS_MAX} levels per call (got {q.size})")
+    if not np.isfinite(q).all() or q.min() < 0 or q.max() > 1:
+        raise RuntimeError(f"quantile_table: levels must be finite and in [0, 1] (got {q.tolist()})")
+    h = q * (K - 1)
+    r = np.rint(h)
+    h = np.where(np.abs(h - r) <= 1e-9, r, h)
+    lo = np.floor(h)
+    hi = np.minimum(lo + 1, K - 1)
+    return lo.astype(np.int32), hi.astype(np.int32), (h - lo).astype(np.float32)
+
+
+def quantile_suffix(levels):
+    """['_q0050', ...]: a level's file-name suffix, the level in per-mille on four digits; levels that collide there raise"""
+    names = ["_q%04d" % int(round(1000 * float(q))) for q in levels]
+    if len(set(names)) != len(names):
+        raise RuntimeError(f"quantile_suffix: levels {list(levels)} collide when rounded to per-mille ({names})")
+    return names
 
 
 def ensemble_passes(B, K, rows_max):

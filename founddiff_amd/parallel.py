@@ -44,7 +44,7 @@ def gather_volume(local, world, n_total=None):
 
 
 def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampler_kwargs=None, n_samples=1, tile=None,
-                  overlap=0, tile_fuse="final", tiled_ensemble=False):
+                  overlap=0, tile_fuse="final", tiled_ensemble=False, *, quantiles=None):
     """Denoise a whole volume ldct (N,1,H,W in [0,1], same tensor on every rank) with `diffusion`
     (a founddiff_amd.DADiff.ResidualDiffusion living on this rank's device).  x_T noise is keyed
     by the GLOBAL slice index, and so is the ancestral sampler's per-step noise (`slice_seeds`:
@@ -57,7 +57,11 @@ def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampl
     fuse=`tile_fuse`) under the slice seed `noise_seed` + its GLOBAL index; every row is keyed, so the volume is the same on any
     `world` and for any `batch`.  Together with n_samples > 1 it is opt-in: `tiled_ensemble=True` samples every slice as a tiled
     ensemble (sample_ensemble(tile=...)) under the same seeds and returns (mean, std) as above, the same on any `world` and for
-    any `batch`; without the switch the combination raises (the raising default is pinned by tests)."""
+    any `batch`; without the switch the combination raises (the raising default is pinned by tests).
+    `quantiles` (keyword-only, with n_samples > 1; it raises otherwise): a sequence of Q levels in [0, 1]; returns (mean, std,
+    quantiles), the third the (N,Q,1,H,W) volume of sample_ensemble(quantiles=...)'s maps, gathered like the first two."""
+    if quantiles is not None and int(n_samples) <= 1:
+        raise RuntimeError(f"sample_volume: quantiles need an ensemble, n_samples > 1 (got {n_samples})")
     n = ldct.shape[0]
     lo, hi = shard_range(n, world, rank)
     dev = next(diffusion.parameters()).device
@@ -73,15 +77,23 @@ def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampl
         return gather_volume(local, world, n)
     if int(n_samples) > 1:
         tkw = {} if tile is None else dict(tile=tile, overlap=overlap, tile_fuse=tile_fuse)
-        means, stds = [], []
+        if quantiles is not None:
+            tkw["quantiles"] = quantiles = tuple(float(q) for q in quantiles)
+        means, stds, quants = [], [], []
         for s in range(lo, hi, batch):
             e = min(s + batch, hi)
             ens = diffusion.sample_ensemble([ldct[s:e].to(dev)], int(n_samples),
                                             slice_seeds=torch.arange(s, e, dtype=torch.int64) + int(noise_seed), **tkw)
             means.append(ens.mean)
             stds.append(ens.std)
+            if quantiles is not None:
+                quants.append(ens.quantiles)
         empty = ldct.new_zeros((0,) + tuple(ldct.shape[1:])).to(dev)
-        return tuple(gather_volume(torch.cat(v, 0) if v else empty, world, n) for v in (means, stds))
+        vols = tuple(gather_volume(torch.cat(v, 0) if v else empty, world, n) for v in (means, stds))
+        if quantiles is None:
+            return vols
+        empty_q = ldct.new_zeros((0, len(quantiles)) + tuple(ldct.shape[1:])).to(dev)
+        return vols + (gather_volume(torch.cat(quants, 0) if quants else empty_q, world, n),)
     outs = []
     for s in range(lo, hi, batch):
         e = min(s + batch, hi)

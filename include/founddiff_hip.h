@@ -835,6 +835,30 @@ int fd_rows_repeat_f32(const float *src, float *dst, int B, int K, int64_t n, vo
 int fd_ensemble_stats_f32(const float *samples, float *mean, float *std, float *ws, float *spread, int B, int K, int64_t n,
                           void *stream);
 
+/* ---- per-pixel order statistics of an ensemble and the coverage of a target (fd_ensemble_order.hip;
+ * ResidualDiffusion.sample_ensemble(quantiles=...), metrics.ensemble_quantiles, metrics.interval_coverage) --------
+ * fp32, the same in both builds of the library.  Deterministic, no float atomics.
+ * fd_ensemble_order_f32: samples [B][K][n] -> out [B][Q][n].  Per pixel, with its K values in ascending order v_(0) <= ... <=
+ *   v_(K-1): out[b][j] = fmaf(frac[j], v_(hi[j]) - v_(lo[j]), v_(lo[j])), and v_(lo[j]) itself, bit for bit, where frac[j] == 0
+ *   (minimum, maximum, the median of an odd K, every level at K = 1).  lo, hi (int) and frac (float) are HOST arrays of Q entries,
+ *   read in the entry and handed to the kernel by value: no device table, no upload, and the call can be captured.
+ *   1 <= Q <= 8, 0 <= lo <= hi <= K - 1, 0 <= frac <= 1, 1 <= K <= 65535, 1 <= B <= 65535, 0 < n < 2^40.  Equal values are
+ *   interchangeable (a pixel that holds -0 and +0 may return either).  If any of a pixel's K values is NaN, every level of that
+ *   pixel is NaN.  K <= 32 sorts in registers (every sample read once); a larger K selects by counting ranks and reads the K values
+ *   K / 4 times, so its time grows with K^2.  Both give the same bits, and so do the 16-byte form (n % 4 == 0, samples and out
+ *   16-byte aligned) and the scalar form.  A pixel's outputs depend on its own K values and the table alone, not on B, the other
+ *   slices or the launch.  No workspace.
+ * fd_ensemble_coverage_f32: count [B] (int64) = the number of pixels i < n with lo_map[b][i] <= target[b][i] <= hi_map[b][i]; a
+ *   NaN compares false.  Slice b of each map starts b * its own stride (in floats, >= 0) past the pointer, so the two maps may be
+ *   rows of one out [B][Q][n] (stride Q n).  Exact: integer block counts, added per slice in index order.  16-byte accesses when
+ *   n % 4 == 0, the three pointers are 16-byte aligned and the strides are multiples of 4; scalar otherwise.
+ *   ws: B * fd_ensemble_coverage_nblk(n) ints (0: unsupported n). */
+int fd_ensemble_order_f32(const float *samples, float *out, const int *lo, const int *hi, const float *frac, int B, int K, int Q,
+                          int64_t n, void *stream);
+int fd_ensemble_coverage_nblk(int64_t n);
+int fd_ensemble_coverage_f32(const float *lo_map, int64_t lo_bstride, const float *hi_map, int64_t hi_bstride, const float *target,
+                             int64_t target_bstride, int *ws, int64_t *count, int B, int64_t n, void *stream);
+
 /* ---- a slice as overlapping tiles (fd_tiles.hip; ResidualDiffusion.sample_tiled; founddiff_amd/tiling.py) --------
  * fp32, the same in both builds of the library.  Deterministic, no atomics, no workspace.  The plan: my x mx tiles of th x tw
  * pixels at the origins ys [my], xs [mx] (int32, DEVICE memory; 0 <= ys <= H - th, 0 <= xs <= W - tw, a tile whose origin is
