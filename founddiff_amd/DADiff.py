@@ -6,7 +6,8 @@ Same class names, constructor kwargs, method names/signatures and state_dict key
 reference (`/root/reference/src/DADiff.py`; contract in SURVEY.md section 8b), so
 `checkpoints/<name>/sample/model-N.pt` loads unchanged.  The modules below hold parameters only:
 `forward` never runs a torch op on activations -- it hands device pointers to libfounddiff_hip.so
-through `founddiff_amd.engine.DAEngine`.
+through `founddiff_amd.engine.DAEngine`.  What the reference does not have -- `sample_ensemble`, `sample_tiled`, their results
+`EnsembleResult` / `EnsembleQuantiles` -- is `founddiff_amd/tiled_sampling.py`, a mixin of `ResidualDiffusion`.
 
 Training runs on the same classes: `Unet.trainable()` is a `unet_train.UnetTrunk` over the very
 parameters of the tree, `Unet.train_forward` runs the frozen DA-CLIP tower on the fp32 engine and the trunk under autograd on the HIP
@@ -16,7 +17,6 @@ around `diffusion_train.ClipRAdamEMA` on request: `UnetRes.trainable()` and `Tra
 """
 import copy
 import ctypes as C
-import functools
 import math
 import os
 import random
@@ -30,15 +30,15 @@ from . import _lib as L
 from . import arch
 from . import diffusion_train as dt
 from .engine import DAEngine, _p
-from .ensemble import ensemble_passes, ensemble_seeds, quantile_suffix, quantile_table
-from .metrics import ensemble_quantiles, ensemble_stats, interval_coverage
-from .tiling import tile_pair, tile_passes, tile_plan, tile_seeds, tile_weights, tiled_ensemble_seeds
+from .ensemble import quantile_suffix, quantile_table
+from .metrics import interval_coverage
+from .tiled_sampling import EnsembleQuantiles, EnsembleResult, TiledSampling  # noqa: F401 (the results are imported from here)
+from .tiling import tiled_ensemble_opt_in
 
 ModelResPrediction = namedtuple("ModelResPrediction", ["pred_res", "pred_noise", "pred_x_start"])
-# sample_ensemble: mean, std (B,1,H,W) in [0, 1] units, spread (B,), samples (B,K,1,H,W) or None
-EnsembleResult = namedtuple("EnsembleResult", ["mean", "std", "spread", "samples"])
-# sample_ensemble(quantiles=levels): the same four, quantiles (B,Q,1,H,W) in the units of mean, levels the tuple of Q levels
-EnsembleQuantiles = namedtuple("EnsembleQuantiles", ["mean", "std", "spread", "samples", "quantiles", "levels"])
+# Trainer.test's quantiles: the levels handed to sample_ensemble, the caller's among them (the first ones), the index of the
+# estimate's level or None
+_QuantilePlan = namedtuple("_QuantilePlan", ["levels", "user", "estimate"])
 
 
 def set_seed(SEED):
@@ -82,22 +82,6 @@ def _affine(x, a, b):
     out = torch.empty_like(x)
     L.call("fd_affine_f32", _p(x), a, b, _p(out), x.numel(), _stream(x))
     return out
-
-
-def _fuse_keyword(fn):
-    """sample_tiled's keyword-only `fuse`: "final" (the default) or "step".  It is taken here, in front of the method, and handed to
-    it as self._tile_fuse for the length of the call, so that the method keeps the parameter list tests/test_tiling_cpu.py pins
-    (inspect.signature follows __wrapped__ to it and therefore does NOT show `fuse`: the docstring is where it is documented)."""
-    @functools.wraps(fn)
-    def sample_tiled(self, *args, fuse="final", **kw):
-        if fuse not in ("final", "step"):
-            raise RuntimeError(f"sample_tiled: fuse must be 'final' or 'step' (got {fuse!r})")
-        self._tile_fuse = fuse
-        try:
-            return fn(self, *args, **kw)
-        finally:
-            self._tile_fuse = "final"
-    return sample_tiled
 
 
 class _ParamTree(nn.Module):
@@ -437,13 +421,15 @@ def load_weights(module, state_dict, what="checkpoint"):
     return res
 
 
-class ResidualDiffusion(nn.Module):
+class ResidualDiffusion(nn.Module, TiledSampling):
     """Residual (RDDM-style) diffusion sampler, reference src/DADiff.py:908-1380.
 
     Differences a caller can see: (1) the t-independent DA-CLIP branch is evaluated once per
     `sample()` instead of once per step; (2) `sample/ddim_sample/p_sample_loop/p_sample` take an
     optional `noise=` so that runs are reproducible against a CPU reference (the reference draws
-    from the global generator; the default here does too)."""
+    from the global generator; the default here does too); (3) sample_ensemble and sample_tiled, which the reference does not
+    have, are tiled_sampling.TiledSampling's."""
+    _normalize, _unnormalize = staticmethod(normalize_to_neg_one_to_one), staticmethod(unnormalize_to_zero_to_one)
 
     def __init__(self, model, *, image_size, timesteps=1000, sampling_timesteps=None, loss_type="l1",
                  objective="pred_res_noise", ddim_sampling_eta=0., condition=False, sum_scale=None,
@@ -1271,362 +1257,6 @@ class ResidualDiffusion(nn.Module):
             res = run()
         return res
 
-    @torch.no_grad()
-    def sample_ensemble(self, x_input, n_samples, slice_seeds=None, return_samples=False, *, tile=None, overlap=0,
-                        tile_condition="tile", tile_fuse="final", quantiles=None):
-        """K = n_samples keyed realisations of every slice of x_input = [ldct (B,1,H,W) in [0,1]], reduced on the device: an
-        EnsembleResult of the per-pixel mean and sample standard deviation over a slice's K final images (both (B,1,H,W), in the
-        [0, 1] units of sample()[-1]), spread (B,) = sqrt(mean over pixels of std^2), and the images themselves (B,K,1,H,W) when
-        `return_samples`.  Replica k of slice b is the image sample([x[b:b+1]], slice_seeds=[ensemble_seeds(slice_seeds, K)[b, k]])
-        returns, bit for bit: x_T -- and the step noise of the ancestral sampler -- is the keyed stream of the replica's seed on
-        every path.  The DA-CLIP tower runs once per slice; the B K rows (slice-major) run in passes of at most streams x
-        max_sub_batch through the paths of sample(), and nothing returned depends on that cut or on B.
-        `tile` (keyword-only, with `overlap`, `tile_condition`, `tile_fuse`; None: all of the above, unchanged): every replica is
-        sampled as overlapping tiles.  Replica k of slice b is then, bit for bit, the final image of sample_tiled([x[b:b+1]],
-        tile, overlap, slice_seeds=[ensemble_seeds(slice_seeds, K)[b, k]], condition=tile_condition, fuse=tile_fuse), on both
-        samplers and for every plan; the result has the same shapes and units.  The rows are tiling.tiled_ensemble_seeds':
-        replica first, then tile, row ((b K + k) my + iy) mx + ix, at most 65535 of them.  The tower runs once per slice and tile
-        ("tile") or once per slice ("slice"), never per replica: a slice's T conditioning rows and input tiles are repeated for
-        its K replicas.  tile_fuse="final": one keyed x_T field per (slice, replica), gathered per tile; the B K T rows run
-        through the paths of sample() in tile_passes, and fd_tiles_ensemble_f32 takes their final images straight to mean, std
-        and spread (the K blended images are written only for `return_samples`) with the bits of fd_tiles_blend_f32 followed by
-        fd_ensemble_stats_f32.  tile_fuse="step": the fused loop of sample_tiled over the B K replicas as pseudo-slices, each
-        under its replica seed, then fd_ensemble_stats_f32.  Nothing returned depends on B, max_sub_batch, streams or the passes.
-        `quantiles` (keyword-only; None: all of the above, the same launches): a sequence of 1 to 8 levels in [0, 1].  The result
-        is then an EnsembleQuantiles, whose `quantiles` (B,Q,1,H,W) holds per pixel the levels of the slice's K final images in the
-        caller's order (metrics.ensemble_quantiles: the `linear` rule, fd_ensemble_order_f32 on the K images) and whose `levels` is
-        the tuple of levels; mean, std, spread and samples are what the call without `quantiles` returns, bit for bit.  On the
-        tile_fuse="final" path the K blended images are written for the order kernel and returned only under `return_samples`."""
-        K = int(n_samples)
-        if K < 1:
-            raise RuntimeError(f"sample_ensemble: n_samples must be at least 1 (got {n_samples})")
-        if self.input_condition:
-            raise RuntimeError("sample_ensemble: input_condition=True is not built (one input plane per slice)")
-        if quantiles is not None:                                        # the levels are checked before any work
-            quantiles = tuple(float(q) for q in quantiles)
-            quantile_table(quantiles, K)
-            ens = self.sample_ensemble(x_input, K, slice_seeds, True, tile=tile, overlap=overlap, tile_condition=tile_condition,
-                                       tile_fuse=tile_fuse)
-            return EnsembleQuantiles(ens.mean, ens.std, ens.spread, ens.samples if return_samples else None,
-                                     ensemble_quantiles(ens.samples, quantiles), quantiles)
-        if tile is not None:
-            return self._sample_ensemble_tiled(x_input, K, slice_seeds, return_samples, tile, overlap, tile_condition, tile_fuse)
-        x01 = list(x_input)[0].contiguous().float()
-        B = x01.shape[0]
-        seeds = self._slice_seeds(slice_seeds, B, "cpu")
-        rows = torch.from_numpy(ensemble_seeds(seeds.numpy(), K).reshape(-1)).to(x01.device)
-        samples = self._range_checked(lambda: self._ensemble_rows(x01, K, rows), "a sampled image")
-        mean, std, spread = ensemble_stats(samples)
-        return EnsembleResult(mean, std, spread, samples if return_samples else None)
-
-    def _ensemble_rows(self, x01, K, seeds):
-        """The B K final images (B,K,1,H,W) of sample_ensemble; seeds (B K,) int64 on the device, row b K + k."""
-        B, npix = x01.shape[0], x01[0].numel()
-        R = B * K
-        x_n = normalize_to_neg_one_to_one(x01)
-        x_rows = self._engines()[0]._b("ens_xin", (R,) + tuple(x01.shape[1:]), torch.float32)
-        L.call("fd_rows_repeat_f32", _p(x_n), _p(x_rows), B, K, npix, _stream(x01))
-        cond = self._cond_repeated("ens", x_n, K, lambda u, e, x: e.encode_condition(x))
-        samples = torch.empty((B, K) + tuple(x01.shape[1:]), device=x01.device, dtype=torch.float32)
-        flat = samples.view((R,) + tuple(x01.shape[1:]))
-        # every plan's ancestral steps take the keyed stream of `sd` inside its captured loop: no step_noise callable
-        for lo, hi in ensemble_passes(B, K, self._group_rows()):
-            sl = slice(lo, hi)
-            size = (hi - lo,) + tuple(x01.shape[1:])
-            sd = seeds[sl].contiguous()
-            out = self._sample([x_rows[sl]], hi - lo, True, self._keyed_noise(sd, self.X_T_STEP, size), None, sd,
-                               cond=self._cond_rows(cond, sl))
-            flat[sl].copy_(out[-1])
-        return samples
-
-    def _sample_ensemble_tiled(self, x_input, K, slice_seeds, return_samples, tile, overlap, condition, fuse):
-        """sample_ensemble(tile=...): see its docstring"""
-        fn = "sample_ensemble"
-        if fuse not in ("final", "step"):
-            raise RuntimeError(f"{fn}: tile_fuse must be 'final' or 'step' (got {fuse!r})")
-        x01, (th, tw), (oy, ox) = self._tiled_args(fn, x_input, tile, overlap, condition)
-        B, _, H, W = x01.shape
-        x01 = x01.contiguous().float()
-        dev, s = x01.device, _stream(x01)
-        seeds = self._slice_seeds(slice_seeds, B, "cpu")
-        ys, xs, wy, wx, my, mx, x4 = self._tile_plan(H, W, th, tw, oy, ox, dev)
-        T = my * mx
-        if B * K * T > 65535:
-            raise RuntimeError(f"{fn}: {B} slices x {K} replicas x {my} x {mx} tiles are more than 65535 rows: sample fewer "
-                               "slices per call")
-        plan = (ys, xs, wy, wx, my, mx, x4, th, tw)
-        rseeds = torch.from_numpy(ensemble_seeds(seeds.numpy(), K).reshape(-1)).to(dev)                    # (B K,): a replica's
-        rows = torch.from_numpy(tiled_ensemble_seeds(seeds.numpy(), K, T).reshape(-1)).to(dev)              # (B K T,): a tile row's
-        field = self._keyed_noise(rseeds, self.X_T_STEP, (B * K, 1, H, W))
-
-        def replica_rows():
-            x_n = normalize_to_neg_one_to_one(x01)
-            x_in = self._tile_gather(x_n, plan)
-            return self._rows_per_replica(x_in, self._tile_cond_rows(x_n, x_in, plan, condition), B, K)
-        if fuse == "step":
-            def fused():
-                x_rows, cond = replica_rows()
-                img = self._x_T_into(x_rows, self._tile_gather(field, plan), torch.empty_like(x_rows))
-                return self._tiled_fused_loop(x_rows, img, cond, rseeds, plan, (B * K, H, W))
-            samples = self._range_checked(fused, "a sampled image").view(B, K, 1, H, W)
-            mean, std, spread = ensemble_stats(samples)
-            return EnsembleResult(mean, std, spread, samples if return_samples else None)
-
-        def final_tiles():
-            x_rows, cond = replica_rows()
-            nz_rows = self._tile_gather(field, plan)
-            tiles = torch.empty((B * K * T, 1, th, tw), device=dev, dtype=torch.float32)
-            for lo, hi in tile_passes(B * K, my, mx, self._group_rows(), self.streams):
-                sl = slice(lo, hi)
-                out = self._sample([x_rows[sl]], hi - lo, True, nz_rows[sl], None, rows[sl].contiguous(),
-                                   cond=self._cond_rows(cond, sl))
-                tiles[sl].copy_(out[-1])
-            return tiles
-        tiles = self._range_checked(final_tiles, "a sampled image (a tile row of a replica)")
-        nblk = L.lib().fd_ensemble_nblk(H * W)
-        mean, std = torch.empty_like(x01), torch.empty_like(x01)
-        ws, spread = torch.empty(B * nblk, device=dev), torch.empty(B, device=dev)
-        samples = torch.empty((B, K, 1, H, W), device=dev, dtype=torch.float32) if return_samples else None
-        L.call("fd_tiles_ensemble_f32", _p(tiles), _p(wy), _p(wx), _p(ys), _p(xs), None if samples is None else _p(samples),
-               _p(mean), _p(std), _p(ws), _p(spread), B, K, H, W, th, tw, my, mx, x4, s)
-        return EnsembleResult(mean, std, spread, samples)
-
-    # ---- a slice as overlapping tiles
-    def _tile_plan(self, H, W, th, tw, oy, ox, dev):
-        """The plan of tiling.py on the device, uploaded once per geometry: (ys, xs int32, wy, wx float32, my, mx, xs % 4 == 0)"""
-        cache = self.__dict__.setdefault("_tile_plans", {})
-        key = (H, W, th, tw, oy, ox, str(dev))
-        plan = cache.get(key)
-        if plan is None:
-            ys, xs = tile_plan(H, th, oy), tile_plan(W, tw, ox)
-            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a.astype(dt))).to(dev)
-            plan = cache[key] = (up(ys, np.int32), up(xs, np.int32), up(tile_weights(ys, H, th), np.float32),
-                                 up(tile_weights(xs, W, tw), np.float32), len(ys), len(xs), int(bool((xs % 4 == 0).all())))
-        return plan
-
-    def _tiled_args(self, fn, x_input, tile, overlap, condition):
-        """The argument checks of a tiled call `fn`: (x01 as given, (th, tw), (oy, ox))"""
-        if self.input_condition:
-            raise RuntimeError(f"{fn}: input_condition=True is not built (one input plane per slice)")
-        if condition not in ("tile", "slice"):
-            raise RuntimeError(f"{fn}: condition must be 'tile' or 'slice' (got {condition!r})")
-        (th, tw), (oy, ox) = tile_pair(fn, tile, "tile"), tile_pair(fn, overlap, "overlap")
-        x01 = list(x_input)[0]
-        if not torch.is_tensor(x01) or x01.dim() != 4 or x01.shape[1] != 1:
-            raise RuntimeError(f"{fn}: x_input must be [ldct (B,1,H,W)]")
-        B, _, H, W = x01.shape
-        div = 2 ** (len(self.model.unet0.dim_mults) - 1)
-        if th < 1 or tw < 1 or th % div or tw % div:
-            raise RuntimeError(f"{fn}: tile {th} x {tw} must be positive multiples of {div} (the U-Net has "
-                               f"{len(self.model.unet0.dim_mults)} levels)")
-        if th > H or tw > W:
-            raise RuntimeError(f"{fn}: tile {th} x {tw} is larger than the slice {H} x {W} (padded tiles are not built)")
-        if not (0 <= oy <= th // 2 and 0 <= ox <= tw // 2):
-            raise RuntimeError(f"{fn}: overlap {oy} x {ox} must lie in [0, tile // 2] = [0, {th // 2}] x [0, {tw // 2}]")
-        return x01, (th, tw), (oy, ox)
-
-    @torch.no_grad()
-    @_fuse_keyword
-    def sample_tiled(self, x_input, tile, overlap=0, slice_seeds=None, condition="tile"):
-        """x_input = [ldct (B,1,H,W) in [0,1]] sampled as overlapping tiles of `tile` = th or (th, tw) pixels, `overlap` (an int or
-        a pair, at most tile // 2) pixels apart from full tiles (tiling.tile_plan: the last tile of an axis is shifted back to end
-        at the border), and blended on the device: what sample(last=True) returns, [x_T image, final image], both (B,1,H,W).  A
-        model trained on crops meets the operator it was trained under, an image larger than a checkpoint's size can be denoised,
-        and the engines' workspaces are those of a tile.
-        x_T is ONE keyed field per slice, fd_keyed_normal(slice seed, X_T_STEP) over the whole plane, and a tile's x_T noise is
-        its window of that field: overlapping tiles start from the same noise in their common pixels, on both samplers.  The first
-        returned image is x_input + sqrt(sum_scale) * field on the whole slice.  Tile (iy, ix) of slice b is an ordinary row of
-        sample() under the seed tiling.tile_seeds(slice_seeds, my * mx)[b, iy * mx + ix] (tile 0 keeps the slice's seed: a one-tile
-        plan is sample() of the slice under that x_T); the rows run slice-major in passes of at most streams x max_sub_batch
-        through the paths of sample().  The ancestral sampler's STEP noise is the keyed stream of the tile's own seed (the
-        graph-captured loop of every plan, the two-U-Net and pred_noise models included), so overlapping tiles see different step
-        noise in their common pixels and the blend averages them.
-        The final image is the weighted mean of the tiles' final images, weights tiling.tile_weights (fd_tiles_blend_f32): a
-        pixel under one tile is that tile's value bit for bit.  Nothing returned depends on B or on the cut into passes.
-        condition="tile": the DA-CLIP tower runs on every tile, which is what crop training saw.  "slice": it runs once per slice
-        on the whole slice (Unet.tower_engine) and every tile of the slice takes those conditioning rows.
-        `fuse` is a further, keyword-only argument (taken by _fuse_keyword in front of this method; an unknown value raises).
-        fuse="final" (the default) is all of the above: every tile runs its own trajectory and the final images are blended once.
-        fuse="step" fuses the tiles at EVERY step instead: the slice has one state x_t, held as tile rows that agree bit for bit
-        in the common pixels of overlapping tiles.  Per step the forwards of all tile rows run into output buffers, in equal
-        sub-batches of at most max_sub_batch rows per engine (half of it for a two-U-Net plan), each under its own conditioning
-        rows (computed once before the loop, for both values of `condition`), and ONE launch of fd_tiles_step_ddim_f32 /
-        fd_tiles_step_keyed_f32 blends the tiles' raw outputs per pixel (the weights and arithmetic of fd_tiles_blend_f32) and
-        applies the scheduler update to every row in place; the ancestral step noise is the keyed stream of the SLICE seed at the
-        slice pixel, the same for every covering tile (tile_seeds are not used).  It is one trajectory of the whole slice under a
-        windowed model: the final image is assembled from the rows on the last step, every pixel being every covering tile's
-        value, so there is no seam and no mean of different denoisings or noise realisations.  A one-tile plan is sample() of the
-        two-U-Net and pred_noise plans bit for bit; the first returned image is that of fuse="final".  Every plan of _plan()
-        runs, the shipped one as mode 0, on both samplers (_anc_max_chunks bounds the ancestral one as in _obj_ancestral), on one
-        stream with slot 0's engines, eagerly: no captured graph, no second stream, and no precision tail for any plan -- a bf16
-        fused run of the shipped plan does not get final_fp32_steps.  Nothing returned depends on B or on max_sub_batch.
-        Ensembles of tiled samples are sample_ensemble(tile=...).  Not built: tiles larger than the slice (padded tiles),
-        last=False, input_condition=True; for fuse="step" also a captured graph or a second stream, a precision tail, and
-        per-tile seeds."""
-        fn = "sample_tiled"
-        # (unbound: the host-side checks run on any object that has input_condition, tests/test_tiled_fused_cpu.py)
-        x01, (th, tw), (oy, ox) = ResidualDiffusion._tiled_args(self, fn, x_input, tile, overlap, condition)
-        B, _, H, W = x01.shape
-        x01 = x01.contiguous().float()
-        seeds = self._slice_seeds(slice_seeds, B, "cpu")
-        ys, xs, wy, wx, my, mx, x4 = self._tile_plan(H, W, th, tw, oy, ox, x01.device)
-        if B * my * mx > 65535:
-            raise RuntimeError(f"{fn}: {B} slices x {my} x {mx} tiles are more than 65535 rows: sample fewer slices per call")
-        rows = torch.from_numpy(tile_seeds(seeds.numpy(), my * mx).reshape(-1)).to(x01.device)
-        plan = (ys, xs, wy, wx, my, mx, x4, th, tw)
-        s = _stream(x01)
-        field = self._keyed_noise(seeds.to(x01.device), self.X_T_STEP, tuple(x01.shape))
-        x_T = self._x_T_into(normalize_to_neg_one_to_one(x01), field, torch.empty_like(x01))
-        if self._tile_fuse == "step":
-            def fused():
-                x_n = normalize_to_neg_one_to_one(x01)
-                x_in = self._tile_gather(x_n, plan)
-                img = self._x_T_into(x_in, self._tile_gather(field, plan), torch.empty_like(x_in))
-                cond = self._tile_cond_rows(x_n, x_in, plan, condition)
-                return self._tiled_fused_loop(x_in, img, cond, seeds.to(x01.device), plan, (B, H, W))
-            return [unnormalize_to_zero_to_one(x_T), self._range_checked(fused, "a sampled image")]
-        tiles = self._range_checked(lambda: self._tile_rows(x01, field, rows, plan, condition), "a sampled image")
-        out = torch.empty_like(x01)
-        L.call("fd_tiles_blend_f32", _p(tiles), _p(wy), _p(wx), _p(ys), _p(xs), _p(out), B, H, W, th, tw, my, mx, x4, s)
-        return [unnormalize_to_zero_to_one(x_T), out]
-
-    def _tile_gather(self, src, plan):
-        ys, xs, _, _, my, mx, x4, th, tw = plan
-        B, _, H, W = src.shape
-        dst = torch.empty((B * my * mx, 1, th, tw), device=src.device, dtype=torch.float32)
-        L.call("fd_tiles_gather_f32", _p(src), _p(dst), _p(ys), _p(xs), B, H, W, th, tw, my, mx, x4, _stream(src))
-        return dst
-
-    def _cond_buffers(self, prefix, R):
-        """One (prompt_emb, local_all) pair of R conditioning rows per engine of _engines(), in buffers `prefix`_prompt /
-        `prefix`_local of the engine whose rows they are (_encode_all and _cond_rows take the list)."""
-        return [(e._b(prefix + "_prompt", (R, e.time_dim), torch.float32), e._b(prefix + "_local", (R, e.loc_total), torch.float32))
-                for e in self._engines()]
-
-    def _cond_repeated(self, prefix, x_n, n, encode):
-        """_cond_buffers of the B n rows in which every slice of x_n (in [-1, 1]) stands n times: encode(unet, engine, slices)
-        leaves the slices' conditioning in the engine, at most max_sub_batch slices at a time (the tower's workspace grows with its
-        batch), on every engine in use, and a slice's rows are repeated for its n rows (replicas, tiles)."""
-        B, s = x_n.shape[0], _stream(x_n)
-        cond = self._cond_buffers(prefix, B * n)
-        for c0 in range(0, B, self.max_sub_batch):
-            nb = min(self.max_sub_batch, B - c0)
-            for u, e, (pe, la) in zip(self._plan_unets(), self._engines(), cond):
-                encode(u, e, x_n[c0:c0 + nb])
-                L.call("fd_rows_repeat_f32", _p(e.prompt_emb), _p(pe[c0 * n:]), nb, n, e.time_dim, s)
-                L.call("fd_rows_repeat_f32", _p(e.local_all), _p(la[c0 * n:]), nb, n, e.loc_total, s)
-        return cond
-
-    def _tile_cond_slice(self, x_n, T):
-        """condition="slice": the conditioning rows of the B x T tile rows of the slices x_n.  The tower runs once per slice on
-        the whole slice, on a tower-only engine per U-Net in use; the engine of the tiles turns its outputs into conditioning rows."""
-        return self._cond_repeated("til", x_n, T, lambda u, e, x: e.condition_from(*u.tower_engine(e.mode).encode_dose(x)))
-
-    def _fused_passes(self, B, my, mx):
-        """The sub-batches of the B my mx tile rows that one engine takes at a time outside _sample: at most max_sub_batch rows,
-        half of it for a two-U-Net plan."""
-        _, r0, r1, _ = self._plan()
-        return tile_passes(B, my, mx, max(1, self.max_sub_batch // 2 if (r0 and r1) else self.max_sub_batch))
-
-    def _tile_cond_rows(self, x_n, x_in, plan, condition):
-        """The conditioning rows of the B my mx tile rows x_in (R,1,th,tw) gathered from the slices x_n (both in [-1, 1]), one
-        (prompt_emb, local_all) pair per engine of _engines().  The tower runs once: on every tile (condition "tile", a
-        sub-batch of _fused_passes at a time), or on the whole slices."""
-        my, mx = plan[4], plan[5]
-        B = x_n.shape[0]
-        if condition == "slice":
-            return self._tile_cond_slice(x_n, my * mx)
-        cond = self._cond_buffers("til", B * my * mx)
-        for lo, hi in self._fused_passes(B, my, mx):
-            for e, (pe, la) in zip(self._engines(), cond):
-                e.encode_condition(x_in[lo:hi])
-                pe[lo:hi].copy_(e.prompt_emb)
-                la[lo:hi].copy_(e.local_all)
-        return cond
-
-    def _rows_per_replica(self, x_in, cond, B, K):
-        """The input tiles and conditioning rows (_tile_cond_rows) of B slices, a slice's T rows repeated for its K replicas:
-        row (b K + k) T + j = row b T + j (fd_rows_repeat_f32 with a row length of T times a row's)."""
-        s = _stream(x_in)
-        x_rows = torch.empty((x_in.shape[0] * K,) + tuple(x_in.shape[1:]), device=x_in.device, dtype=torch.float32)
-        L.call("fd_rows_repeat_f32", _p(x_in), _p(x_rows), B, K, x_in.numel() // B, s)
-        rows = self._cond_buffers("tens", x_in.shape[0] * K)
-        for src, dst in zip(cond, rows):
-            for a, b in zip(src, dst):
-                L.call("fd_rows_repeat_f32", _p(a), _p(b), B, K, a.numel() // B, s)
-        return x_rows, rows
-
-    def _tiled_fused_loop(self, x_in, img, cond, seeds, plan, shape):
-        """One trajectory of B slices of H x W, shape = (B, H, W), as R = B my mx tile rows (sample_tiled's docstring), given the
-        rows' input tiles x_in, their x_T img (updated in place), their conditioning rows cond (_tile_cond_rows) and one seed
-        per slice: sample_tiled hands in its slices' rows, sample_ensemble those of its B K replicas.  Per step: [fd_obj_begin
-        on the ancestral sampler,] per U-Net of the plan and per sub-batch load_condition + forward into the rows of o0 / o1,
-        then one fd_tiles_step_* launch over all R rows in place on img, which also writes the slice image on the last step."""
-        ys, xs, wy, wx, my, mx, x4, th, tw = plan
-        B, H, W = shape
-        dev, s = x_in.device, _stream(x_in)
-        mode = self._plan()[0]
-        engines = self._engines()
-        passes = self._fused_passes(B, my, mx)
-        nmax = max(hi - lo for lo, hi in passes)
-        outs = [torch.empty_like(x_in) for _ in engines]
-        o0, o1 = self._o01(outs)
-        final = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
-        geom = (_p(wy), _p(wx), _p(ys), _p(xs), B, H, W, th, tw, my, mx, x4)
-
-        def forwards(times):
-            for e, o, tb, c in zip(engines, outs, times, cond):
-                for lo, hi in passes:
-                    e.load_condition(c[0][lo:hi], c[1][lo:hi])
-                    e.forward(img[lo:hi], x_in[lo:hi], tb[:hi - lo], out=o[lo:hi])
-
-        if self.is_ddim_sampling:
-            S = self.sampling_timesteps
-            par, tt0, tt1 = self._obj_ddim_table(nmax)
-            gpar = par[:, 0].contiguous().to(dev)                  # (S, 8): all rows of a step share the parameters
-            gts = [tt.to(dev) for tt in (tt0, tt1) if tt is not None]
-            for i in range(S):
-                forwards([gt[i] for gt in gts])
-                L.call("fd_tiles_step_ddim_f32", mode, _p(o0), _p(o1), _p(img), _p(x_in), _p(gpar[i]), *geom, _p(img),
-                       _p(final) if i == S - 1 else None, s)
-        else:
-            T = self.num_timesteps
-            t_dev = torch.full((1,), T, device=dev, dtype=torch.int32)
-            gpar = self._obj_anc_table().to(dev)
-            tabs = [None if tt is None else tt.to(dev) for tt in self._obj_time_tables()]
-            bufs = [None if tt is None else torch.zeros(nmax, device=dev, dtype=torch.float32) for tt in tabs]
-            G, reps, rem = self._anc_chunks(T)                     # _obj_ancestral's steps under _anc_max_chunks
-            steps = rem + reps * G
-            for i in range(steps):
-                L.call("fd_obj_begin", _p(t_dev), _p(tabs[0]), _p(tabs[1]), _p(bufs[0]), _p(bufs[1]), nmax, T, s)
-                forwards([b for b in bufs if b is not None])
-                L.call("fd_tiles_step_keyed_f32", mode, _p(o0), _p(o1), _p(img), _p(x_in), _p(gpar), _p(t_dev), _p(seeds), *geom,
-                       _p(img), _p(final) if i == steps - 1 else None, T, s)
-            self._anc_steps_run = steps
-        return unnormalize_to_zero_to_one(final)
-
-    def _tile_rows(self, x01, field, seeds, plan, condition):
-        """The B my mx final tile images (R,1,th,tw) of sample_tiled, in [0, 1] units; seeds (R,) int64 on the device."""
-        my, mx, th, tw = plan[4], plan[5], plan[7], plan[8]
-        B, T = x01.shape[0], my * mx
-        R = B * T
-        nz_rows = self._tile_gather(field, plan)
-        cond = None
-        if condition == "slice":
-            x_n = normalize_to_neg_one_to_one(x01)                 # the rows of a preset are already in [-1, 1] (_sample)
-            x_rows = self._tile_gather(x_n, plan)
-            cond = self._tile_cond_slice(x_n, T)
-        else:
-            x_rows = self._tile_gather(x01, plan)                  # plain rows of _sample, which normalises them itself
-        tiles = torch.empty((R, 1, th, tw), device=x01.device, dtype=torch.float32)
-        for lo, hi in tile_passes(B, my, mx, self._group_rows(), self.streams):
-            sl = slice(lo, hi)
-            sd = seeds[sl].contiguous()
-            pre = {} if cond is None else {"cond": self._cond_rows(cond, sl)}
-            out = self._sample([x_rows[sl]], hi - lo, True, nz_rows[sl], None, sd, **pre)
-            tiles[sl].copy_(out[-1])
-        return tiles
-
     def _sample(self, x_input, batch_size, last, noise, step_noise, slice_seeds, cond=None):
         """`cond`: the preset conditioning of sample_ensemble (_encode_all), whose x_input is already in [-1, 1]; it is sliced the
         way `noise` is and no tower runs."""
@@ -2355,17 +1985,14 @@ class Trainer(object):
             raise RuntimeError(f"Trainer.test: quantiles and estimate='median' need an ensemble, n_samples > 1 (got {n_samples})")
         qplan = None
         if quantiles is not None or estimate == "median":
-            # (levels handed to sample_ensemble, how many of them are the caller's, the estimate's index or None)
             levels = tuple(float(q) for q in (() if quantiles is None else quantiles))
             n_user = len(levels)
             if estimate == "median" and 0.5 not in levels:
                 levels = levels + (0.5,)
             quantile_table(levels, int(n_samples))
             quantile_suffix(levels[:n_user])
-            qplan = (levels, n_user, levels.index(0.5) if estimate == "median" else None)
-        if tile is not None and int(n_samples) > 1 and not tiled_ensemble:
-            raise RuntimeError(f"Trainer.test: tile={tile!r} with n_samples={n_samples}: ensembles of tiled samples are opt-in: "
-                               "pass tiled_ensemble=True (DESIGN.md section 8)")
+            qplan = _QuantilePlan(levels, levels[:n_user], levels.index(0.5) if estimate == "median" else None)
+        tiled_ensemble_opt_in("Trainer.test", tile, n_samples, tiled_ensemble)
         if tile is not None and not last:
             raise RuntimeError("Trainer.test: tile with last=False is not built (sample_tiled returns the final image)")
         # batch_size 1 is the reference's loop: one slice per sample() call -> the kernel set for a lone slice (DAEngine
@@ -2381,14 +2008,14 @@ class Trainer(object):
             if batch_size == 1 and int(n_samples) == 1 and tile is None:      # (an ensemble is a batch of replicas, a tiled slice
                 for u in unets:                                           # a batch of tiles: the default kernel set)
                     u.low_latency = True
-            tiled = None if tile is None else (tile, overlap, tile_condition, tile_fuse)
+            tiled = None if tile is None else dict(tile=tile, overlap=overlap, tile_condition=tile_condition, tile_fuse=tile_fuse)
             return self._test(sample, last, FID, batch_size, int(n_samples), int(ensemble_seed), tiled, qplan)
         finally:
             for u, v in zip(unets, saved):
                 u.low_latency = v
 
     def _test(self, sample, last, FID, batch_size, n_samples=1, ensemble_seed=0, tiled=None, qplan=None):
-        """`qplan`: None, or test()'s (levels, how many of them are the caller's, the index of the estimate's level or None)"""
+        """`tiled`: None, or the keyword arguments of sample_ensemble that make it tiled; `qplan`: None, or test()'s _QuantilePlan"""
         from .metrics import compute_metrics
         model = self.ema.ema_model                   # inference uses the EMA weights (src/DADiff.py:1818-1822)
         model.init()
@@ -2412,10 +2039,10 @@ class Trainer(object):
         q_names, q_cover = [], None
         if qplan is not None:
             self.test_running_coverage = []
-            q_names = quantile_suffix(qplan[0][:qplan[1]])
-            if qplan[1] >= 2:                                  # the interval [lowest level, highest level] of the caller's levels
-                user = list(qplan[0][:qplan[1]])
-                q_cover = (user.index(min(user)), user.index(max(user)))
+            q_names = quantile_suffix(qplan.user)
+            if len(qplan.user) >= 2:                           # the interval [lowest level, highest level] of the caller's levels
+                q_cover = (qplan.user.index(min(qplan.user)), qplan.user.index(max(qplan.user)))
+        ens_kw = dict(tiled or {}, **({} if qplan is None else {"quantiles": qplan.levels}))
         ds = self.sample_dataset
         for s in range(0, len(ds), batch_size):
             idx = list(range(s, min(s + batch_size, len(ds))))
@@ -2424,20 +2051,17 @@ class Trainer(object):
             xs = [torch.stack([it[k] for it in items]).to(self.device) for k in range(1, len(items[0]))]
             y_std = y_q = cover = None
             if n_samples > 1:
-                tkw = {} if tiled is None else dict(tile=tiled[0], overlap=tiled[1], tile_condition=tiled[2], tile_fuse=tiled[3])
-                if qplan is not None:
-                    tkw["quantiles"] = qplan[0]
-                ens = model.sample_ensemble(xs, n_samples, slice_seeds=[ensemble_seed + i for i in idx], **tkw)
+                ens = model.sample_ensemble(xs, n_samples, slice_seeds=[ensemble_seed + i for i in idx], **ens_kw)
                 y_pred, y_std = ens.mean, ens.std
                 if qplan is not None:
                     y_q = ens.quantiles
-                    if qplan[2] is not None:                   # estimate="median": the 0.5 level is scored and saved
-                        y_pred = y_q[:, qplan[2]]
+                    if qplan.estimate is not None:             # estimate="median": the 0.5 level is scored and saved
+                        y_pred = y_q[:, qplan.estimate]
                     if q_cover is not None and not sample:
                         cover = interval_coverage(y_q[:, q_cover[0]], y_q[:, q_cover[1]], y)[1]
             elif tiled is not None:
-                outs = model.sample_tiled(xs, tiled[0], tiled[1], slice_seeds=[ensemble_seed + i for i in idx], condition=tiled[2],
-                                          fuse=tiled[3])
+                outs = model.sample_tiled(xs, tiled["tile"], tiled["overlap"], slice_seeds=[ensemble_seed + i for i in idx],
+                                          condition=tiled["tile_condition"], fuse=tiled["tile_fuse"])
                 all_images_list = [y] + xs + list(outs)
                 y_pred = outs[-1]
             elif sample:
@@ -2485,8 +2109,8 @@ class Trainer(object):
             np.mean(self.test_running_psnr), np.mean(self.test_running_ssim), np.mean(self.test_running_rmse)))
         if q_cover is not None:
             self.train_logger.info("test_coverage: {:.4f} of the NDCT pixels inside [q{:g}, q{:g}] (nominal {:.4f})".format(
-                np.mean(self.test_running_coverage), qplan[0][q_cover[0]], qplan[0][q_cover[1]],
-                qplan[0][q_cover[1]] - qplan[0][q_cover[0]]))
+                np.mean(self.test_running_coverage), qplan.user[q_cover[0]], qplan.user[q_cover[1]],
+                qplan.user[q_cover[1]] - qplan.user[q_cover[0]]))
         print("test end")
         return float(np.mean(self.test_running_psnr)), float(np.mean(self.test_running_ssim)), \
             float(np.mean(self.test_running_rmse))

@@ -10,6 +10,8 @@ rank 0's model at set-up and the replicas' fingerprints.
 """
 import torch
 
+from .tiling import tiled_ensemble_opt_in
+
 
 def shard_range(n, world, rank):
     """Contiguous block split of range(n): rank r gets [lo, hi); ragged tails go to the last ranks."""
@@ -65,9 +67,7 @@ def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampl
     n = ldct.shape[0]
     lo, hi = shard_range(n, world, rank)
     dev = next(diffusion.parameters()).device
-    if tile is not None and int(n_samples) > 1 and not tiled_ensemble:
-        raise RuntimeError(f"sample_volume: tile={tile!r} with n_samples={n_samples}: ensembles of tiled samples are opt-in: pass "
-                           "tiled_ensemble=True (DESIGN.md section 8)")
+    tiled_ensemble_opt_in("sample_volume", tile, n_samples, tiled_ensemble)
     if tile is not None and int(n_samples) <= 1:
         outs = [diffusion.sample_tiled([ldct[s:min(s + batch, hi)].to(dev)], tile, overlap,
                                        slice_seeds=torch.arange(s, min(s + batch, hi), dtype=torch.int64) + int(noise_seed),

@@ -99,6 +99,14 @@ def tiled_ensemble_seeds(slice_seeds, K, n_tiles):
     return tile_seeds(ensemble_seeds(seeds, K).reshape(-1), n_tiles).reshape(len(seeds), K, n_tiles)
 
 
+def tiled_ensemble_opt_in(fn, tile, n_samples, tiled_ensemble):
+    """The callers of the samplers (`fn`: Trainer.test, sample_volume) run an ensemble of tiled samples only on request: `tile`
+    with n_samples > 1 raises without `tiled_ensemble` (the raising default is pinned by tests)."""
+    if tile is not None and int(n_samples) > 1 and not tiled_ensemble:
+        raise RuntimeError(f"{fn}: tile={tile!r} with n_samples={n_samples}: ensembles of tiled samples are opt-in: pass "
+                           "tiled_ensemble=True (DESIGN.md section 8)")
+
+
 def tile_passes(B, my, mx, rows_max, multiple=1):
     """The B * my * mx tile rows (slice-major: row (b * my + iy) * mx + ix) as consecutive passes [(lo, hi), ...] of at most
     `rows_max` rows; every row once.  ensemble_passes, asked for the fewest passes that `rows_max` allows and then for passes of

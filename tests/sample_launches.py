@@ -19,6 +19,11 @@ Four cases were recorded again with that gathering, and nothing else in them cha
 no-graph", "anc keyed T=84 no-graph max-chunks" and "generic anc rn_res trajectory" are the eager form of the shipped ancestral
 loop (use_graph off, or last=False), which now runs under the driver of every ancestral loop: it writes _anc_steps_run, and it
 honours _anc_max_chunks, which it used to ignore (the third case: 40 main steps, the jump, the tail step, instead of all 84).
+
+The cases of sample_ensemble(tile=...) and of quantiles= ("ensemble tiled ...", "ensemble quantiles ...", "fallback ensemble tiled
+...") were recorded later, on the commit "Add ensemble quantiles: per-pixel order statistics and coverage", before the tiled and
+ensemble paths moved into founddiff_amd/tiled_sampling.py; no older case was recorded again.  The stubs go into every module of
+MODULES that imports, so this file also records on a tree from before that module.
 """
 import json
 import os
@@ -33,6 +38,14 @@ if ROOT not in sys.path:
 
 from founddiff_amd import DADiff                                       # noqa: E402
 
+MODULES = [DADiff]                                                     # the modules whose _p, _stream and metrics are stubbed
+try:
+    from founddiff_amd import tiled_sampling                           # noqa: E402
+    MODULES.append(tiled_sampling)
+except ImportError:                                                    # (a tree from before the module: DADiff holds it all)
+    pass
+STUBBED = ("_p", "_stream", "ensemble_stats", "ensemble_quantiles")
+
 GOLDEN = os.path.join(ROOT, "tests", "golden", "sample_launches.json")
 HW = 8
 TINY_CLIP = dict(layers=(2, 1, 1, 1), width=16, embed_dim=1024)
@@ -46,7 +59,8 @@ ENV = ("FOUNDDIFF_LOOP_GRAPH", "FOUNDDIFF_TAIL_EXACT")                 # read at
 def _case(path, plan="shipped", **kw):
     """S: sampling_timesteps (a DDIM case keeps the 1000-step schedule), T: the ancestral schedule cut to T steps.  The other keys
     are attributes set on the sampler (use_graph, final_fp32_steps, final_outer_levels, _time_table, _anc_max_chunks,
-    max_sub_batch) or arguments of the call (last, noise, seeds, step_noise, K, fuse, condition, fail)."""
+    max_sub_batch) or arguments of the call (last, noise, seeds, step_noise, K, fuse, condition, fail; of the "ensemble" path also
+    tile -- with fuse and condition as tile_fuse and tile_condition, overlap 2 --, return_samples and quantiles)."""
     c = dict(path=path, plan=plan)
     c.update(kw)
     return c
@@ -118,6 +132,27 @@ def _cases():
         add(f"fallback tiled step {prec}", "tiled", S=3, fuse="step", condition="tile", max_sub_batch=4, precision=prec, fail=1)
     add("fp16 sample in range", "sample", S=3, precision="fp16")
     add("fallback sample anc auto", "sample", "res_noise", T=9, precision="auto", fail=1)
+    # ---- tiled ensembles: the tiles above, K = 2 replicas per slice: 16 rows, final in passes of 4 (2 for two U-Nets)
+    tens = dict(K=2, tile=6, max_sub_batch=4)
+    for fuse in ("final", "step"):
+        for cond in ("tile", "slice"):
+            add(f"ensemble tiled {fuse} {cond} ddim", "ensemble", S=3, fuse=fuse, condition=cond, **tens)
+            add(f"ensemble tiled {fuse} {cond} anc", "ensemble", T=9, fuse=fuse, condition=cond, **tens)
+            add(f"ensemble tiled {fuse} {cond} ddim res_noise", "ensemble", "res_noise", S=3, fuse=fuse, condition=cond, **tens)
+            add(f"ensemble tiled {fuse} {cond} anc res_noise", "ensemble", "res_noise", T=9, fuse=fuse, condition=cond, **tens)
+    add("ensemble tiled final tile ddim no-samples", "ensemble", S=3, fuse="final", condition="tile", return_samples=0, **tens)
+    add("ensemble tiled step slice ddim msb=1", "ensemble", S=3, K=2, tile=6, fuse="step", condition="slice", max_sub_batch=1)
+    add("ensemble tiled step tile anc pred_noise T=83 max-chunks", "ensemble", "pred_noise", T=83, fuse="step", condition="tile",
+        _anc_max_chunks=1, **tens)
+    # ---- quantiles: the order kernel after the K = 3 images, which the tile_fuse="final" path then writes
+    qs = (0.05, 0.5, 0.95)
+    add("ensemble quantiles ddim msb=4", "ensemble", S=3, K=3, max_sub_batch=4, quantiles=qs, return_samples=0)
+    add("ensemble quantiles tiled final", "ensemble", S=3, K=3, tile=6, fuse="final", condition="tile", max_sub_batch=4, quantiles=qs,
+        return_samples=0)
+    add("ensemble quantiles tiled step", "ensemble", S=3, K=3, tile=6, fuse="step", condition="tile", max_sub_batch=4, quantiles=qs)
+    for prec in ("fp16", "auto"):
+        for fuse in ("final", "step"):
+            add(f"fallback ensemble tiled {fuse} {prec}", "ensemble", S=3, fuse=fuse, condition="tile", precision=prec, fail=1, **tens)
     return out
 
 
@@ -281,6 +316,10 @@ class Recorder:
         B, sh = samples.shape[0], tuple(samples.shape[2:])
         return torch.zeros((B,) + sh), torch.zeros((B,) + sh), torch.zeros(B)
 
+    def _quantiles(self, samples, levels):
+        self.row("ensemble_quantiles", list(samples.shape), list(levels))
+        return torch.zeros((samples.shape[0], len(levels)) + tuple(samples.shape[2:]))
+
     def _dif(self, c):
         nu, obj, tst = PLANS[c["plan"]]
         prec = c.get("precision", "bf16")
@@ -314,10 +353,13 @@ class Recorder:
         noise = self.named(torch.zeros(shape), "arg:noise") if c.get("noise") else None
         seeds = torch.tensor([11, 12], dtype=torch.int64) if c.get("seeds") else None
         step_noise = (lambda t: self.named(torch.zeros(shape), f"arg:step_noise({t})")) if c.get("step_noise") else None
-        saved = (DADiff.L.call, DADiff._p, DADiff._stream, DADiff.ensemble_stats, DADiff.Unet.engine, DADiff.Unet.tower_engine,
-                 torch.isfinite)
+        saved = (DADiff.L.call, DADiff.Unet.engine, DADiff.Unet.tower_engine, torch.isfinite)
+        stubs = dict(zip(STUBBED, (self.p, (lambda t: "s"), self._stats, self._quantiles)))
+        saved_stubs = [(m, k, getattr(m, k)) for m in MODULES for k in STUBBED if hasattr(m, k)]
         env = {k: os.environ.pop(k) for k in ENV if k in os.environ}
-        DADiff.L.call, DADiff._p, DADiff._stream, DADiff.ensemble_stats = self._call, self.p, (lambda t: "s"), self._stats
+        DADiff.L.call = self._call
+        for m, k, _ in saved_stubs:
+            setattr(m, k, stubs[k])
         rec = self
         DADiff.Unet.engine = lambda u, precision=None, slot=0: rec._engine(u, precision, slot)
         DADiff.Unet.tower_engine = lambda u, precision=None: rec._engine(u, precision, "tower")
@@ -332,8 +374,14 @@ class Recorder:
                         out = dif.sample([x01], batch_size=B, last=bool(c.get("last", 1)), noise=noise, step_noise=step_noise,
                                          slice_seeds=seeds)
                     elif c["path"] == "ensemble":
-                        res = dif.sample_ensemble([x01], c["K"], slice_seeds=seeds, return_samples=True)
-                        out = [res.mean, res.std, res.spread, res.samples]
+                        kw = {}
+                        if "tile" in c:
+                            kw.update(tile=c["tile"], overlap=2, tile_condition=c["condition"], tile_fuse=c["fuse"])
+                        if "quantiles" in c:
+                            kw["quantiles"] = c["quantiles"]
+                        res = dif.sample_ensemble([x01], c["K"], slice_seeds=seeds, return_samples=bool(c.get("return_samples", 1)),
+                                                  **kw)
+                        out = list(res[:4]) + ([res.quantiles] if "quantiles" in c else [])
                     else:
                         out = dif.sample_tiled([x01], 6, 2, slice_seeds=seeds, condition=c["condition"], fuse=c["fuse"])
                 except DADiff.L.FoundDiffHipError as e:
@@ -341,11 +389,12 @@ class Recorder:
             for w in caught:
                 self.row("warns", str(w.message))
         finally:
-            (DADiff.L.call, DADiff._p, DADiff._stream, DADiff.ensemble_stats, DADiff.Unet.engine, DADiff.Unet.tower_engine,
-             torch.isfinite) = saved
+            DADiff.L.call, DADiff.Unet.engine, DADiff.Unet.tower_engine, torch.isfinite = saved
+            for m, k, v in saved_stubs:
+                setattr(m, k, v)
             os.environ.update(env)
         self.row("_auto_bf16", [bool(u._auto_bf16) for u in dif.model._unets()])
-        self.row("returns", None if out is None else [list(o.shape) for o in out])
+        self.row("returns", None if out is None else [None if o is None else list(o.shape) for o in out])
         counters = {f"{e.name}:{k[0]}": int(t) for e in self.engines.values() for k, t in e.buf.items() if k[0] in ("loop_t", "obj_t")}
         self.row("state", getattr(dif, "_anc_steps_run", None), counters, getattr(dif, "_tile_fuse", None))
         return fold(json.loads(json.dumps(self.rows)))
@@ -357,12 +406,12 @@ def snapshot():
 
 
 def write(path=GOLDEN, only=()):
-    """record every case, or only the named ones into the golden that is there"""
+    """record every case, or only the named ones (and those the golden lacks) into the golden that is there"""
     g = snapshot()
     if only:
         with open(path) as f:
             old = json.load(f)
-        g = {k: g[k] if k in only else old[k] for k in g}
+        g = {k: g[k] if k in only or k not in old else old[k] for k in g}
     with open(path, "w") as f:
         f.write("{\n" + ",\n".join(f' {json.dumps(k)}: {json.dumps(v, separators=(",", ":"))}' for k, v in g.items()) + "\n}\n")
     return g

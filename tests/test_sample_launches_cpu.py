@@ -88,8 +88,25 @@ def test_snapshot_covers_every_path(gold):
             for smp in ("ddim", "anc"):
                 assert ("encode_dose" in _names(gold[f"tiled {fuse} {cond} {smp}"])) == (cond == "slice")
                 assert ("fd_tiles_blend_f32" in _names(gold[f"tiled {fuse} {cond} {smp}"])) == (fuse == "final")
-    # the range check of the four entry points: 'fp16' raises, 'auto' warns, sets _auto_bf16 and runs again on the bf16 engines
-    for what in ("sample", "ensemble", "tiled final", "tiled step"):
+    # tiled ensembles: the tower never runs per replica; "final" reduces the tile rows in one launch, whose samples pointer is
+    # null unless the images are asked for (quantiles ask); "step" goes through ensemble_stats; the order kernel sees K images
+    for fuse in ("final", "step"):
+        for cond in ("tile", "slice"):
+            for smp in ("ddim", "anc", "ddim res_noise", "anc res_noise"):
+                rows = gold[f"ensemble tiled {fuse} {cond} {smp}"]
+                assert ("encode_dose" in _names(rows)) == (cond == "slice")
+                assert ("fd_tiles_ensemble_f32" in _names(rows)) == (fuse == "final") == ("ensemble_stats" not in _names(rows))
+                assert ("fd_tiles_step_ddim_f32" in _names(rows) or "fd_tiles_step_keyed_f32" in _names(rows)) == (fuse == "step")
+                assert "fd_tiles_blend_f32" not in _names(rows)
+    reduce_of = lambda k: next(r for r in _flat(gold[k]) if r[0] == "fd_tiles_ensemble_f32")
+    assert reduce_of("ensemble tiled final tile ddim no-samples")[6] is None
+    assert reduce_of("ensemble tiled final tile ddim")[6] is not None and reduce_of("ensemble quantiles tiled final")[6] is not None
+    assert ["returns", [[2, 1, 8, 8], [2, 1, 8, 8], [2], None]] in gold["ensemble tiled final tile ddim no-samples"]
+    for k in ("ensemble quantiles ddim msb=4", "ensemble quantiles tiled final", "ensemble quantiles tiled step"):
+        assert ["ensemble_quantiles", [2, 3, 1, 8, 8], [0.05, 0.5, 0.95]] in gold[k]
+    assert _state(gold["ensemble tiled step tile anc pred_noise T=83 max-chunks"])[1] == 40
+    # the range check of the entry points: 'fp16' raises, 'auto' warns, sets _auto_bf16 and runs again on the bf16 engines
+    for what in ("sample", "ensemble", "tiled final", "tiled step", "ensemble tiled final", "ensemble tiled step"):
         rows = gold[f"fallback {what} fp16"]
         assert "raises" in _names(rows) and ["returns", None] in rows and ["_auto_bf16", [False]] in rows
         rows = _flat(gold[f"fallback {what} auto"])
