@@ -9,14 +9,20 @@ reference (`/root/reference/src/DADiff.py`; contract in SURVEY.md section 8b), s
 through `founddiff_amd.engine.DAEngine`.  What the reference does not have -- `sample_ensemble`, `sample_tiled`, their results
 `EnsembleResult` / `EnsembleQuantiles` -- is `founddiff_amd/tiled_sampling.py`, a mixin of `ResidualDiffusion`.
 
+This file holds the parameter-only `Unet` / `UnetRes`, the `ResidualDiffusion` sampler and its training entry points (`forward`,
+`p_losses`, `eval_items`).  Three things it used to hold live beside it and are imported from here as before:
+`founddiff_amd/objectives.py` states the routing rule once -- which U-Net runs, at which time input, predicting what, per objective,
+`num_unet` and `test_res_or_noise` -- and `UnetRes.forward`, `ResidualDiffusion._plan` and `eval_items` read it;
+`founddiff_amd/trainer.py` is the `Trainer` with `_Accel` and `_EMAView`; `founddiff_amd/schedule.py` is `residual_schedule` and
+`load_weights`, which the sampler and the Trainer share.
+
 Training runs on the same classes: `Unet.trainable()` is a `unet_train.UnetTrunk` over the very
 parameters of the tree, `Unet.train_forward` runs the frozen DA-CLIP tower on the fp32 engine and the trunk under autograd on the HIP
 training kernels, `ResidualDiffusion.forward` / `p_losses` are the reference's (diffusion_train), and `Trainer.train / save / load`
-are its loop and checkpoint around `diffusion_train.ClipAdamEMA`.  Two U-Nets, which the reference optimises with RAdam, train
+(trainer.py) are its loop and checkpoint around `diffusion_train.ClipAdamEMA`.  Two U-Nets, which the reference optimises with RAdam, train
 around `diffusion_train.ClipRAdamEMA` on request: `UnetRes.trainable()` and `Trainer(optimizer="radam")`; the defaults raise.
 """
 import copy
-import ctypes as C
 import math
 import os
 import random
@@ -29,16 +35,13 @@ from torch import nn
 from . import _lib as L
 from . import arch
 from . import diffusion_train as dt
+from . import objectives
 from .engine import DAEngine, _p
-from .ensemble import quantile_suffix, quantile_table
-from .metrics import interval_coverage
+from .schedule import load_weights, residual_schedule  # noqa: F401 (load_weights is imported from here)
 from .tiled_sampling import EnsembleQuantiles, EnsembleResult, TiledSampling  # noqa: F401 (the results are imported from here)
-from .tiling import tiled_ensemble_opt_in
+from .trainer import Trainer, _Accel, _EMAView, _QuantilePlan  # noqa: F401 (the reference's names: they are imported from here)
 
 ModelResPrediction = namedtuple("ModelResPrediction", ["pred_res", "pred_noise", "pred_x_start"])
-# Trainer.test's quantiles: the levels handed to sample_ensemble, the caller's among them (the first ones), the index of the
-# estimate's level or None
-_QuantilePlan = namedtuple("_QuantilePlan", ["levels", "user", "estimate"])
 
 
 def set_seed(SEED):
@@ -346,79 +349,21 @@ class UnetRes(nn.Module):
         """src/DADiff.py:817-836.  time = [alphas_cumsum[t]*T, betas_cumsum[t]*T].  With gradients enabled on a model whose
         trainable view exists (Unet.trainable(): ResidualDiffusion.forward and Trainer.train ask for it) the call is a training
         forward, Unet.train_forward; under no_grad, and on a model that never trained, it is the engine as ever."""
-        views = [u._trainable is not None for u in self._unets()]
+        unets = self._unets()
+        views = [u._trainable is not None for u in unets]
         if torch.is_grad_enabled() and any(views):
-            if self.num_unet == 2:
-                # two training forwards (src/DADiff.py:817-823): unet0 at time[0], unet1 at time[1], each behind its own frozen tower
-                if not all(views):
-                    raise NotImplementedError("training two U-Nets: the reference optimises them with RAdam, and one of the two has "
-                                              "no trainable view: call model.trainable() (DESIGN.md section 8)")
-                if self.objective not in ("pred_res_noise", "pred_x0_noise"):
-                    raise ValueError(f"objective {self.objective!r} needs num_unet=1 (src/DADiff.py:826-831)")
-                return [self.unet0.train_forward(x, time[0]), self.unet1.train_forward(x, time[1])]
-            if self.objective not in ("pred_res", "pred_noise"):
-                raise ValueError(f"objective {self.objective!r} needs num_unet=2 (src/DADiff.py:826-831)")
-            return [self.unet0.train_forward(x, time[1] if self.objective == "pred_noise" else time[0])]
+            # one training forward per row of the objective (src/DADiff.py:817-823), each behind its own frozen tower
+            if self.num_unet == 2 and not all(views):
+                raise NotImplementedError("training two U-Nets: the reference optimises them with RAdam, and one of the two has "
+                                          "no trainable view: call model.trainable() (DESIGN.md section 8)")
+            return [unets[r.unet].train_forward(x, time[r.time]) for r in objectives.routed(self.objective, self.num_unet)]
         kw = dict(x_self_cond=x_self_cond, reuse_condition=reuse_condition)
         if self.num_unet == 2:
-            if self.test_res_or_noise == "res_noise":
-                return self.unet0(x, time[0], **kw), self.unet1(x, time[1], **kw)
-            if self.test_res_or_noise == "res":
-                return self.unet0(x, time[0], **kw), 0
-            if self.test_res_or_noise == "noise":
-                return 0, self.unet1(x, time[1], **kw)
-            raise ValueError(f"test_res_or_noise={self.test_res_or_noise!r}")
-        if self.objective == "pred_noise":
-            time = time[1]
-        elif self.objective == "pred_res":
-            time = time[0]
-        else:
-            raise ValueError(f"objective {self.objective!r} needs num_unet=2 (src/DADiff.py:826-831)")
-        return [self.unet0(x, time, **kw)]
-
-
-def residual_schedule(timesteps=1000, after_init=False):
-    """The 12 schedule vectors (src/DADiff.py:946-1027 for __init__, 1033-1118 for init())."""
-    import torch.nn.functional as F
-    betas = torch.linspace(1e-4, 0.02, timesteps, dtype=torch.float32)
-    acp = torch.cumprod(1.0 - betas, dim=0)
-    acs = 1 - acp ** 0.5
-    b2cs = 1 - acp
-    acs_prev = F.pad(acs[:-1], (1, 0), value=1.0)
-    b2cs_prev = F.pad(b2cs[:-1], (1, 0), value=1.0)
-    alphas = acs - acs_prev
-    betas2 = b2cs - b2cs_prev
-    alphas[0] = alphas[1] if after_init else 0
-    betas2[0] = betas2[1] if after_init else 0
-    pv = betas2 * b2cs_prev / b2cs
-    pv[0] = 0
-    out = dict(alphas=alphas, alphas_cumsum=acs, one_minus_alphas_cumsum=1 - acs, betas2=betas2,
-               betas=torch.sqrt(betas2), betas2_cumsum=b2cs, betas_cumsum=torch.sqrt(b2cs),
-               posterior_mean_coef1=b2cs_prev / b2cs,
-               posterior_mean_coef2=(betas2 * acs_prev - b2cs_prev * alphas) / b2cs,
-               posterior_mean_coef3=betas2 / b2cs, posterior_variance=pv,
-               posterior_log_variance_clipped=torch.log(pv.clamp(min=1e-20)))
-    out["posterior_mean_coef1"][0] = 0
-    out["posterior_mean_coef2"][0] = 0
-    out["posterior_mean_coef3"][0] = 1
-    out["one_minus_alphas_cumsum"][-1] = 1e-6
-    return {k: v.to(torch.float32) for k, v in out.items()}
-
-
-def load_weights(module, state_dict, what="checkpoint"):
-    """`load_state_dict` the way the reference's strict `Trainer.load` does (src/DADiff.py:1655-1663) for every
-    key that is live on the sampling path: dead weight is dropped by the modules' own `load_state_dict`, the
-    12 schedule buffers may be absent (they are re-derived by `init()`), anything else missing or unexpected
-    raises -- a checkpoint of another dim / dim_mults / num_unet / input_condition must not leave zero-
-    initialised weights behind silently."""
-    res = module.load_state_dict(state_dict, strict=False)
-    sched = set(residual_schedule(1000).keys())
-    missing = [k for k in res.missing_keys if k not in sched]
-    unexpected = list(res.unexpected_keys)
-    if missing or unexpected:
-        raise RuntimeError(f"{what} does not match this model: {len(missing)} live keys missing "
-                           f"(e.g. {missing[:3]}), {len(unexpected)} unexpected (e.g. {unexpected[:3]})")
-    return res
+            run = objectives.TEST_UNETS.get(self.test_res_or_noise)
+            if run is None:
+                raise ValueError(f"test_res_or_noise={self.test_res_or_noise!r}")
+            return tuple(unets[i](x, time[i], **kw) if i in run else 0 for i in (0, 1))
+        return [unets[r.unet](x, time[r.time], **kw) for r in objectives.routed(self.objective, 1)]
 
 
 class ResidualDiffusion(nn.Module, TiledSampling):
@@ -438,13 +383,11 @@ class ResidualDiffusion(nn.Module, TiledSampling):
         super().__init__()
         assert not (type(self) == ResidualDiffusion and model.channels != model.out_dim)
         assert not model.random_or_learned_sinusoidal_cond
-        if objective not in ("pred_res", "pred_noise", "pred_res_noise", "pred_x0_noise"):
-            raise ValueError(f"unknown objective {objective!r}")
+        objectives.check_objective(objective)
         if not condition:
             raise NotImplementedError("condition=True is what the DA-CLIP conditioned Unet supports "
                                       "(it reads x[:,1], src/DADiff.py:692)")
-        if objective in ("pred_res_noise", "pred_x0_noise") and getattr(model, "num_unet", 1) != 2:
-            raise ValueError(f"objective {objective!r} needs UnetRes(num_unet=2) (src/DADiff.py:826-831)")
+        objectives.check_model(objective, objectives.num_unet(model))
         if timesteps != 1000:
             raise NotImplementedError("init() of the reference hard-codes 1000 timesteps (src/DADiff.py:1034)")
         self.model = model
@@ -516,15 +459,13 @@ class ResidualDiffusion(nn.Module, TiledSampling):
         self._drop_graphs()
 
     def load_state_dict(self, state_dict, strict=True, assign=False):
-        live = {k: v for k, v in state_dict.items()
-                if not (arch.is_dead_key(k, "model.unet0.") or arch.is_dead_key(k, "model.unet1."))}
+        live = {k: v for k, v in state_dict.items() if not any(arch.is_dead_key(k, f"model.{n}.") for n in objectives.UNET_NAMES)}
         return super().load_state_dict(live, strict=strict, assign=assign)     # new weights -> new engines -> new graphs
 
     # ---- helpers
     def _drop_graphs(self):
         """Forget every captured graph (they bake in scheduler constants): init() re-derives the schedule."""
-        for name in ("unet0", "unet1"):
-            u = getattr(self.model, name, None)
+        for u in objectives.unets_of(self.model):
             for e in (getattr(u, "_engine", None) or {}).values():
                 e.graphs.clear()
 
@@ -543,25 +484,14 @@ class ResidualDiffusion(nn.Module, TiledSampling):
         time = (self.alphas_cumsum[t_idx] * self.num_timesteps).float().contiguous()
         return self._eng().forward(x, x_input, time, out=out)
 
-    # ---- objectives other than the shipped 'pred_res' 
+    # ---- objectives other than the shipped one: the rule is objectives.py's, the readings of it are here
     def _plan(self):
-        """(mode of fd_res_step_obj, run unet0?, run unet1?, unet0's time entry) for this objective /
+        """objectives.SamplePlan -- (mode of fd_res_step_obj, run unet0?, run unet1?, unet0's time entry) -- for this objective /
         test_res_or_noise -- UnetRes.forward (src/DADiff.py:817-836) + model_predictions (1168-1207)."""
-        if getattr(self.model, "num_unet", 1) == 2:
-            tst = self.test_res_or_noise
-            if self.objective == "pred_x0_noise":
-                if tst != "res_noise":
-                    raise ValueError("pred_x0_noise reads both model outputs: test_res_or_noise must be 'res_noise'")
-                return 3, True, True, 0
-            if self.objective != "pred_res_noise":
-                raise ValueError(f"objective {self.objective!r} with num_unet=2")
-            return {"res_noise": (2, True, True, 0), "res": (0, True, False, 0), "noise": (1, False, True, 0)}[tst]
-        if self.objective == "pred_noise":
-            return 1, True, False, 1            # the single UNet predicts the noise, fed with time[1]
-        return 0, True, False, 0
+        return objectives.sample_plan(self.objective, objectives.num_unet(self.model), self.test_res_or_noise)
 
     def _is_shipped(self):
-        return self._plan() == (0, True, False, 0) and not self.input_condition
+        return self._plan() == objectives.SHIPPED_PLAN and not self.input_condition
 
     def _captured_plan(self):
         """Every plan of _plan() samples on captured loops and device tables unless the model takes a third input plane."""
@@ -577,16 +507,14 @@ class ResidualDiffusion(nn.Module, TiledSampling):
         (each then holds max_sub_batch // 2 slices, so a call's workspace stays what max_sub_batch promises) and kept a
         multiple of `streams`."""
         grp = self.streams * self.max_sub_batch
-        _, r0, r1, _ = self._plan()
-        if r0 and r1:
+        if self._plan().two_engines:
             grp //= 2
             grp = max(grp - grp % self.streams, self.streams)
         return grp
 
     def _plan_unets(self):
         """The U-Nets this plan evaluates, unet0 first."""
-        _, r0, r1, _ = self._plan()
-        return ([self.model.unet0] if r0 else []) + ([self.model.unet1] if r1 else [])
+        return [getattr(self.model, objectives.UNET_NAMES[i]) for i in self._plan().unets]
 
     def _engines(self):
         """The engines of this plan's U-Nets in the slot of the running sub-batch (slot 0 outside _sample_concurrent)."""
@@ -594,21 +522,17 @@ class ResidualDiffusion(nn.Module, TiledSampling):
 
     def _o01(self, outs):
         """(o0, o1) as the step kernels (fd_res_step_obj*, fd_tiles_step_*) take them, from the raw outputs of _plan_unets() in
-        that order.  The single U-Net of 'pred_noise' predicts the noise: its output is the kernels' o1."""
-        mode, r0, r1, _ = self._plan()
-        if mode == 1 and r0:
-            return None, outs[0]
-        return outs[0] if r0 else None, outs[-1] if r1 else None
+        that order (objectives.SamplePlan.o01)."""
+        return self._plan().o01(outs)
+
+    _TIME_CUMSUMS = ("alphas_cumsum", "betas_cumsum")          # the schedule vector behind time input 0 and 1 (times T)
 
     # ---- the step tables of the captured loops of every plan: pure host functions of the schedule (tests/test_obj_loop_cpu.py)
     def _obj_time_tables(self):
         """(times0, times1): (T,) fp32 CPU tables of the two U-Nets' time inputs, or None where the plan does not run that U-Net --
         entry t is what _outputs feeds at step t."""
-        _, r0, r1, tsel0 = self._plan()
         hs, T = self._hs(), self.num_timesteps
-        t0 = ((hs["alphas_cumsum"] if tsel0 == 0 else hs["betas_cumsum"]) * T).float().contiguous() if r0 else None
-        t1 = (hs["betas_cumsum"] * T).float().contiguous() if r1 else None
-        return t0, t1
+        return tuple(None if ti is None else (hs[self._TIME_CUMSUMS[ti]] * T).float().contiguous() for ti in self._plan().times)
 
     def _obj_anc_table(self):
         """(T, 8) fp32 CPU: row t = {ac, bc, omac, c1, c2, c3, logvar, 0}, the row _par builds for p_sample at step t."""
@@ -657,13 +581,10 @@ class ResidualDiffusion(nn.Module, TiledSampling):
 
     def _outputs(self, x_in, x, t_idx):
         """raw outputs (o0, o1) of the UNets this configuration evaluates (None where it does not)."""
-        mode, r0, r1, tsel0 = self._plan()
-        T = self.num_timesteps
-        t0 = ((self.alphas_cumsum if tsel0 == 0 else self.betas_cumsum)[t_idx] * T).float().contiguous()
-        t1 = (self.betas_cumsum[t_idx] * T).float().contiguous()
+        plan, T = self._plan(), self.num_timesteps
         c2 = self._xc2 if self.input_condition else None
-        times = ([t0] if r0 else []) + ([t1] if r1 else [])
-        return (mode,) + self._o01([u.engine().forward(x, x_in, t, x_cond2=c2).clone() for u, t in zip(self._plan_unets(), times)])
+        times = [(getattr(self, self._TIME_CUMSUMS[plan.times[i]])[t_idx] * T).float().contiguous() for i in plan.unets]
+        return (plan.mode,) + plan.o01([u.engine().forward(x, x_in, t, x_cond2=c2).clone() for u, t in zip(self._plan_unets(), times)])
 
     def _set_cond2(self, x_input_condition):
         """third input plane (src/DADiff.py:1157-1158); already normalised by the caller / sample()."""
@@ -1108,7 +1029,7 @@ class ResidualDiffusion(nn.Module, TiledSampling):
         """The persistent loop buffers of this plan on the engines of the running slot, x_in loaded and the conditioning of every
         engine in place: (engines, mode, x_in, img, (o0, o1) as the step kernels take them, [(engine, time buffer, output buffer)
         of unet0, the same of unet1]) -- (None, None, None) where the plan does not run that U-Net."""
-        mode, r0, r1, _ = self._plan()
+        plan = self._plan()
         engines = self._engines()
         own = engines[0]                                          # holds what the U-Nets share, and the loop's graph
         x_in = own._b("obj_xin", shape, torch.float32)
@@ -1116,8 +1037,8 @@ class ResidualDiffusion(nn.Module, TiledSampling):
         img = own._b("obj_img", shape, torch.float32)
         self._encode_all(x_in, cond)
         nets = [(e, e._b("obj_time", (shape[0],), torch.float32), e._b("obj_out", shape, torch.float32)) if e else (None, None, None)
-                for e in (engines[0] if r0 else None, engines[-1] if r1 else None)]
-        return engines, mode, x_in, img, self._o01([out for _, _, out in nets if out is not None]), nets
+                for e in (engines[0] if plan.run0 else None, engines[-1] if plan.run1 else None)]
+        return engines, plan.mode, x_in, img, plan.o01([out for _, _, out in nets if out is not None]), nets
 
     def _obj_key(self, engines, shape):
         return (tuple(shape), self._plan(), self.num_timesteps) + tuple((e.mode, e.gen) for e in engines)
@@ -1251,9 +1172,8 @@ class ResidualDiffusion(nn.Module, TiledSampling):
             import warnings
             warnings.warn("founddiff_amd: precision='auto': this checkpoint's activations leave IEEE binary16's range; "
                           "this and every later sample() of the model run on the bfloat16 kernels")
-            for u in (getattr(self.model, "unet0", None), getattr(self.model, "unet1", None)):
-                if u is not None:
-                    u._auto_bf16 = True
+            for u in objectives.unets_of(self.model):
+                u._auto_bf16 = True
             res = run()
         return res
 
@@ -1339,15 +1259,13 @@ class ResidualDiffusion(nn.Module, TiledSampling):
     def weights_changed(self):
         """The parameters were written in place (ClipAdamEMA's raw pointers): forget the captured graphs and the packed engines."""
         self._drop_graphs()
-        for name in ("unet0", "unet1"):
-            u = getattr(self.model, name, None)
-            if u is not None:
-                u.weights_changed()
+        for u in objectives.unets_of(self.model):
+            u.weights_changed()
 
     def clone(self):
         """A deep copy with its own parameters and no engines, graphs or streams (the EMA model of Trainer.train)."""
         self.weights_changed()
-        unets = [u for u in (getattr(self.model, n, None) for n in ("unet0", "unet1")) if u is not None]
+        unets = objectives.unets_of(self.model)
         saved, self._side_streams = self._side_streams, {}
         engines = [u._train_engine for u in unets]
         for u in unets:
@@ -1360,12 +1278,12 @@ class ResidualDiffusion(nn.Module, TiledSampling):
                 u._train_engine = e
 
     def _train_ready(self, fn):
-        if getattr(self.model, "num_unet", 1) != 1:
+        if objectives.num_unet(self.model) != 1:
             # opt-in: the raising default is pinned by tests
-            if any(getattr(self.model, n)._trainable is None for n in ("unet0", "unet1")):
+            if any(u._trainable is None for u in objectives.unets_of(self.model)):
                 raise NotImplementedError(f"{fn}: training two U-Nets: the reference optimises them with RAdam, and this is opt-in: "
                                           "call model.trainable() on the UnetRes first, or train through Trainer(optimizer=\"radam\") "
-                                          "(DESIGN.md section 8); objectives 'pred_res' and 'pred_noise' train one")
+                                          f"(DESIGN.md section 8); objectives {objectives.ONE_UNET_TEXT} train one")
             return
         self.model.unet0.trainable()
 
@@ -1406,711 +1324,13 @@ class ResidualDiffusion(nn.Module, TiledSampling):
         precision.  The engines hold packed weights: after an optimiser step, weights_changed() comes first."""
         fn = "ResidualDiffusion.eval_items"
         _, schedule, objective, loss_type = dt._diffusion_args(fn, self)
-        if isinstance(imgs, dt.StoreBatch):
-            dt._check_qsample_store(fn, imgs, t, schedule, noise, slice_seeds)
-            x_in, x_res, noise, times, x0 = dt.q_sample(imgs, None, t, schedule, noise, slice_seeds, step, True, x0_out=True)
-        else:
-            if not isinstance(imgs, (list, tuple)) or len(imgs) != 2:
-                raise RuntimeError(f"{fn}: imgs must be [x_start, x_input] (condition=True without an input condition)")
-            dt._check_qsample(fn, imgs[0], imgs[1], t, schedule, noise, slice_seeds, dims=(4,))
-            x_in, x_res, noise, times, x0 = dt.q_sample(imgs[0], imgs[1], t, schedule, noise, slice_seeds, step, True, x0_out=True)
+        x_in, times, targets = dt._diffused(fn, imgs, t, schedule, noise, slice_seeds, step, True, x0_out=True)
         x_t, x_input = x_in[:, 0:1].contiguous(), x_in[:, 1:2].contiguous()
-        # (U-Net, its time input, its target, whether its output is a residual): UnetRes.forward's routing, p_losses_fn's targets
-        plan = {"pred_res": [("unet0", 0, x_res, True)], "pred_noise": [("unet0", 1, noise, False)],
-                "pred_res_noise": [("unet0", 0, x_res, True), ("unet1", 1, noise, False)],
-                "pred_x0_noise": [("unet0", 0, x0, False), ("unet1", 1, noise, False)]}[objective]
         out = []
         with torch.cuda.device(x_in.device):
-            for name, ti, target, residual in plan:
-                eng = getattr(self.model, name).engine(precision)
+            for r in objectives.TRAINING[objective]:              # UnetRes.forward's routing, p_losses_fn's targets
+                eng = getattr(self.model, objectives.UNET_NAMES[r.unet]).engine(precision)
                 eng.encode_condition(x_input)
-                pred = eng.forward(x_t, x_input, times[ti])
-                out.append(dt.val_items(pred, target, loss_type, *((x_input, x0) if residual else ())))
+                pred = eng.forward(x_t, x_input, times[r.time])
+                out.append(dt.val_items(pred, targets[r.target], loss_type, *((x_input, targets["x0"]) if r.residual else ())))
         return out
-
-
-class _Accel:
-    """Stand-in for the accelerate attributes train.py reads (train.py:162-177)."""
-    is_local_main_process = True
-    is_main_process = True
-
-    def __init__(self, device, group=None, data_parallel=False):
-        """data_parallel: the attributes become those of this rank of `group` (Trainer(data_parallel=True))"""
-        self.device, self.group, self.data_parallel = device, group, bool(data_parallel)
-        if self.data_parallel:
-            import torch.distributed as dist
-            self.is_main_process = dist.get_rank(group) == 0
-            self.is_local_main_process = int(os.environ.get("LOCAL_RANK", dist.get_rank(group))) == 0
-
-    def wait_for_everyone(self):
-        if self.data_parallel:
-            import torch.distributed as dist
-            if dist.get_backend(self.group) == "nccl" and self.device.index is not None:
-                dist.barrier(group=self.group, device_ids=[self.device.index])
-            else:
-                dist.barrier(group=self.group)
-
-
-class _EMAView:
-    """`trainer.ema.ema_model` of the reference (ema_pytorch wrapper around the diffusion)."""
-
-    def __init__(self, model):
-        self.ema_model = model
-
-    def to(self, device):
-        self.ema_model.to(device)
-        return self
-
-    def load_state_dict(self, sd, strict=True):
-        live = {k[len("ema_model."):]: v for k, v in sd.items() if k.startswith("ema_model.")}
-        if strict:
-            return load_weights(self.ema_model, live, "ema state")
-        return self.ema_model.load_state_dict(live, strict=False)
-
-
-class Trainer(object):
-    """The reference Trainer's surface (src/DADiff.py:1506-1966): `train`, `save`, `load`, `sample`, `test`,
-    `.accelerator.is_local_main_process`, `.results_folder`, `.train_logger`.  Unlike the reference (whose datasets glob
-    private paths inside the class), the datasets are passed in: `dataset` (evaluation) is any object with
-    `__len__`, `__getitem__ -> [ndct, ldct]` ((1,H,W) tensors in [0,1]) and `load_name(i)`; `train_dataset` needs the first two.
-    `augment=True` applies the reference's RandomFlip + RandomRotate90 to every training pair (data/pdf_dataset.py:521-545), both
-    images under one transform, drawn per item by diffusion_train.train_augment; `augment_flip` is ignored, as before.
-    `crop_size` (an int or (h, w), multiples of 2 ** (levels - 1) of the U-Net; None: whole slices) trains on the reference's
-    CropToFixed patches (data/transforms.py:196-249): every training pair is cut to the window diffusion_train.train_crop draws
-    per item, reflect-padded where the slice is smaller, before the flip / rot90, which then needs a square crop for its odd
-    rotations and no longer square slices; sample() and test() keep whole slices (test(tile=...) samples them as tiles of that size).
-    `train_dataset` may be a data.DeviceSliceStore: train() then gathers (and augments) every micro-batch on the device and
-    uploads no image.  `seed` keys what train() draws (diffusion_train.train_batch_indices / train_t_and_seeds / train_augment),
-    `log_every` is how often the loss is read back from the device.
-    `optimizer`: None or 'adam' is clip + Adam(`adam_betas`) on one U-Net, and train() / save() raise NotImplementedError for
-    two; 'radam' is the reference's optimiser of two U-Nets (src/DADiff.py:1598-1602, 1707): one diffusion_train.ClipRAdamEMA
-    with `radam_betas` (RAdam's defaults, as there) over the trainable parameters of every U-Net -- one clip over both, both
-    updates and the one EMA in three launches -- and a checkpoint with 'opt0' and 'opt1' (diffusion_train.CHECKPOINT_KEYS_2).
-    It is opt-in because the raising default is pinned by tests.  On one U-Net 'radam' is the reference's
-    commented-out alternative (line 1594): the checkpoint keeps its five keys, 'opt0' in RAdam's layout.
-    `val_dataset` (as train_dataset, or a data.DeviceSliceStore) is what validate() evaluates the EMA model on, forward-only: the
-    held-out loss and the one-step PSNR / RMSE per noise band of `val_bands` (increasing edges inside [0, T]), on the first
-    `val_items` items (None: all), keyed by `val_seed`, `val_batch_size` (item, band) pairs per launch sequence.  train() calls
-    it every `validate_every` steps (0: never) and, with `keep_best`, saves model-best.pt whenever a validation beats every
-    earlier one of this process.  All of it is off by default.  `val_crop_size` (an int or (h, w); None: whole slices) makes
-    validate() evaluate the centred window of that size of every held-out slice -- the reference's CropToFixed(Center=True),
-    origin (n - c) // 2 per axis -- which is how a model trained with `crop_size` was trained; a crop larger than the slice
-    raises.
-    `data_parallel=True` (off by default; `process_group` None: the default group) trains on the W ranks of an initialised
-    torch.distributed group, one process per GPU, the reference's accelerate / DDP run (src/DADiff.py:1546-1623, 1705-1720).
-    init_process_group is the caller's job (give it a finite timeout=, so that a lost peer ends in an error).  Micro-batch a of
-    rank r is global micro-batch a W + r of A W, A = gradient_accumulate_every per rank: that number and that count key the
-    indices, t, seeds, codes and windows, and the loss scale is 1 / (A W); diffusion_train.GradReducer adds the ranks' gradients
-    in rank order, so that every parameter, EMA tensor, optimiser tensor and logged loss is bit for bit that of one process with
-    gradient_accumulate_every = A W, whatever W.  Batch semantics: the reference's split_batches=True splits one batch of
-    train_batch_size over the ranks; here a rank keeps train_batch_size and A W counts the micro-batches of a step.  Rank 0's
-    model and buffers are broadcast once when training is set up; a DeviceSliceStore is held whole by every rank; previews,
-    validate() and the checkpoint file are rank 0's, save() is called by every rank and ends in a barrier and check_replicas(),
-    load(for_training=True) runs on every rank.  `split_batches` itself is ignored, as before."""
-
-    def __init__(self, opt, diffusion_model, folder=None, *, train_batch_size=16, gradient_accumulate_every=1,
-                 augment_flip=True, train_lr=1e-4, train_num_steps=100000, ema_update_every=10, ema_decay=0.995,
-                 adam_betas=(0.9, 0.99), save_and_sample_every=1000, num_samples=25, results_folder=".results/sample",
-                 amp=False, fp16=False, split_batches=True, convert_image_to=None, condition=False, sub_dir=False,
-                 equalizeHist=False, crop_patch=False, generation=False, num_unet=2, checkpoint_folder=None,
-                 is_train=True, train_logger=None, dataset=None, device=None, train_dataset=None, seed=0, log_every=100,
-                 augment=False, crop_size=None, optimizer=None, radam_betas=(0.9, 0.999), val_crop_size=None, data_parallel=False,
-                 process_group=None, val_dataset=None,
-                 validate_every=0, val_bands=(0, 250, 500, 750, 1000), val_items=None, val_seed=0, val_batch_size=8, keep_best=False):
-        import logging
-        import os as _os
-        self.data_parallel, self.process_group = bool(data_parallel), process_group
-        self.world, self.rank = 1, 0
-        if self.data_parallel:
-            import torch.distributed as dist
-            if not (dist.is_available() and dist.is_initialized()):
-                raise RuntimeError("Trainer: data_parallel=True needs an initialised process group: call "
-                                   "torch.distributed.init_process_group (with a finite timeout=) before the constructor")
-            self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
-        self._reducer = None                 # diffusion_train.GradReducer, made with the optimiser
-        self.fingerprints = None             # with data_parallel: every rank's fingerprint at the last replica check
-        if optimizer not in (None, "adam", "radam"):
-            raise RuntimeError(f"Trainer: optimizer must be None, 'adam' or 'radam' (got {optimizer!r})")
-        if len(tuple(radam_betas)) != 2 or not all(isinstance(b, (int, float)) and 0 <= b < 1 for b in radam_betas):
-            raise RuntimeError(f"Trainer: radam_betas must be two numbers in [0, 1) (got {radam_betas!r})")
-        self.optimizer, self.radam_betas = optimizer or "adam", tuple(float(b) for b in radam_betas)
-        self.val_bands = dt.check_bands("Trainer", val_bands, getattr(diffusion_model, "num_timesteps", 1000))
-        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-        if not is_int(validate_every) or validate_every < 0 or not is_int(val_batch_size) or not 1 <= val_batch_size <= 65535 or \
-                not is_int(val_seed) or not (val_items is None or (is_int(val_items) and val_items >= 1)):
-            raise RuntimeError(f"Trainer: invalid validation arguments validate_every={validate_every!r} val_items={val_items!r} "
-                               f"val_seed={val_seed!r} val_batch_size={val_batch_size!r} (integers; validate_every >= 0, val_items "
-                               f"None or >= 1, 1 <= val_batch_size <= 65535)")
-        if validate_every > 0 and val_dataset is None:
-            raise RuntimeError(f"Trainer: validate_every={validate_every} needs a val_dataset")
-        self.val_dataset, self.validate_every, self.val_items = val_dataset, int(validate_every), val_items
-        self.val_seed, self.val_batch_size, self.keep_best = int(val_seed), int(val_batch_size), bool(keep_best)
-        self.val_log = []                    # validate()'s results of this process, in order; not part of a checkpoint
-        self.best = None                     # with keep_best: the entry of val_log that save("best") was last called for
-        self._val_store = None               # val_dataset on the device, made at the first validate()
-        self.val_crop_size = None if val_crop_size is None else dt.crop_pair("Trainer", val_crop_size, "val_crop_size")
-        if self.val_crop_size is not None and min(self.val_crop_size) < 1:
-            raise RuntimeError(f"Trainer: val_crop_size {self.val_crop_size} must be positive")
-        self.crop_size = None
-        if crop_size is not None:
-            from .data import crop_pair
-            ch, cw = crop_pair("Trainer", crop_size, "crop_size")
-            unet = getattr(getattr(diffusion_model, "model", None), "unet0", None)
-            step = 2 ** (len(getattr(unet, "dim_mults", (1,))) - 1)
-            if ch < 1 or cw < 1 or ch % step or cw % step:
-                raise RuntimeError(f"Trainer: crop_size {ch} x {cw} must be positive multiples of {step} (the U-Net has "
-                                   f"{len(getattr(unet, 'dim_mults', (1,)))} levels)")
-            self.crop_size = (ch, cw)
-        self.opt = opt
-        self.checkpoint_folder = checkpoint_folder or "."
-        self.results_folder = self.checkpoint_folder + "/sample"
-        _os.makedirs(self.results_folder, exist_ok=True)
-        assert int(math.sqrt(num_samples)) ** 2 == num_samples, "number of samples must have an integer square root"
-        self.num_samples = num_samples
-        self.condition = condition
-        self.num_unet = num_unet
-        self.sub_dir, self.crop_patch = sub_dir, crop_patch
-        self.image_size = diffusion_model.image_size
-        self.device = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
-        self.accelerator = _Accel(self.device, process_group, self.data_parallel)
-        self.model = diffusion_model.to(self.device)
-        self.ema = _EMAView(self.model)      # inference uses the EMA weights (src/DADiff.py:1818-1822)
-        self.sample_dataset = dataset if dataset is not None else folder
-        self.train_logger = train_logger or logging.getLogger("founddiff_amd")
-        self.step = 0
-        self.train_dataset = train_dataset
-        self.batch_size, self.gradient_accumulate_every = int(train_batch_size), int(gradient_accumulate_every)
-        self.train_lr, self.adam_betas, self.train_num_steps = train_lr, tuple(adam_betas), int(train_num_steps)
-        self.ema_decay, self.ema_update_every = ema_decay, int(ema_update_every)
-        self.save_and_sample_every = int(save_and_sample_every)
-        self.seed, self.log_every = int(seed), int(log_every)
-        self.augment = bool(augment)
-        self.opt0 = None                     # ClipAdamEMA, made with the EMA copy at the first train() / save() / load(for_training=True)
-        self.losses = None                   # the last step's losses, on the device
-        self.loss_log = []                   # (step, [loss per U-Net]) of every logged step (the last 1024), as floats
-        self.batch_log = []                  # a debugging aid: the dataset indices train() drew, one list per micro-batch (the
-                                             # last 1024); diffusion_train.train_batch_indices gives the same without a run
-        self._stale = False                  # a step has written the weights since the engines were packed
-        self.condition_type = 2
-        self.test_running_psnr, self.test_running_ssim, self.test_running_rmse = [], [], []
-
-    def load(self, milestone, for_training=False):
-        """Read `<ckpt>/sample/model-N.pt` = {'step','model','opt0','ema','scaler'}
-        (src/DADiff.py:1648-1669).  The EMA weights win when present; a missing file is skipped
-        silently like the reference does.  for_training=True resumes instead: the online model takes 'model', the EMA copy
-        'ema', the optimiser 'opt0', and the step and EMA counters are restored, so that train() continues as the run that
-        saved would have."""
-        from pathlib import Path
-        path = Path(self.results_folder + "/" + f"model-{milestone}.pt")
-        if not path.exists():
-            return
-        data = torch.load(str(path), map_location="cpu", weights_only=False)
-        if for_training:
-            index, n = self._setup_training()
-            if self._two_unets():
-                step, model_sd, ema_sd, opt_sd = dt.checkpoint_unpack2(data, index, self._unet_index())
-            else:
-                step, model_sd, ema_sd, opt_sd = dt.checkpoint_unpack(data, index, n, optimizer=self.optimizer)
-            load_weights(self.model, model_sd, f"{path}['model']")
-            load_weights(self.ema.ema_model, ema_sd, f"{path}['ema']")
-            self.model.to(self.device)
-            self.ema.ema_model.to(self.device)
-            self.opt0.load_state_dict(opt_sd)
-            self.step = step
-            self._stale = False
-            self.model.weights_changed()
-            self.ema.ema_model.weights_changed()
-            print("load model - " + str(path))
-            return
-        load_weights(self.model, data["model"], f"{path}['model']")
-        self.step = data.get("step", 0)
-        ema = data.get("ema")
-        if ema:
-            live = {k[len("ema_model."):]: v for k, v in ema.items() if k.startswith("ema_model.")}
-            if live:
-                load_weights(self.model, live, f"{path}['ema']")
-        self.model.to(self.device)
-        getattr(self.model, "weights_changed", lambda: None)()
-        if self.ema.ema_model is not self.model:
-            # train() has made the EMA copy, and sample() / test() read it: it takes the same winning weights
-            self.ema.ema_model.load_state_dict(self.model.state_dict())
-            self.ema.ema_model.to(self.device)
-            self.ema.ema_model.weights_changed()
-            self._stale = False
-        print("load model - " + str(path))
-
-    # ---- training (src/DADiff.py:1626-1646, 1673-1763)
-    def _setup_training(self):
-        """The EMA copy and the optimiser, made once: (the places of the trainable parameters in diffusion.parameters(), their
-        number).  Until here self.ema.ema_model is self.model."""
-        dif = self.model
-        if getattr(dif.model, "num_unet", 1) != 1 and self.optimizer != "radam":
-            raise NotImplementedError("Trainer.train: two U-Nets are optimised with RAdam in the reference: pass optimizer='radam' "
-                                      "(the default, Adam, trains one U-Net; DESIGN.md section 8)")
-        dif.model.trainable()
-        params = list(dif.parameters())
-        index = [i for i, p in enumerate(params) if p.requires_grad]
-        if self.opt0 is None:
-            if self.device.type != "cuda":
-                raise RuntimeError("Trainer.train: the model must live on the GPU (there is no CPU path)")
-            if self.data_parallel:
-                # once: every replica starts from rank 0's model and buffers; from here on identical gradients keep them identical
-                from .parallel import broadcast_tensors
-                broadcast_tensors(list(dif.parameters()) + list(dif.buffers()), 0, self.process_group)
-                if self.ema.ema_model is not dif:
-                    broadcast_tensors(list(self.ema.ema_model.parameters()) + list(self.ema.ema_model.buffers()), 0, self.process_group)
-                dif.weights_changed()
-            if self.ema.ema_model is dif:
-                self.ema = _EMAView(dif.clone())
-            eparams = list(self.ema.ema_model.parameters())
-            cls, betas = (dt.ClipRAdamEMA, self.radam_betas) if self.optimizer == "radam" else (dt.ClipAdamEMA, self.adam_betas)
-            self.opt0 = cls([params[i] for i in index], [eparams[i] for i in index], lr=self.train_lr, betas=betas, max_norm=1.0,
-                            ema_beta=self.ema_decay, ema_update_every=self.ema_update_every)
-            if self.data_parallel:
-                self._reducer = dt.GradReducer(self.opt0, self.process_group)
-        return index, len(params)
-
-    def fingerprint(self):
-        """an int64 sum of the parameters, the EMA copy's, the optimiser's moments and its step counts, each viewed as int32: equal
-        on two replicas whose tensors are bitwise equal (and almost surely different otherwise).  Reads the device."""
-        self._setup_training()
-        tensors = [p.detach() for p in self.model.parameters()] + [p.detach() for p in self.ema.ema_model.parameters()] + \
-            [self.opt0._m, self.opt0._v, self.opt0._steps]
-        tot = torch.zeros((), dtype=torch.int64, device=self.device)
-        for t in tensors:
-            if t.element_size() == 4 and t.numel():
-                tot = tot + t.contiguous().view(-1).view(torch.int32).sum(dtype=torch.int64)
-        return int(tot.item()) + int(self.opt0.ema_step)
-
-    def check_replicas(self):
-        """data_parallel: every rank's fingerprint() gathered on every rank (self.fingerprints); RuntimeError on every rank if two
-        differ -- the replicas have drifted apart, which identical gradients and identical optimisers cannot do."""
-        if not self.data_parallel:
-            return
-        from .parallel import gather_int64
-        self.fingerprints = gather_int64(self.fingerprint(), self.device, self.process_group)
-        if len(set(self.fingerprints)) != 1:
-            raise RuntimeError(f"Trainer: the replicas differ at step {self.step}: fingerprints per rank {self.fingerprints} "
-                               f"(parameters, EMA and optimiser state as int32 sums)")
-
-    def _two_unets(self):
-        return getattr(self.model.model, "num_unet", 1) == 2
-
-    def _unet_index(self):
-        """the places of unet0.parameters() and of unet1.parameters() in diffusion.parameters(), each in its U-Net's order
-        (diffusion_train.checkpoint_pack2)"""
-        place = {id(p): i for i, p in enumerate(self.model.parameters())}
-        return tuple([place[id(p)] for p in u.parameters()] for u in (self.model.model.unet0, self.model.model.unet1))
-
-    def _fresh_engines(self):
-        """before anything samples after a step has written the weights"""
-        if self._stale:
-            self.model.weights_changed()
-            if self.ema.ema_model is not self.model:
-                self.ema.ema_model.weights_changed()
-            self._stale = False
-
-    def train(self):
-        """The reference's loop (src/DADiff.py:1683-1732) from self.step to train_num_steps: gradient_accumulate_every micro-batches
-        through diffusion_train.train_step (clip 1.0, Adam, zero_grad, the EMA), a preview from the EMA model every
-        save_and_sample_every steps and save() on the reference's schedule (its FID run is not built).  Micro-batch m of step s,
-        its t, its noise and (with augment) its flip / rot90 codes are functions of (seed, s, m) alone; the losses stay on the
-        device and are read every log_every steps.  From a data.DeviceSliceStore, or with augment or crop_size, a micro-batch is a
-        diffusion_train.StoreBatch: its indices, codes, windows, t and seeds go up as one table and nothing waits for the host; a
-        host dataset without augment and crop_size is loaded, stacked and uploaded as before.
-        With validate_every > 0 every validate_every-th step is followed by validate(), which reads the weights and writes none:
-        the run's tensors and counters are those of the same run without it.  With keep_best a validation that beats every
-        earlier one of this process is followed by save("best") (_keep_best).  val_log and best are not part of a checkpoint,
-        whose keys stay diffusion_train.CHECKPOINT_KEYS (CHECKPOINT_KEYS_2 for two U-Nets): a resumed run starts with both empty
-        and re-establishes its best at its first validation, overwriting model-best.pt whatever the interrupted run had reached.
-        optimizer='radam' runs the same loop around ClipRAdamEMA, on one U-Net or two; the log line then has loss_unet1 too.
-        With data_parallel every rank runs this loop over its own micro-batch numbers (a W + rank) and the gradients meet in
-        diffusion_train.GradReducer; rank 0 logs, previews and validates, every rank joins save() and the replica check that
-        also ends the run.  loss_log keeps (step, losses) of every logged step on every rank."""
-        from .data import DeviceSliceStore
-        self._setup_training()
-        ds = self.train_dataset
-        if ds is None or len(ds) < 1:
-            raise RuntimeError("Trainer.train: give the constructor a train_dataset (__len__, __getitem__ -> [ndct, ldct])")
-        if self.sample_dataset is None:
-            self.sample_dataset = ds
-        every, T = self.save_and_sample_every, self.model.num_timesteps
-        # data_parallel: micro-batch a of this rank is global micro-batch a W + rank of the step's A W
-        W, rank, main = self.world, self.rank, self.rank == 0
-        acc = self.gradient_accumulate_every * W
-        while self.step < self.train_num_steps:
-            batches, ts, seeds = [], [], []
-            for m in (dt.dp_micro(a, W, rank) for a in range(self.gradient_accumulate_every)):
-                idx = dt.train_batch_indices(self.seed, self.step, m, self.batch_size, len(ds), acc)
-                self.batch_log.append(idx)
-                t, sd = dt.train_t_and_seeds(self.seed, self.step, m, idx, T)
-                if isinstance(ds, DeviceSliceStore) or self.augment or self.crop_size:
-                    store, local = (ds, idx) if isinstance(ds, DeviceSliceStore) else \
-                        (DeviceSliceStore.from_items([ds[i] for i in idx], self.device), list(range(len(idx))))
-                    crop = self.crop_size
-                    square = store.H == store.W if crop is None else crop[0] == crop[1]
-                    codes = dt.train_augment(self.seed, self.step, m, idx, square) if self.augment else None
-                    windows = dt.train_crop(self.seed, self.step, m, idx, store.H, store.W, crop) if crop else None
-                    batches.append(dt.StoreBatch(store, local, codes, windows, crop))
-                    ts.append(t)
-                    seeds.append(sd)
-                    continue
-                items = [ds[i] for i in idx]
-                batches.append([torch.stack([it[j] for it in items]).float().to(self.device) for j in range(2)])
-                ts.append(torch.from_numpy(t).to(self.device))
-                seeds.append(torch.from_numpy(sd).to(self.device))
-            del self.batch_log[:-1024]
-            self.losses = dt.train_step(self.model, self.opt0, batches, t=ts, slice_seeds=seeds, step=self.step, reducer=self._reducer)
-            self._stale = True
-            self.step += 1
-            if self.log_every > 0 and self.step % self.log_every == 0:                 # the one synchronisation of these steps
-                vals = [float(v) for v in self.losses]
-                self.loss_log.append((self.step, vals))
-                del self.loss_log[:-1024]
-                if main:
-                    self.train_logger.info("Iters: [%d/%d], " % (self.step, self.train_num_steps) +
-                                           ", ".join("loss_unet%d: %.6f" % (u, v) for u, v in enumerate(vals)))
-            if self.validate_every > 0 and self.step % self.validate_every == 0:
-                res = self.validate() if main else None
-                if self.keep_best and not self.data_parallel:
-                    self._keep_best(res)
-                elif self.keep_best:                                                   # rank 0 decides, every rank joins save()
-                    from .parallel import gather_int64
-                    if gather_int64(int(self._is_best(res)) if main else 0, self.device, self.process_group)[0]:
-                        self.save("best")
-            if self.step % every == 0:
-                milestone = self.step // every
-                if main:
-                    self.sample(milestone)
-                if self.step > every * 10 * 4 and self.step % (every * 10) == 0:
-                    self.save(milestone)
-        self.check_replicas()
-        print("training complete")
-
-    def save(self, milestone):
-        """`<results>/model-N.pt` = {'step', 'model', 'opt0', 'ema', 'scaler': None} (src/DADiff.py:1626-1646;
-        diffusion_train.checkpoint_pack)."""
-        index, n = self._setup_training()
-        if self.data_parallel:
-            # every rank calls save(): rank 0 writes the file (its keys and layout are the single process's: a checkpoint written
-            # at W ranks of A micro-batches resumes at any W', A' with A' W' = A W), then a barrier and the replica check
-            if self.rank == 0:
-                self._write_checkpoint(milestone, index, n)
-            self.accelerator.wait_for_everyone()
-            self.check_replicas()
-            return
-        self._write_checkpoint(milestone, index, n)
-
-    def _write_checkpoint(self, milestone, index, n):
-        ema_sd = {k: v.detach().clone() for k, v in self.ema.ema_model.state_dict().items()}
-        model_sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        if self._two_unets():
-            data = dt.checkpoint_pack2(self.step, model_sd, ema_sd, self.opt0.state_dict(), index, self._unet_index())
-        else:
-            data = dt.checkpoint_pack(self.step, model_sd, ema_sd, self.opt0.state_dict(), index, n)
-        torch.save(data, self.results_folder + "/" + f"model-{milestone}.pt")
-
-    # ---- held-out evaluation during a run (the reference has none before its full test() at step 50 000, src/DADiff.py:1731-1745)
-    @torch.no_grad()
-    def validate(self, precision="fp32"):
-        """The EMA model (the model itself until train() copies it) on val_dataset: whole slices (with val_crop_size their centred
-        window of that size, through the store's explicit windows), no augmentation, the first val_items of them (None: all).
-        Every item is evaluated once per noise band of val_bands, at the t and with the
-        noise diffusion_train.val_draws keys by (val_seed, item, band), in batches of val_batch_size (item, band) pairs through
-        diffusion_train.StoreBatch and ResidualDiffusion.eval_items on the `precision` engine; a host dataset goes to the device
-        once, at the first call.  Returns {"step", "bands", "loss", "psnr", "rmse", "n"}: loss, psnr and rmse are lists per
-        U-Net, then per band, of diffusion_train.val_summary's means (psnr and rmse of the one-step denoising error, NaN for an
-        output that is no residual), n the items per band; the dict is appended to val_log and logged, one line per band and
-        one over all bands.  Deterministic: the numbers depend on the weights alone, not on the step, the training seed or
-        val_batch_size."""
-        from .data import DeviceSliceStore
-        fn = "Trainer.validate"
-        if self.val_dataset is None:
-            raise RuntimeError(f"{fn}: give the constructor a val_dataset (__len__, __getitem__ -> [ndct, ldct])")
-        if self.device.type != "cuda":
-            raise RuntimeError(f"{fn}: the model must live on the GPU (there is no CPU path)")
-        if self._val_store is None:
-            ds = self.val_dataset
-            self._val_store = ds if isinstance(ds, DeviceSliceStore) else DeviceSliceStore.from_dataset(ds, self.device)
-        store, ema = self._val_store, self.ema.ema_model
-        crop = self.val_crop_size
-        if crop is not None and (crop[0] > store.H or crop[1] > store.W):
-            raise RuntimeError(f"{fn}: val_crop_size {crop[0]} x {crop[1]} is larger than the slices {store.H} x {store.W}")
-        n = len(store) if self.val_items is None else min(int(self.val_items), len(store))
-        item, band, t, seeds = dt.val_draws(self.val_seed, range(n), self.val_bands, ema.num_timesteps)
-        self._fresh_engines()
-        rows = []
-        for s in range(0, len(item), self.val_batch_size):
-            sl = slice(s, s + self.val_batch_size)
-            if crop is None:
-                batch = dt.StoreBatch(store, item[sl])
-            else:                                             # the centred window: CropToFixed(Center=True), origin (n - c) // 2
-                win = np.tile(np.array([[(store.H - crop[0]) // 2, (store.W - crop[1]) // 2]], dtype=np.int64), (len(item[sl]), 1))
-                batch = dt.StoreBatch(store, item[sl], None, win, crop)
-            rows.append(ema.eval_items(batch, t[sl], slice_seeds=seeds[sl], precision=precision))
-        nb = len(self.val_bands) - 1
-        per_unet = [torch.cat([r[u] for r in rows]).cpu().numpy() for u in range(len(rows[0]))]      # the one synchronisation
-        sums = [dt.val_summary(v, band, nb) for v in per_unet]
-        res = {"step": self.step, "bands": list(self.val_bands), "loss": [s["loss"] for s in sums], "psnr": [s["psnr"] for s in sums],
-               "rmse": [s["rmse"] for s in sums], "n": sums[0]["n"]}
-        self.val_log.append(res)
-        info = self.train_logger.info
-        for u, s in enumerate(sums):
-            for k in range(nb):
-                info("Iters: [%d/%d], unet%d t in [%d, %d): val_loss: %.6f, val_psnr: %.4f, val_rmse: %.6f (%d items)" % (
-                    self.step, self.train_num_steps, u, self.val_bands[k], self.val_bands[k + 1], s["loss"][k], s["psnr"][k],
-                    s["rmse"][k], s["n"][k]))
-            tot = dt.val_summary(per_unet[u], np.zeros(len(band), dtype=np.int64), 1)
-            info("Iters: [%d/%d], unet%d val_loss: %.6f, val_psnr: %.4f, val_rmse: %.6f" % (
-                self.step, self.train_num_steps, u, tot["loss"][0], tot["psnr"][0], tot["rmse"][0]))
-        return res
-
-    @staticmethod
-    def _val_score(res):
-        """("psnr", the mean one-step PSNR over the items of every band) where a U-Net has a residual output, else ("loss", the
-        mean loss over items, bands and U-Nets)"""
-        mean = lambda per_band: float(np.average(per_band, weights=res["n"]))
-        psnr = [mean(p) for p in res["psnr"] if not np.isnan(p).all()]
-        if psnr:
-            return "psnr", float(np.mean(psnr))
-        return "loss", float(np.mean([mean(v) for v in res["loss"]]))
-
-    def _keep_best(self, res):
-        """save("best") if `res` (a result of validate()) beats every earlier one of this process: a higher mean one-step PSNR,
-        or a lower mean loss where no U-Net has a residual output.  self.best = {"step", "metric", "value"} of the winner."""
-        if self._is_best(res):
-            self.save("best")
-            self.train_logger.info("Iters: [%d/%d], best val_%s so far: %.6f, saved model-best.pt" % (
-                self.step, self.train_num_steps, self.best["metric"], self.best["value"]))
-
-    def _is_best(self, res):
-        """whether `res` beats every earlier validation of this process; self.best then becomes its entry"""
-        metric, value = self._val_score(res)
-        old = self.best
-        if old is None or np.isnan(old["value"]) or (value > old["value"] if metric == "psnr" else value < old["value"]):
-            self.best = {"step": res["step"], "metric": metric, "value": value}
-            return True
-        return False
-
-    # anatomy groups of the reference's 2020 test list, in item order: (name, slices per dose level); each holds
-    # 4 dose levels back to back (src/DADiff.py:1918-1950).  "head" is taken from the END of the list, as there.
-    test_groups = (("ab", 290), ("lung", 637), ("head", 159))
-
-    @torch.no_grad()
-    def sample(self, milestone, last=True, FID=False):
-        """Preview grid of [NDCT, LDCT, x_T, output] in the HU display window, `<results>/sample-N.png`
-        (src/DADiff.py:1765-1815); with FID, one PNG per generated image, `milestone` advancing."""
-        from .data import hu_window, save_image
-        n = min(self.num_samples, len(self.sample_dataset))
-        items = [self.sample_dataset[i] for i in range(n)]
-        show = [torch.stack([it[j] for it in items]).to(self.device) for j in range(len(items[0]))]
-        self._fresh_engines()
-        outs = list(self.ema.ema_model.sample(show[1:], batch_size=n, last=last))      # (the model itself until train() copies it)
-        all_images_list = show + outs
-        all_images = hu_window(torch.cat(all_images_list, dim=0))
-        nrow = int(math.sqrt(self.num_samples)) if last else all_images.shape[0]
-        if FID:
-            for i in range(n):
-                file_name = f"sample-{milestone}.png"
-                save_image(all_images_list[0][i].unsqueeze(0), os.path.join(self.results_folder, file_name), nrow=1)
-                milestone += 1
-                if milestone >= getattr(self, "total_n_samples", 50000):
-                    break
-        else:
-            file_name = f"sample-{milestone}.png"
-            save_image(all_images, self.results_folder + "/" + file_name, nrow=nrow)
-        print("sampe-save " + file_name)
-        return milestone
-
-    @staticmethod
-    def image_file_name(file_name):
-        """PNG name of a result (src/DADiff.py:1904-1907): quarter-dose files keep the part before the first
-        dot, simulated-dose files (`...-0.25-0012.npy`) keep the dose fraction's dot."""
-        if "quarter" in file_name:
-            return file_name.split(".")[0] + ".png"
-        return file_name.split(".")[0] + "." + file_name.split(".")[1] + ".png"
-
-    def _log_groups(self):
-        """Per-anatomy and per-dose means of the running metrics (src/DADiff.py:1918-1950), same slicing rule
-        and log lines; groups the evaluated list does not reach log nan, as np.mean of an empty slice does."""
-        def mean(v):
-            return float(np.mean(v)) if len(v) else float("nan")
-        P, S, R = self.test_running_psnr, self.test_running_ssim, self.test_running_rmse
-        out, off = {}, 0
-        for gi, (name, length) in enumerate(self.test_groups):
-            if gi == len(self.test_groups) - 1:
-                sl = slice(-length * 4, None)
-            else:
-                sl = slice(off, off + length * 4)
-            gp, gs, gr = P[sl], S[sl], R[sl]
-            self.train_logger.info("(%s average mean: psnr: %.4f, ssim: %.4f,rmse: %.4f)" % (name, mean(gp), mean(gs), mean(gr)))
-            out[name] = {"mean": (mean(gp), mean(gs), mean(gr)), "dose": []}
-            for i in range(4):
-                d = slice(int(i * length), int((i + 1) * length))
-                row = (mean(gp[d]), mean(gs[d]), mean(gr[d]))
-                out[name]["dose"].append(row)
-                self.train_logger.info("(%s\u2014\u2014\u2014\u2014dose: %2d,average: psnr: %.4f, ssim: %.4f,rmse: %.4f)" % ((name, i) + row))
-            off += length * 4
-        return out
-
-    @torch.no_grad()
-    def test(self, sample=False, last=True, FID=False, batch_size=1, n_samples=1, ensemble_seed=0, tile=None, overlap=0,
-             tile_condition="tile", tile_fuse="final", tiled_ensemble=False, *, quantiles=None, estimate="mean"):
-        """Evaluation loop of src/DADiff.py:1817-1966: init() the schedule, denoise every slice,
-        PSNR/SSIM/RMSE vs NDCT (on device), np.save each output in [0,1], per-anatomy / per-dose means.
-        `batch_size` > 1 batches independent slices (the reference uses 1).  `sample=True` keeps the
-        reference's branch that returns inputs + outputs without metrics; without `condition` the loop is the
-        reference's unconditional `self.sample` rounds (100, or up to 50000 images with FID).
-        `n_samples` > 1: every slice is denoised as an ensemble (ResidualDiffusion.sample_ensemble) under the slice seed
-        `ensemble_seed` + its dataset index; the metrics and the saved image are those of the ensemble mean, and outside
-        training the per-pixel standard deviation is saved beside it as `<name>_std.npy`.
-        `tile` (an int or (th, tw); None: whole slices, as ever): every slice is sampled as overlapping tiles
-        (ResidualDiffusion.sample_tiled with `overlap`, condition=`tile_condition` and fuse=`tile_fuse`) under the slice seed
-        `ensemble_seed` + its dataset index; the metrics and the saved image are those of the blended slice.  Ensembles of tiled samples
-        (n_samples > 1 with a tile) are opt-in: `tiled_ensemble=True` runs sample_ensemble(tile=...) under the same slice seeds and
-        scores and saves the ensemble mean and `<name>_std.npy` as above; without the switch the combination raises (the raising
-        default is pinned by tests).  last=False with a tile is not built and raises.
-        `quantiles` (keyword-only, with n_samples > 1): a sequence of levels in [0, 1]; outside training every level's map of
-        the ensemble (sample_ensemble(quantiles=...)) is saved beside the image as `<name>_qNNNN.npy`, NNNN the level in
-        per-mille (0.05: `_q0050`; levels that collide there raise), cropped like `_std`.  With at least two levels the share of
-        each slice's NDCT pixels inside [lowest level, highest level] (metrics.interval_coverage) goes to
-        `self.test_running_coverage`, and its mean is logged next to the nominal highest - lowest.
-        `estimate` (keyword-only): "mean", or "median" (n_samples > 1): the metrics and the saved image are those of the ensemble's
-        0.5 level, which joins the levels if it is not among them."""
-        if int(n_samples) < 1:
-            raise RuntimeError(f"Trainer.test: n_samples must be at least 1 (got {n_samples})")
-        if estimate not in ("mean", "median"):
-            raise RuntimeError(f"Trainer.test: estimate must be 'mean' or 'median' (got {estimate!r})")
-        if (quantiles is not None or estimate == "median") and int(n_samples) <= 1:
-            raise RuntimeError(f"Trainer.test: quantiles and estimate='median' need an ensemble, n_samples > 1 (got {n_samples})")
-        qplan = None
-        if quantiles is not None or estimate == "median":
-            levels = tuple(float(q) for q in (() if quantiles is None else quantiles))
-            n_user = len(levels)
-            if estimate == "median" and 0.5 not in levels:
-                levels = levels + (0.5,)
-            quantile_table(levels, int(n_samples))
-            quantile_suffix(levels[:n_user])
-            qplan = _QuantilePlan(levels, levels[:n_user], levels.index(0.5) if estimate == "median" else None)
-        tiled_ensemble_opt_in("Trainer.test", tile, n_samples, tiled_ensemble)
-        if tile is not None and not last:
-            raise RuntimeError("Trainer.test: tile with last=False is not built (sample_tiled returns the final image)")
-        # batch_size 1 is the reference's loop: one slice per sample() call -> the kernel set for a lone slice (DAEngine
-        # low_latency: same arithmetic, chunked scans at every level; outputs differ from a batched run by fp32
-        # summation order).  The switch is only ever turned ON here (FOUNDDIFF_LOW_LATENCY=1 stays in force for any batch
-        # size) and is restored on the way out, so later sample() calls on the same model are not affected.  Cost: the
-        # low-latency engine is a second DAEngine (its own weight copy, workspaces and graphs) next to the default one.
-        self._fresh_engines()
-        unets = [u for u in (getattr(getattr(self.ema.ema_model, "model", None), n, None) for n in ("unet0", "unet1"))
-                 if u is not None and hasattr(u, "low_latency")]
-        saved = [u.low_latency for u in unets]
-        try:
-            if batch_size == 1 and int(n_samples) == 1 and tile is None:      # (an ensemble is a batch of replicas, a tiled slice
-                for u in unets:                                           # a batch of tiles: the default kernel set)
-                    u.low_latency = True
-            tiled = None if tile is None else dict(tile=tile, overlap=overlap, tile_condition=tile_condition, tile_fuse=tile_fuse)
-            return self._test(sample, last, FID, batch_size, int(n_samples), int(ensemble_seed), tiled, qplan)
-        finally:
-            for u, v in zip(unets, saved):
-                u.low_latency = v
-
-    def _test(self, sample, last, FID, batch_size, n_samples=1, ensemble_seed=0, tiled=None, qplan=None):
-        """`tiled`: None, or the keyword arguments of sample_ensemble that make it tiled; `qplan`: None, or test()'s _QuantilePlan"""
-        from .metrics import compute_metrics
-        model = self.ema.ema_model                   # inference uses the EMA weights (src/DADiff.py:1818-1822)
-        model.init()
-        print("test start")
-        if not self.condition:
-            if FID:
-                import glob
-                self.total_n_samples = 50000
-                img_id = len(glob.glob(f"{self.results_folder}/*"))
-                n_rounds = (self.total_n_samples - img_id) // self.num_samples + 1
-            else:
-                n_rounds = 100
-            for i in range(n_rounds):
-                if FID:
-                    i = img_id
-                img_id = self.sample(i, last=last, FID=FID)
-            print("test end")
-            return None
-        self.test_running_psnr, self.test_running_ssim, self.test_running_rmse = [], [], []
-        self.test_image_names = []
-        q_names, q_cover = [], None
-        if qplan is not None:
-            self.test_running_coverage = []
-            q_names = quantile_suffix(qplan.user)
-            if len(qplan.user) >= 2:                           # the interval [lowest level, highest level] of the caller's levels
-                q_cover = (qplan.user.index(min(qplan.user)), qplan.user.index(max(qplan.user)))
-        ens_kw = dict(tiled or {}, **({} if qplan is None else {"quantiles": qplan.levels}))
-        ds = self.sample_dataset
-        for s in range(0, len(ds), batch_size):
-            idx = list(range(s, min(s + batch_size, len(ds))))
-            items = [ds[i] for i in idx]
-            y = torch.stack([it[0] for it in items]).to(self.device)
-            xs = [torch.stack([it[k] for it in items]).to(self.device) for k in range(1, len(items[0]))]
-            y_std = y_q = cover = None
-            if n_samples > 1:
-                ens = model.sample_ensemble(xs, n_samples, slice_seeds=[ensemble_seed + i for i in idx], **ens_kw)
-                y_pred, y_std = ens.mean, ens.std
-                if qplan is not None:
-                    y_q = ens.quantiles
-                    if qplan.estimate is not None:             # estimate="median": the 0.5 level is scored and saved
-                        y_pred = y_q[:, qplan.estimate]
-                    if q_cover is not None and not sample:
-                        cover = interval_coverage(y_q[:, q_cover[0]], y_q[:, q_cover[1]], y)[1]
-            elif tiled is not None:
-                outs = model.sample_tiled(xs, tiled["tile"], tiled["overlap"], slice_seeds=[ensemble_seed + i for i in idx],
-                                          condition=tiled["tile_condition"], fuse=tiled["tile_fuse"])
-                all_images_list = [y] + xs + list(outs)
-                y_pred = outs[-1]
-            elif sample:
-                all_images_list = [y] + xs + list(model.sample(xs, batch_size=len(idx)))
-                y_pred = all_images_list[-1]
-            else:
-                y_pred = list(model.sample(xs, batch_size=len(idx), last=last))[-1]
-            if not sample:
-                # src/DADiff.py:1872-1886: the metrics use the UNCROPPED prediction; crop_patch only crops what is saved
-                m = compute_metrics(y_pred, y).cpu().numpy()
-            y_save = y_pred
-            if self.crop_patch and not sample:
-                # the reference calls get_pad_size with its 1-based item counter (1826-1838, 1875): the last item would
-                # index one past the end of a 0-based table, so the index is clamped
-                pad = [tuple(ds.get_pad_size(min(i + 1, len(ds) - 1))) for i in idx]
-                if len(set(pad)) != 1:
-                    raise ValueError("crop_patch needs one pad size per batch (use batch_size=1)")
-                h, w = y_pred.shape[-2:]
-                y_save = y_pred[:, :, 0:h - pad[0][0], 0:w - pad[0][1]]
-            for j, i in enumerate(idx):
-                file_name = ds.load_name(i, sub_dir=self.sub_dir)
-                self.test_image_names.append(self.image_file_name(file_name))
-                if not sample:
-                    self.test_running_psnr.append(m[j, 0])
-                    self.test_running_ssim.append(m[j, 1])
-                    self.test_running_rmse.append(m[j, 2])
-                    print("(psnr: %.4f, ssim: %.4f,rmse:.%.4f) " % (m[j, 0], m[j, 1], m[j, 2]))
-                    if cover is not None:
-                        self.test_running_coverage.append(float(cover[j]))
-                if not getattr(self.opt, "is_train", False) and not sample:
-                    h, w = y_save.shape[-2:]
-                    np.save(self.results_folder + "/" + file_name[:-4], y_save[j].detach().cpu().numpy().reshape(h, w))
-                    if y_std is not None:                      # the spread of the ensemble, cropped like the image
-                        np.save(self.results_folder + "/" + file_name[:-4] + "_std",
-                                y_std[j, :, :h, :w].detach().cpu().numpy().reshape(h, w))
-                    for qi, suffix in enumerate(q_names):      # the caller's levels, cropped like the image
-                        np.save(self.results_folder + "/" + file_name[:-4] + suffix,
-                                y_q[j, qi, :, :h, :w].detach().cpu().numpy().reshape(h, w))
-                    print("test-save " + file_name)
-        if sample:
-            print("test end")
-            return None
-        self.test_group_means = self._log_groups()
-        self.train_logger.info("test_psnr: {:.4f}, test_ssim: {:.4f},test_rmse:{:.4f}".format(
-            np.mean(self.test_running_psnr), np.mean(self.test_running_ssim), np.mean(self.test_running_rmse)))
-        if q_cover is not None:
-            self.train_logger.info("test_coverage: {:.4f} of the NDCT pixels inside [q{:g}, q{:g}] (nominal {:.4f})".format(
-                np.mean(self.test_running_coverage), qplan.user[q_cover[0]], qplan.user[q_cover[1]],
-                qplan.user[q_cover[1]] - qplan.user[q_cover[0]]))
-        print("test end")
-        return float(np.mean(self.test_running_psnr)), float(np.mean(self.test_running_ssim)), \
-            float(np.mean(self.test_running_rmse))

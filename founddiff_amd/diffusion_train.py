@@ -49,6 +49,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import objectives
 from ._train import empty, ptr, stream, workspace
 from .data import check_batch, crop_pads, crop_pair, upload_table, window_rows
 
@@ -60,7 +61,6 @@ __all__ = ["q_sample", "residual_loss", "p_losses_fn", "p_losses", "ClipAdamEMA"
 
 CHUNK = 4096                      # elements of a parameter per workgroup (fd_opt_chunk_elems())
 _LOSS_TYPES = {"l1": 1, "l2": 2}
-_OBJECTIVES = {"pred_res": 1, "pred_noise": 1, "pred_res_noise": 2, "pred_x0_noise": 2}
 
 
 # ---- pure host code ----------------------------------------------------------------------------------------------------------------
@@ -706,6 +706,22 @@ def val_items(pred, target, loss_type, x_input=None, x_start=None):
     return items
 
 
+def _diffused(fn, imgs, t, schedule, noise, slice_seeds, step, normalize, x0_out):
+    """The preamble of p_losses_fn and ResidualDiffusion.eval_items: imgs = [x_start, x_input] or a StoreBatch, checked and put
+    through q_sample -> (x_in, the two time inputs, the targets by the names of objectives.TRAINING: "res", "noise" and, with
+    x0_out, "x0")."""
+    if isinstance(imgs, StoreBatch):
+        _check_qsample_store(fn, imgs, t, schedule, noise, slice_seeds)
+        pair = (imgs, None)
+    else:
+        if not isinstance(imgs, (list, tuple)) or len(imgs) != 2:
+            raise RuntimeError(f"{fn}: imgs must be [x_start, x_input] (condition=True without an input condition)")
+        pair = tuple(imgs)
+        _check_qsample(fn, *pair, t, schedule, noise, slice_seeds, dims=(4,))
+    x_in, x_res, noise, times, *x0 = q_sample(*pair, t, schedule, noise, slice_seeds, step, normalize, x0_out=x0_out)
+    return x_in, times, dict(zip(("res", "noise", "x0"), (x_res, noise, *x0)))
+
+
 def p_losses_fn(model_fn, imgs, t, schedule, objective="pred_res", loss_type="l1", noise=None, slice_seeds=None, step=0, scale=1.0,
                 normalize=False):
     """p_losses (src/DADiff.py:1399-1482) for condition=True, input_condition=False on a free function:
@@ -714,25 +730,13 @@ def p_losses_fn(model_fn, imgs, t, schedule, objective="pred_res", loss_type="l1
     fn = "p_losses"
     if not callable(model_fn):
         raise RuntimeError(f"{fn}: model_fn must be callable (got {type(model_fn).__name__})")
-    if objective not in _OBJECTIVES:
-        raise RuntimeError(f"{fn}: unknown objective {objective!r}")
+    objectives.check_objective(objective, RuntimeError, f"{fn}: ")
     if loss_type not in _LOSS_TYPES:
         raise RuntimeError(f"{fn}: invalid loss type {loss_type!r} ('l1' or 'l2')")
-    want_x0 = objective == "pred_x0_noise"
-    if isinstance(imgs, StoreBatch):
-        _check_qsample_store(fn, imgs, t, schedule, noise, slice_seeds)
-        x_in, x_res, noise, times, *x0 = q_sample(imgs, None, t, schedule, noise, slice_seeds, step, normalize, x0_out=want_x0)
-    else:
-        if not isinstance(imgs, (list, tuple)) or len(imgs) != 2:
-            raise RuntimeError(f"{fn}: imgs must be [x_start, x_input] (condition=True without an input condition)")
-        x_start, x_input = imgs
-        _check_qsample(fn, x_start, x_input, t, schedule, noise, slice_seeds, dims=(4,))
-        x_in, x_res, noise, times, *x0 = q_sample(x_start, x_input, t, schedule, noise, slice_seeds, step, normalize, x0_out=want_x0)
+    rows = objectives.TRAINING[objective]
+    x_in, times, targets = _diffused(fn, imgs, t, schedule, noise, slice_seeds, step, normalize, x0_out=any(r.target == "x0" for r in rows))
     model_out = model_fn(x_in, [times[0], times[1]])
-    if want_x0:
-        target = [x0[0], noise]
-    else:
-        target = {"pred_res": [x_res], "pred_noise": [noise], "pred_res_noise": [x_res, noise]}[objective]
+    target = [targets[r.target] for r in rows]
     if not isinstance(model_out, (list, tuple)) or len(model_out) != len(target):
         raise RuntimeError(f"{fn}: objective {objective!r} needs {len(target)} model output(s) (got "
                            f"{len(model_out) if isinstance(model_out, (list, tuple)) else type(model_out).__name__})")

@@ -1,10 +1,11 @@
 """This project's extensions of the reference's sampling API: ensembles (`sample_ensemble`), a slice as overlapping tiles
 (`sample_tiled`), and both at once (`sample_ensemble(tile=...)`), as a mixin of `DADiff.ResidualDiffusion`.
 
-`DADiff.py` keeps the reference-shaped API (`sample`, `_sample`, the loops, the Trainer); everything here is built on it and adds no
-loop of the samplers but the per-step fused one.  The host class gives `_sample`, `_range_checked`, `_slice_seeds`, `_keyed_noise`,
-`_x_T_into`, `_cond_rows`, `_plan`, `_plan_unets`, `_engines`, `_group_rows`, `_o01`, the `_obj_*` tables and `_anc_chunks`, and
-the units of an image as `_normalize` / `_unnormalize` ([0, 1] <-> [-1, 1]).  Three pieces are shared by every path below:
+`DADiff.py` keeps the reference-shaped API (`sample`, `_sample`, the loops; the Trainer is `trainer.py`); everything here is built
+on it and adds no loop of the samplers but the per-step fused one.  The host class gives `_sample`, `_range_checked`, `_slice_seeds`,
+`_keyed_noise`, `_x_T_into`, `_cond_rows`, `_plan` (an `objectives.SamplePlan`: its `mode` and `two_engines` are read here),
+`_plan_unets`, `_engines`, `_group_rows`, `_o01`, the `_obj_*` tables and `_anc_chunks`, and the units of an image as `_normalize` /
+`_unnormalize` ([0, 1] <-> [-1, 1]).  Three pieces are shared by every path below:
 
     TilePlan       the geometry of a tiled call on the device, built and cached whole by `_tile_plan`; every launch takes its
                    geometry arguments from `TilePlan.geometry`
@@ -340,8 +341,7 @@ class TiledSampling:
     def _fused_passes(self, B, plan):
         """The sub-batches of the B T tile rows that one engine takes at a time outside _sample: at most max_sub_batch rows,
         half of it for a two-U-Net plan."""
-        _, r0, r1, _ = self._plan()
-        return tile_passes(B, plan.my, plan.mx, max(1, self.max_sub_batch // 2 if (r0 and r1) else self.max_sub_batch))
+        return tile_passes(B, plan.my, plan.mx, max(1, self.max_sub_batch // 2 if self._plan().two_engines else self.max_sub_batch))
 
     def _tile_cond_rows(self, x_n, x_in, plan, condition):
         """The conditioning rows of the B T tile rows x_in (R,1,th,tw) gathered from the slices x_n (both in [-1, 1]), one
@@ -378,7 +378,7 @@ class TiledSampling:
         over all R rows in place on img, which also writes the slice image on the last step."""
         B = x_in.shape[0] // plan.T
         dev, s = x_in.device, _stream(x_in)
-        mode = self._plan()[0]
+        mode = self._plan().mode
         engines = self._engines()
         passes = self._fused_passes(B, plan)
         nmax = max(hi - lo for lo, hi in passes)
