@@ -14,12 +14,13 @@
 // The padded positions of odd-sized images take part in the recurrence with u = 0, a zero x_dbl row and dy = 0, as in the
 // reference's autograd through EfficientScan / EfficientMerge: their ddelta counts in ddtb and dA, their dx is dropped.
 //
-// Launches (the scheme of fd_scan_bwd.hip -- h and dL/dh recomputed from tile carries -- on the NHWC operands):
+// Launches (the scheme of fd_scan_bwd_core.h -- h and dL/dh recomputed from tile carries -- on the NHWC operands):
 //   1. carry: per (batch, direction, tile, channel split) a workgroup stages the tile's x_dbl rows and, 16 channels at a time,
 //             its u / dy pixels in LDS (coalesced 64-byte loads per pixel, stored transposed: [channel][position]); each wave
-//             walks 4 channels of a slab, lane = E consecutive positions, and leaves per (row, tile, state) the composites;
-//   2. chain: the carries over the tiles, sequentially per (row, state);
-//   3. main:  the same staging; per channel the replay of h and g, du straight into dx (NCHW), ddelta, the dxdbl row partial
+//             walks 4 channels of a slab, lane = E consecutive positions, and leaves per (row, tile, state) the composites
+//             (the core's fold and lane-0 composition);
+//   2. chain: the core's chain kernel;
+//   3. main:  the same staging; per channel the core's carry-in and replay of h and g, du straight into dx (NCHW), ddelta, the dxdbl row partial
 //             kept in registers (R + 2N values per position, summed over the channels in-lane), per (row, tile) partials of
 //             dA / ddtw / dD / ddtb; the four waves' rows are summed through LDS in wave order;
 //   4. (channel splits only) the split partials of dxdbl summed in split order;
@@ -32,7 +33,7 @@
 // sides: the forward without the layout move, the backward with the kernels' NHWC template parameter set (a second instantiation: the NCHW one
 // is the code it was, register for register) -- launch 3 sends du back through the slab
 // buffer and stores it as the slab was loaded, launch 5 adds W^T dxdbl in its lane = channel loop.
-#include "fd_train_common.h"
+#include "fd_scan_bwd_core.h"
 
 namespace {
 
@@ -53,12 +54,6 @@ __device__ __forceinline__ int cs_pix(const CsGeom &g, int k, int l, int &lrow) 
     lrow = h2 * g.W2 + w2;
     const int hh = 2 * h2 + (k & 1), ww = 2 * w2 + (k >> 1);
     return hh < g.H && ww < g.W ? hh * g.W + ww : -1;
-}
-
-__device__ __forceinline__ float cs_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // ---- 1. / 3. carry and main ---------------------------------------------------------------------------------------------
@@ -142,97 +137,40 @@ __global__ __launch_bounds__(CS_T) void cs_scan_kernel(const float *__restrict__
             for (int i = 0; i < E; ++i) {
                 const float v = dl[i];
                 dt[i] = l0 + p0 + i < g.L ? fd_softplus(v) : 0.f;     // past the end: the identity map a = 1, b = 0
-                fac[i] = v > 20.0f ? 1.f : 1.f / (1.f + __expf(-v));
+                fac[i] = sbc_softplus_grad(v);
             }
-            if constexpr (!MAIN) {
+            float gu[E], gt[E], pA[N];
+            if constexpr (MAIN) {
+                const float Dd = Ds[kd];
 #pragma unroll
-                for (int n = 0; n < N; ++n) {
-                    const float An = A[(int64_t)kd * N + n];
-                    float a[E];
-                    float Pa = 1.f, Pb = 0.f, Qb = 0.f;
+                for (int i = 0; i < E; ++i) gu[i] = Dd * yy[i], gt[i] = 0.f;
+            }
 #pragma unroll
-                    for (int i = 0; i < E; ++i) {
-                        a[i] = __expf(dt[i] * An);
-                        Pb = a[i] * Pb + dt[i] * sT[(R + n) * TP + p0 + i] * uu[i];
-                        Pa = a[i] * Pa;
-                    }
+            for (int n = 0; n < N; ++n) {
+                const float An = A[(int64_t)kd * N + n];
+                float Bv[E], Cv[E], a[E], hv[E], Pa, Pb, Qb;
 #pragma unroll
-                    for (int i = E - 1; i >= 0; --i) Qb = a[i] * (yy[i] * sT[(R + N + n) * TP + p0 + i] + Qb);
-#pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) {
-                        const float pa = __shfl_down(Pa, o, 64), pb = __shfl_down(Pb, o, 64), qb = __shfl_down(Qb, o, 64);
-                        Pb = pa * Pb + pb;
-                        Qb = Pa * qb + Qb;
-                        Pa = Pa * pa;
-                    }
+                for (int i = 0; i < E; ++i) {
+                    Bv[i] = sT[(R + n) * TP + p0 + i];
+                    Cv[i] = sT[(R + N + n) * TP + p0 + i];
+                }
+                sbc_fold(dt, An, Bv, Cv, uu, yy, a, hv, Pa, Pb, Qb);
+                const int64_t kk = ((int64_t)tile * rows + row) * N + n;
+                if constexpr (!MAIN) {
+                    sbc_compose0(Pa, Pb, Qb);
                     if (lane == 0) {
-                        const int64_t kk = ((int64_t)tile * rows + row) * N + n;
                         ws_pa[kk] = Pa;
                         ws_h[kk] = Pb;
                         ws_g[kk] = Qb;
                     }
-                }
-            } else {
-                float gu[E], gt[E], pA[N];
-                const float Dd = Ds[kd];
-#pragma unroll
-                for (int i = 0; i < E; ++i) gu[i] = Dd * yy[i], gt[i] = 0.f;
-#pragma unroll
-                for (int n = 0; n < N; ++n) {
-                    const float An = A[(int64_t)kd * N + n];
-                    float Bv[E], Cv[E], a[E], hp[E], hv[E];
-                    float Pa = 1.f, Pb = 0.f, Qb = 0.f;
-#pragma unroll
-                    for (int i = 0; i < E; ++i) {
-                        Bv[i] = sT[(R + n) * TP + p0 + i];
-                        Cv[i] = sT[(R + N + n) * TP + p0 + i];
-                        a[i] = __expf(dt[i] * An);
-                        hv[i] = dt[i] * Bv[i] * uu[i];
-                        Pb = a[i] * Pb + hv[i];
-                        Pa = a[i] * Pa;
-                    }
-#pragma unroll
-                    for (int i = E - 1; i >= 0; --i) Qb = a[i] * (yy[i] * Cv[i] + Qb);
-                    float fa = Pa, fb = Pb, ra = Pa, rb = Qb;
-#pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) {
-                        const float pa = __shfl_up(fa, o, 64), pb = __shfl_up(fb, o, 64);
-                        const float qa = __shfl_down(ra, o, 64), qb = __shfl_down(rb, o, 64);
-                        if (lane >= o) {
-                            fb = fa * pb + fb;
-                            fa = fa * pa;
-                        }
-                        if (lane + o < 64) {
-                            rb = ra * qb + rb;
-                            ra = ra * qa;
-                        }
-                    }
-                    float ea = __shfl_up(fa, 1, 64), eb = __shfl_up(fb, 1, 64);
-                    float xa = __shfl_down(ra, 1, 64), xb2 = __shfl_down(rb, 1, 64);
-                    if (lane == 0) ea = 1.f, eb = 0.f;
-                    if (lane == 63) xa = 1.f, xb2 = 0.f;
-                    const int64_t kk = ((int64_t)tile * rows + row) * N + n;
-                    float h = ea * ws_h[kk] + eb;
-#pragma unroll
-                    for (int i = 0; i < E; ++i) {
-                        hp[i] = h;
-                        h = a[i] * h + hv[i];
-                        hv[i] = h;
-                    }
-                    float X = xa * ws_g[kk] + xb2;          // a_{t+1} g_{t+1} after this lane's last position
+                } else {
+                    float h, X;
+                    sbc_carry_in(lane, Pa, Pb, Qb, ws_h[kk], ws_g[kk], h, X);
                     pA[n] = 0.f;
-#pragma unroll
-                    for (int i = E - 1; i >= 0; --i) {
-                        const float gi = yy[i] * Cv[i] + X;
-                        X = a[i] * gi;
-                        const float gdt = gi * dt[i], w = X * hp[i];       // w = g a h_{t-1}
-                        acc[R + N + n][i] += yy[i] * hv[i];
-                        acc[R + n][i] += gdt * uu[i];
-                        gu[i] += gdt * Bv[i];
-                        gt[i] += gi * Bv[i] * uu[i] + An * w;
-                        pA[n] += dt[i] * w;
-                    }
+                    sbc_replay(dt, An, Bv, Cv, uu, yy, a, hv, h, X, acc[R + n], acc[R + N + n], gu, gt, pA[n]);
                 }
+            }
+            if constexpr (MAIN) {
                 if constexpr (NHWC) {
                     // NHWC dx: du, complete here, goes back over this channel's u in the slab buffer (read by this lane alone,
                     // above) and the slab leaves as it came, 16 bytes per (pixel, 4 channels), after the channel loop
@@ -267,15 +205,15 @@ __global__ __launch_bounds__(CS_T) void cs_scan_kernel(const float *__restrict__
                 float *pp = part + ((int64_t)b * g.ntiles + tile) * (4 * (int64_t)g.D * J) + (int64_t)kd * J;
 #pragma unroll
                 for (int n = 0; n < N; ++n) {
-                    const float v = cs_wave_sum(pA[n]);
+                    const float v = wave_sum(pA[n]);
                     if (lane == 0) pp[n] = v;
                 }
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
-                    const float v = cs_wave_sum(pR[r]);
+                    const float v = wave_sum(pR[r]);
                     if (lane == 0) pp[N + r] = v;
                 }
-                const float vD = cs_wave_sum(pD), vB = cs_wave_sum(pBias);
+                const float vD = wave_sum(pD), vB = wave_sum(pBias);
                 if (lane == 0) {
                     pp[N + R] = vD;
                     pp[N + R + 1] = vB;
@@ -321,27 +259,6 @@ __global__ __launch_bounds__(CS_T) void cs_scan_kernel(const float *__restrict__
                 for (int e = 0; e < CD; ++e) ob[(int64_t)lrow * CD + e] = acc[e][i];
             }
         }
-    }
-}
-
-// ---- 2. carries: H -> h entering tile j, G -> a_{t+1} g_{t+1} entering tile j from its end ------------------------------
-__global__ __launch_bounds__(CS_T) void cs_chain_kernel(const float *__restrict__ ws_pa, float *__restrict__ ws_h,
-                                                       float *__restrict__ ws_g, int64_t RN, int ntiles) {
-    const int64_t i = (int64_t)blockIdx.x * CS_T + threadIdx.x;
-    if (i >= RN) return;
-    float h = 0.f;
-    for (int j = 0; j < ntiles; ++j) {
-        const int64_t kk = (int64_t)j * RN + i;
-        const float a = ws_pa[kk], hb = ws_h[kk];
-        ws_h[kk] = h;
-        h = a * h + hb;
-    }
-    float x = 0.f;
-    for (int j = ntiles - 1; j >= 0; --j) {
-        const int64_t kk = (int64_t)j * RN + i;
-        const float a = ws_pa[kk], gb = ws_g[kk];
-        ws_g[kk] = x;
-        x = a * x + gb;
     }
 }
 
@@ -503,6 +420,14 @@ bool cs_shape_ok(int B, int H, int W, int D, int N, int R) {
            (R == 2 || R == 4 || R == 8 || R == 16 || R == 32) && (int64_t)H * W * D * 4 < (1ll << 31);
 }
 
+// the shape check of every entry, with the entry's name in the error
+int cs_shape(const char *name, int B, int H, int W, int D, int N, int R) {
+    FD_REQUIRE(cs_shape_ok(B, H, W, D, N, R),
+               "%s: unsupported shape B=%d H=%d W=%d d_inner=%d d_state=%d dt_rank=%d (d_inner %% 64 == 0, "
+               "N in {4,8,16,32}, R in {2,4,8,16,32}, B <= 16383)", name, B, H, W, D, N, R);
+    return FD_OK;
+}
+
 template <int N, int R, bool NHWC>
 void cs_launch(const CsLayout &w, const float *xc, const float *xdbl, const float *xw, const float *dtw, const float *dtb,
                const float *A, const float *Ds, const float *dy, float *dx, float *dxw, float *ddtw, float *ddtb, float *dA,
@@ -514,7 +439,7 @@ void cs_launch(const CsLayout &w, const float *xc, const float *xdbl, const floa
     hipLaunchKernelGGL((cs_scan_kernel<N, R, false>), grid, dim3(CS_T), 0, st, xc, xdbl, dy, dtw, dtb, A, Ds, pa, hh, gg,
                        dx, nullptr, nullptr, g);
     const int64_t RN = (int64_t)g.B * 4 * g.D * N;
-    hipLaunchKernelGGL(cs_chain_kernel, dim3((unsigned)((RN + CS_T - 1) / CS_T)), dim3(CS_T), 0, st, pa, hh, gg, RN, g.ntiles);
+    scan_bwd_chain_launch(pa, hh, gg, RN, g.ntiles, st);
     hipLaunchKernelGGL((cs_scan_kernel<N, R, true, NHWC>), grid, dim3(CS_T), 0, st, xc, xdbl, dy, dtw, dtb, A, Ds, pa, hh, gg, dx,
                        g.S > 1 ? dxp : dxd, part, g);
     if (g.S > 1) {
@@ -541,9 +466,7 @@ extern "C" int64_t fd_cross_scan_bwd_ws_floats(int B, int H, int W, int D, int N
 extern "C" int fd_cross_scan_bwd_geom(int B, int H, int W, int D, int N, int R, int32_t out[8]) {
     FD_REQUIRE(out, "fd_cross_scan_bwd_geom: null pointer");
     for (int i = 0; i < 8; ++i) out[i] = 0;
-    FD_REQUIRE(cs_shape_ok(B, H, W, D, N, R),
-               "fd_cross_scan_bwd_geom: unsupported shape B=%d H=%d W=%d d_inner=%d d_state=%d dt_rank=%d (d_inner %% 64 == 0, "
-               "N in {4,8,16,32}, R in {2,4,8,16,32}, B <= 16383)", B, H, W, D, N, R);
+    if (int rc = cs_shape("fd_cross_scan_bwd_geom", B, H, W, D, N, R)) return rc;
     const CsLayout w = cs_layout(B, H, W, D, N, R);
     const CsGeom &g = w.g;
     out[0] = cs_e(g.CD);
@@ -590,9 +513,7 @@ int cs_bwd(const char *name, int nhwc, const float *xc, const float *xdbl, const
            float *ddtb, float *dA, float *dDs, float *ws, int B, int H, int W, int D, int N, int R, void *stream) {
     FD_REQUIRE(xc && xdbl && x_proj_w && dtw && dtb && A && Ds && dy && dx && dx_proj_w && ddtw && ddtb && dA && dDs && ws,
                "%s: null pointer", name);
-    FD_REQUIRE(cs_shape_ok(B, H, W, D, N, R),
-               "%s: unsupported shape B=%d H=%d W=%d d_inner=%d d_state=%d dt_rank=%d (d_inner %% 64 == 0, "
-               "N in {4,8,16,32}, R in {2,4,8,16,32}, B <= 16383)", name, B, H, W, D, N, R);
+    if (int rc = cs_shape(name, B, H, W, D, N, R)) return rc;
     FD_REQUIRE((((uintptr_t)xc | (uintptr_t)dy | (uintptr_t)ws | (nhwc ? (uintptr_t)dx : 0)) & 15) == 0,
                "%s: tensors must be 16-byte aligned", name);
     const CsLayout w = cs_layout(B, H, W, D, N, R);
@@ -619,9 +540,7 @@ extern "C" int fd_cross_scan_fwd_f32(const float *x, const float *x_proj_w, cons
                                      const float *Ds, float *xc, float *xdbl, float *y, float *ws, int B, int H, int W, int D,
                                      int N, int R, void *stream) {
     FD_REQUIRE(x && x_proj_w && dtw && dtb && A && Ds && xc && xdbl && y && ws, "fd_cross_scan_fwd_f32: null pointer");
-    FD_REQUIRE(cs_shape_ok(B, H, W, D, N, R),
-               "fd_cross_scan_fwd_f32: unsupported shape B=%d H=%d W=%d d_inner=%d d_state=%d dt_rank=%d (d_inner %% 64 == 0, "
-               "N in {4,8,16,32}, R in {2,4,8,16,32}, B <= 16383)", B, H, W, D, N, R);
+    if (int rc = cs_shape("fd_cross_scan_fwd_f32", B, H, W, D, N, R)) return rc;
     FD_REQUIRE((((uintptr_t)x | (uintptr_t)xc | (uintptr_t)xdbl | (uintptr_t)y | (uintptr_t)x_proj_w) & 15) == 0,
                "fd_cross_scan_fwd_f32: tensors must be 16-byte aligned");
     const hipStream_t st = (hipStream_t)stream;
@@ -636,9 +555,7 @@ extern "C" int fd_cross_scan_fwd_nhwc_f32(const float *xc, const float *x_proj_w
                                           const float *A, const float *Ds, float *xdbl, float *y, float *ws, int B, int H, int W,
                                           int D, int N, int R, void *stream) {
     FD_REQUIRE(xc && x_proj_w && dtw && dtb && A && Ds && xdbl && y && ws, "fd_cross_scan_fwd_nhwc_f32: null pointer");
-    FD_REQUIRE(cs_shape_ok(B, H, W, D, N, R),
-               "fd_cross_scan_fwd_nhwc_f32: unsupported shape B=%d H=%d W=%d d_inner=%d d_state=%d dt_rank=%d (d_inner %% 64 == 0, "
-               "N in {4,8,16,32}, R in {2,4,8,16,32}, B <= 16383)", B, H, W, D, N, R);
+    if (int rc = cs_shape("fd_cross_scan_fwd_nhwc_f32", B, H, W, D, N, R)) return rc;
     FD_REQUIRE((((uintptr_t)xc | (uintptr_t)xdbl | (uintptr_t)y | (uintptr_t)x_proj_w) & 15) == 0,
                "fd_cross_scan_fwd_nhwc_f32: tensors must be 16-byte aligned");
     return cs_fwd_from_xc(xc, x_proj_w, dtw, dtb, A, Ds, xdbl, y, ws, B, H, W, D, N, R, stream);

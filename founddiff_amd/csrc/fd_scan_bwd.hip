@@ -9,13 +9,13 @@
 //     ddt = sum_n g (B u + A a h_{t-1}) ddelta = ddt * sigmoid(delta + bias) (softplus, below its threshold of 20)
 //     dA[d,n] = sum_{b,t} g dt a h_{t-1}   dD[d] = sum_{b,t} dout u   ddelta_bias[d] = sum_{b,t} ddelta
 //
-// Nothing of the forward is stored: the h and g of every position are recomputed from tile carries.  A tile is one
-// wave's span, 64 lanes x 4 consecutive positions.  Four launches (plus one when the rows of a group are split):
-//   1. carry:  per (row, tile, n) the tile's composite Pa = prod a, its local end state H (from h = 0) and its local
-//              reverse composite G (the a_{t0} g_{t0} the tile hands to its predecessor, from a zero carry);
-//   2. chain:  per (row, n) a sequential pass over the tiles turns H into each tile's carry-in h and G into its carry-in g;
+// Nothing of the forward is stored: the h and g of every position are recomputed from tile carries by the shared core,
+// fd_scan_bwd_core.h.  A tile is one wave's span, 64 lanes x 4 consecutive positions.  Four launches (plus one when the rows of a
+// group are split):
+//   1. carry:  per (row, tile, n) the tile's composites (the core's fold and lane-0 composition);
+//   2. chain:  the core's chain kernel;
 //   3. main:   per (batch, group, tile, row split) a workgroup of 4 waves walks the split's rows, wave w taking every fourth,
-//              replays h forward and g backward inside the tile (wave-level scans), writes du and ddelta per row, keeps dB
+//              replays h forward and g backward inside the tile (the core's carry-in and replay), writes du and ddelta per row, keeps dB
 //              and dC of the tile in registers and sums the four waves through LDS in a fixed order; per (row, tile) partials
 //              of dA, dD and ddelta_bias go to the workspace.  Rows are split over workgroups only where (batch, group,
 //              tile) alone would leave the chip idle (the deep levels: L = 1024, up to 1024 rows per group); the splits
@@ -23,7 +23,7 @@
 //   4. params: one workgroup per channel sums the dA / dD / ddelta_bias partials over (batch, tile) in a fixed order.
 // No float atomics anywhere: two calls on the same inputs give the same bits.  States beyond NC = 4 / 8 are walked in
 // chunks of NC; du and the un-scaled ddt then accumulate in place over the chunks (same lane, same addresses).
-#include "fd_train_common.h"
+#include "fd_scan_bwd_core.h"
 
 namespace {
 
@@ -58,17 +58,11 @@ __device__ __forceinline__ void sb_dt(const float (&dl)[SB_E], float bias, int s
         float t = v, f = 1.f;
         if (softplus) {
             t = fd_softplus(v);
-            f = v > 20.0f ? 1.f : 1.f / (1.f + __expf(-v));
+            f = sbc_softplus_grad(v);
         }
         dt[i] = l0 + i < L ? t : 0.f;
         fac[i] = f;
     }
-}
-
-__device__ __forceinline__ float sb_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // ---- 1. tile composites -------------------------------------------------------------------------------------------
@@ -97,53 +91,21 @@ __global__ __launch_bounds__(SB_T) void scan_bwd_carry_kernel(const float *__res
     sb_dt(dl, dbias ? dbias[d] : 0.f, softplus, l0, L, dt, fac);
     for (int n = 0; n < N; ++n) {
         const float An = A[(int64_t)d * N + n];
-        float Bv[SB_E], Cv[SB_E], a[SB_E];
+        float Bv[SB_E], Cv[SB_E], a[SB_E], hv[SB_E], Pa, Pb, Qb;
         sb_load4(Bg + (int64_t)n * L, l0, L, vec, Bv);
         sb_load4(Cg + (int64_t)n * L, l0, L, vec, Cv);
-        float Pa = 1.f, Pb = 0.f, Qb = 0.f;
+        sbc_fold(dt, An, Bv, Cv, uu, dy, a, hv, Pa, Pb, Qb);
+        // this kernel's H has been rounded as fma(dt B, u, a H) since it was written, not as the core's fma(a, H, dt B u): kept
+        Pb = 0.f;
 #pragma unroll
-        for (int i = 0; i < SB_E; ++i) {
-            a[i] = __expf(dt[i] * An);
-            Pb = a[i] * Pb + dt[i] * Bv[i] * uu[i];
-            Pa = a[i] * Pa;
-        }
-#pragma unroll
-        for (int i = SB_E - 1; i >= 0; --i) Qb = a[i] * (dy[i] * Cv[i] + Qb);
-        // lane 0 composes lanes [0, 2o) from [0, o) and [o, 2o): forward map 1 then 2, reverse map 2 then 1
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const float pa = __shfl_down(Pa, o, 64), pb = __shfl_down(Pb, o, 64), qb = __shfl_down(Qb, o, 64);
-            Pb = pa * Pb + pb;
-            Qb = Pa * qb + Qb;
-            Pa = Pa * pa;
-        }
+        for (int i = 0; i < SB_E; ++i) Pb = __builtin_fmaf(dt[i] * Bv[i], uu[i], a[i] * Pb);
+        sbc_compose0(Pa, Pb, Qb);
         if (lane == 0) {
             const int64_t k = ((int64_t)tile * rows + row) * N + n;
             ws_pa[k] = Pa;
             ws_h[k] = Pb;
             ws_g[k] = Qb;
         }
-    }
-}
-
-// ---- 2. carries: H -> h entering tile j, G -> a_{t+1} g_{t+1} entering tile j from its end ----------------------------
-__global__ __launch_bounds__(SB_T) void scan_bwd_chain_kernel(const float *__restrict__ ws_pa, float *__restrict__ ws_h,
-                                                             float *__restrict__ ws_g, int64_t RN, int ntiles) {
-    const int64_t i = (int64_t)blockIdx.x * SB_T + threadIdx.x;
-    if (i >= RN) return;
-    float h = 0.f;
-    for (int j = 0; j < ntiles; ++j) {
-        const int64_t k = (int64_t)j * RN + i;
-        const float a = ws_pa[k], hb = ws_h[k];
-        ws_h[k] = h;
-        h = a * h + hb;
-    }
-    float x = 0.f;
-    for (int j = ntiles - 1; j >= 0; --j) {
-        const int64_t k = (int64_t)j * RN + i;
-        const float a = ws_pa[k], gb = ws_g[k];
-        ws_g[k] = x;
-        x = a * x + gb;
     }
 }
 
@@ -199,58 +161,13 @@ __global__ __launch_bounds__(SB_T) void scan_bwd_main_kernel(
                 const int n = n0 + j;
                 if (n >= N) continue;
                 const float An = A[(int64_t)d * N + n];
-                float Bv[SB_E], Cv[SB_E], a[SB_E], hp[SB_E], hv[SB_E];
+                float Bv[SB_E], Cv[SB_E], a[SB_E], hv[SB_E], Pa, Pb, Qb, h, X;
                 sb_load4(Bg + (int64_t)n * L, l0, L, vec, Bv);
                 sb_load4(Cg + (int64_t)n * L, l0, L, vec, Cv);
-                float Pa = 1.f, Pb = 0.f, Qb = 0.f;
-#pragma unroll
-                for (int i = 0; i < SB_E; ++i) {
-                    a[i] = __expf(dt[i] * An);
-                    hv[i] = dt[i] * Bv[i] * uu[i];           // b_t for now, h_t after the replay
-                    Pb = a[i] * Pb + hv[i];
-                    Pa = a[i] * Pa;
-                }
-#pragma unroll
-                for (int i = SB_E - 1; i >= 0; --i) Qb = a[i] * (dy[i] * Cv[i] + Qb);
-                // inclusive scans over the wave: forward over the lanes before, reverse over the lanes after
-                float fa = Pa, fb = Pb, ra = Pa, rb = Qb;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const float pa = __shfl_up(fa, o, 64), pb = __shfl_up(fb, o, 64);
-                    const float qa = __shfl_down(ra, o, 64), qb = __shfl_down(rb, o, 64);
-                    if (lane >= o) {
-                        fb = fa * pb + fb;
-                        fa = fa * pa;
-                    }
-                    if (lane + o < 64) {
-                        rb = ra * qb + rb;
-                        ra = ra * qa;
-                    }
-                }
-                float ea = __shfl_up(fa, 1, 64), eb = __shfl_up(fb, 1, 64);
-                float xa = __shfl_down(ra, 1, 64), xb = __shfl_down(rb, 1, 64);
-                if (lane == 0) ea = 1.f, eb = 0.f;
-                if (lane == 63) xa = 1.f, xb = 0.f;
+                sbc_fold(dt, An, Bv, Cv, uu, dy, a, hv, Pa, Pb, Qb);
                 const int64_t k = ((int64_t)tile * rows + row) * N + n;
-                float h = ea * hin[k] + eb;
-#pragma unroll
-                for (int i = 0; i < SB_E; ++i) {
-                    hp[i] = h;
-                    h = a[i] * h + hv[i];
-                    hv[i] = h;
-                }
-                float X = xa * gin[k] + xb;              // a_{t+1} g_{t+1} after this lane's last position
-#pragma unroll
-                for (int i = SB_E - 1; i >= 0; --i) {
-                    const float gi = dy[i] * Cv[i] + X;
-                    X = a[i] * gi;
-                    const float gdt = gi * dt[i], w = X * hp[i];       // w = g a h_{t-1}
-                    accC[j][i] += dy[i] * hv[i];
-                    accB[j][i] += gdt * uu[i];
-                    gu[i] += gdt * Bv[i];
-                    gt[i] += gi * Bv[i] * uu[i] + An * w;
-                    pA[j] += dt[i] * w;
-                }
+                sbc_carry_in(lane, Pa, Pb, Qb, hin[k], gin[k], h, X);
+                sbc_replay(dt, An, Bv, Cv, uu, dy, a, hv, h, X, accB[j], accC[j], gu, gt, pA[j]);
             }
             float pD = 0.f, pBias = 0.f;
             if (first)
@@ -268,15 +185,15 @@ __global__ __launch_bounds__(SB_T) void scan_bwd_main_kernel(
 #pragma unroll
             for (int j = 0; j < NC; ++j) {
                 if (n0 + j >= N) continue;
-                const float v = sb_wave_sum(pA[j]);
+                const float v = wave_sum(pA[j]);
                 if (lane == 0) part[(n0 + j) * qs + pk] = v;
             }
             if (first) {
-                const float v = sb_wave_sum(pD);
+                const float v = wave_sum(pD);
                 if (lane == 0) part[N * qs + pk] = v;
             }
             if (last) {
-                const float v = sb_wave_sum(pBias);
+                const float v = wave_sum(pBias);
                 if (lane == 0) part[(N + 1) * qs + pk] = v;
             }
         }
@@ -431,8 +348,7 @@ extern "C" int fd_selective_scan_bwd_f32(const float *u, const float *delta, con
     hipLaunchKernelGGL(scan_bwd_carry_kernel, dim3((unsigned)(rows * w.tgroups)), dim3(SB_T), 0, st, u, delta, A, B, C,
                        delta_bias, dout, delta_softplus, pa, hh, gg, KD, K, N, L, w.ntiles, rows);
     FD_LAUNCH_OK("fd_selective_scan_bwd_f32 (carry)");
-    hipLaunchKernelGGL(scan_bwd_chain_kernel, dim3((unsigned)((RN + SB_T - 1) / SB_T)), dim3(SB_T), 0, st, pa, hh, gg, RN,
-                       w.ntiles);
+    scan_bwd_chain_launch(pa, hh, gg, RN, w.ntiles, st);
     FD_LAUNCH_OK("fd_selective_scan_bwd_f32 (chain)");
     const dim3 grid((unsigned)((int64_t)batch * K * w.S * w.ntiles));
     if (w.NC == 4)
