@@ -192,6 +192,11 @@ SIGNATURES = {
     "fd_ensemble_coverage_nblk": (i32, [i64]),
     # (lo_map, its batch stride, hi_map, its stride, target, its stride, ws, count, B, n, stream)
     "fd_ensemble_coverage_f32": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, i32, i64, vp]),
+    # (src, dst, codes: device int32 [K], B, K, H, W, stream)
+    "fd_rows_orient_f32": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+    # (samples, inv_codes: device int32 [K], mean, std, ws, spread, samples_out or None, B, K, H, W, stream)
+    "fd_ensemble_orient_stats_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "fd_rows_take_f32": (i32, [vp, vp, vp, i32, i64, vp]),
     "fd_tiles_gather_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "fd_tiles_blend_f32": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     # (mode, o0, o1, x_t, x_in, par[, t_dev, slice_seeds], wy, wx, ys, xs, B, H, W, th, tw, my, mx, xs_mult4, img_out, slice_out[, T])

@@ -1,5 +1,5 @@
-"""Seeds, passes and quantile tables of an ensemble of K keyed realisations per slice (ResidualDiffusion.sample_ensemble).  Pure
-numpy, no GPU.
+"""Seeds, passes, quantile tables and orientation codes of an ensemble of K keyed realisations per slice
+(ResidualDiffusion.sample_ensemble).  Pure numpy, no GPU.
 
 A replica is an ordinary slice of the samplers with a seed of its own: x_T and the ancestral sampler's step noise are functions of
 (seed, step, pixel) alone (fd_keyed_normal), so replica k of a slice is the same image in any batch, on any rank and stream.
@@ -67,6 +67,67 @@ def quantile_suffix(levels):
     if len(set(names)) != len(names):
         raise RuntimeError(f"quantile_suffix: levels {list(levels)} collide when rounded to per-mille ({names})")
     return names
+
+
+# ---- orientation ensembles: replica k sees the slice under a flip / rot90 code and is turned back before the reduction
+ORIENTATIONS_D4 = (0, 1, 2, 3, 4, 5, 6, 7)     # the 8 elements of the dihedral group of the square
+ORIENTATIONS_FLIPS = (0, 1, 2, 3)              # the four that keep an H != W shape
+
+
+def _orient(m, code):
+    """diffusion_train.train_augment's code on a 2-D array: bit 0 flips H, bit 1 flips W, bits 2-3 are k"""
+    if code & 1:
+        m = m[::-1]
+    if code & 2:
+        m = m[:, ::-1]
+    return np.rot90(m, (code >> 2) & 3)
+
+
+def _inverse_table():
+    g = np.arange(9).reshape(3, 3)             # 9 distinct values: no two elements of the group agree on it
+    return tuple(next(c for c in range(8) if np.array_equal(_orient(_orient(g, code), c), g)) for code in range(16))
+
+
+_INVERSE = _inverse_table()
+
+
+def orientation_inverse(code):
+    """The code c' in 0..7 whose map undoes `code` (0..15): augment_source_index(c') composed with augment_source_index(code) is
+    the identity on a square.  Codes 8..15 reach the group's elements a second time and map to the inverse of theirs, so
+    orientation_inverse(orientation_inverse(c)) is c's element as a code in 0..7."""
+    if isinstance(code, bool) or not isinstance(code, (int, np.integer)) or not 0 <= int(code) <= 15:
+        raise RuntimeError(f"orientation_inverse: a code is an integer in 0..15 (got {code!r})")
+    return _INVERSE[int(code)]
+
+
+def orientation_codes(orientations, K, square):
+    """(K,) int32: replica k sees the slice under codes[k % len(codes)].  `orientations`: "d4" (ORIENTATIONS_D4; a square slice),
+    "flips" (ORIENTATIONS_FLIPS) or a non-empty sequence of codes in 0..15.  K may be smaller or larger than the set: K = 16 with
+    "d4" is every orientation under two noise seeds.  A transposing code (k odd) on a slice that is not square raises."""
+    K = int(K)
+    if K < 1:
+        raise RuntimeError(f"orientation_codes: K must be at least 1 (got {K})")
+    if isinstance(orientations, str):
+        if orientations not in ("d4", "flips"):
+            raise RuntimeError(f"orientation_codes: orientations must be 'd4', 'flips' or a sequence of codes (got {orientations!r})")
+        if orientations == "d4" and not square:
+            raise RuntimeError("orientation_codes: 'd4' turns the slice by 90 degrees and needs a square one: use 'flips'")
+        codes = ORIENTATIONS_D4 if orientations == "d4" else ORIENTATIONS_FLIPS
+    else:
+        try:
+            given = list(orientations)
+        except TypeError:
+            raise RuntimeError(f"orientation_codes: orientations must be 'd4', 'flips' or a sequence of codes (got {orientations!r})")
+        if not given:
+            raise RuntimeError("orientation_codes: an empty sequence of orientations")
+        for c in given:
+            if isinstance(c, (bool, str)) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) <= 15:
+                raise RuntimeError(f"orientation_codes: a code is an integer in 0..15 (got {c!r})")
+        codes = tuple(int(c) for c in given)
+        bad = [c for c in codes if c & 4]
+        if bad and not square:
+            raise RuntimeError(f"orientation_codes: codes {bad} transpose (k odd) and need a square slice")
+    return np.asarray([codes[k % len(codes)] for k in range(K)], dtype=np.int32)
 
 
 def ensemble_passes(B, K, rows_max):

@@ -46,7 +46,7 @@ def gather_volume(local, world, n_total=None):
 
 
 def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampler_kwargs=None, n_samples=1, tile=None,
-                  overlap=0, tile_fuse="final", tiled_ensemble=False, *, quantiles=None):
+                  overlap=0, tile_fuse="final", tiled_ensemble=False, *, quantiles=None, orientations=None):
     """Denoise a whole volume ldct (N,1,H,W in [0,1], same tensor on every rank) with `diffusion`
     (a founddiff_amd.DADiff.ResidualDiffusion living on this rank's device).  x_T noise is keyed
     by the GLOBAL slice index, and so is the ancestral sampler's per-step noise (`slice_seeds`:
@@ -61,7 +61,12 @@ def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampl
     ensemble (sample_ensemble(tile=...)) under the same seeds and returns (mean, std) as above, the same on any `world` and for
     any `batch`; without the switch the combination raises (the raising default is pinned by tests).
     `quantiles` (keyword-only, with n_samples > 1; it raises otherwise): a sequence of Q levels in [0, 1]; returns (mean, std,
-    quantiles), the third the (N,Q,1,H,W) volume of sample_ensemble(quantiles=...)'s maps, gathered like the first two."""
+    quantiles), the third the (N,Q,1,H,W) volume of sample_ensemble(quantiles=...)'s maps, gathered like the first two.
+    `orientations` (keyword-only; None: all of the above): "d4", "flips" or a sequence of flip / rot90 codes; every slice is an
+    orientation ensemble (sample_ensemble(orientations=...)) of n_samples >= 1 replicas under the same seeds; returns (mean, std)
+    as an ensemble does, at n_samples=1 too, the same on any `world` and for any `batch`.  Together with a tile it raises."""
+    if orientations is not None and tile is not None:
+        raise RuntimeError("sample_volume: orientation ensembles of tiled samples are not built")
     if quantiles is not None and int(n_samples) <= 1:
         raise RuntimeError(f"sample_volume: quantiles need an ensemble, n_samples > 1 (got {n_samples})")
     n = ldct.shape[0]
@@ -75,8 +80,10 @@ def sample_volume(diffusion, ldct, world=1, rank=0, noise_seed=0, batch=8, sampl
                 for s in range(lo, hi, batch)]
         local = torch.cat(outs, 0) if outs else ldct.new_zeros((0,) + tuple(ldct.shape[1:])).to(dev)
         return gather_volume(local, world, n)
-    if int(n_samples) > 1:
+    if int(n_samples) > 1 or orientations is not None:
         tkw = {} if tile is None else dict(tile=tile, overlap=overlap, tile_fuse=tile_fuse)
+        if orientations is not None:
+            tkw["orientations"] = orientations
         if quantiles is not None:
             tkw["quantiles"] = quantiles = tuple(float(q) for q in quantiles)
         means, stds, quants = [], [], []

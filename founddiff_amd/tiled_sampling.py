@@ -1,5 +1,6 @@
 """This project's extensions of the reference's sampling API: ensembles (`sample_ensemble`), a slice as overlapping tiles
-(`sample_tiled`), and both at once (`sample_ensemble(tile=...)`), as a mixin of `DADiff.ResidualDiffusion`.
+(`sample_tiled`), both at once (`sample_ensemble(tile=...)`), and ensembles over the orientations of the square
+(`sample_ensemble(orientations=...)`), as a mixin of `DADiff.ResidualDiffusion`.
 
 `DADiff.py` keeps the reference-shaped API (`sample`, `_sample`, the loops; the Trainer is `trainer.py`); everything here is built
 on it and adds no loop of the samplers but the per-step fused one.  The host class gives `_sample`, `_range_checked`, `_slice_seeds`,
@@ -22,7 +23,7 @@ import torch
 
 from . import _lib as L
 from .engine import _p
-from .ensemble import ensemble_passes, ensemble_seeds, quantile_table
+from .ensemble import ensemble_passes, ensemble_seeds, orientation_codes, orientation_inverse, quantile_table
 from .metrics import ensemble_quantiles, ensemble_stats
 from .tiling import tile_pair, tile_passes, tile_plan, tile_seeds, tile_weights, tiled_ensemble_seeds
 
@@ -92,7 +93,7 @@ class TiledSampling:
 
     @torch.no_grad()
     def sample_ensemble(self, x_input, n_samples, slice_seeds=None, return_samples=False, *, tile=None, overlap=0,
-                        tile_condition="tile", tile_fuse="final", quantiles=None):
+                        tile_condition="tile", tile_fuse="final", quantiles=None, orientations=None):
         """K = n_samples keyed realisations of every slice of x_input = [ldct (B,1,H,W) in [0,1]], reduced on the device: an
         EnsembleResult of the per-pixel mean and sample standard deviation over a slice's K final images (both (B,1,H,W), in the
         [0, 1] units of sample()[-1]), spread (B,) = sqrt(mean over pixels of std^2), and the images themselves (B,K,1,H,W) when
@@ -115,25 +116,48 @@ class TiledSampling:
         is then an EnsembleQuantiles, whose `quantiles` (B,Q,1,H,W) holds per pixel the levels of the slice's K final images in the
         caller's order (metrics.ensemble_quantiles: the `linear` rule, fd_ensemble_order_f32 on the K images) and whose `levels` is
         the tuple of levels; mean, std, spread and samples are what the call without `quantiles` returns, bit for bit.  On the
-        tile_fuse="final" path the K blended images are written for the order kernel and returned only under `return_samples`."""
+        tile_fuse="final" path the K blended images are written for the order kernel and returned only under `return_samples`.
+        `orientations` (keyword-only; None: all of the above, the same launches): the geometric self-ensemble.  "d4" (the 8
+        orientations of a square slice), "flips" (the four that keep an H != W shape) or a sequence of flip / rot90 codes in 0..15
+        (diffusion_train.train_augment's: bit 0 flips H, bit 1 flips W, bits 2-3 are k); replica k takes
+        ensemble.orientation_codes(orientations, K, H == W)[k], the set cycled, so K = 16 with "d4" is every orientation under
+        two noise seeds.  Replica k of slice b is then, bit for bit, U(sample([T(x[b:b+1])], batch_size=1,
+        slice_seeds=[ensemble_seeds(slice_seeds, K)[b, k]])[-1]), T its orientation and U the inverse: x_T and the step noise are
+        the replica seed's keyed stream in the ORIENTED frame.  fd_rows_orient_f32 makes the B K oriented input rows; the tower,
+        which is not equivariant, runs on oriented inputs once per slice and distinct orientation, and replicas that share one
+        share its row (fd_rows_take_f32); the passes are those above; fd_ensemble_orient_stats_f32 reads every final image back
+        through its inverse code, so mean, std, spread, `samples` and `quantiles` are in the slice's own frame with the shapes and
+        units above.  The std now also holds where the model is not equivariant.  (0,) is the plain ensemble bit for bit, and
+        K = 1 with (c,) is sample() on the oriented slice, turned back.  Nothing returned depends on B, max_sub_batch, streams or
+        the passes.  Together with `tile` it is not built and raises."""
         K = int(n_samples)
         if K < 1:
             raise RuntimeError(f"sample_ensemble: n_samples must be at least 1 (got {n_samples})")
         if self.input_condition:
             raise RuntimeError("sample_ensemble: input_condition=True is not built (one input plane per slice)")
+        if orientations is not None and tile is not None:
+            raise RuntimeError("sample_ensemble: orientation ensembles of tiled samples are not built")
         if quantiles is not None:                                        # the levels are checked before any work
             quantiles = tuple(float(q) for q in quantiles)
             quantile_table(quantiles, K)
             ens = self.sample_ensemble(x_input, K, slice_seeds, True, tile=tile, overlap=overlap, tile_condition=tile_condition,
-                                       tile_fuse=tile_fuse)
+                                       tile_fuse=tile_fuse, orientations=orientations)
             return EnsembleQuantiles(ens.mean, ens.std, ens.spread, ens.samples if return_samples else None,
                                      ensemble_quantiles(ens.samples, quantiles), quantiles)
         if tile is not None:
             return self._sample_ensemble_tiled(x_input, K, slice_seeds, return_samples, tile, overlap, tile_condition, tile_fuse)
-        x01 = list(x_input)[0].contiguous().float()
+        x01 = list(x_input)[0]
+        codes = None
+        if orientations is not None:                                     # the codes are checked before any work
+            if not torch.is_tensor(x01) or x01.dim() != 4 or x01.shape[1] != 1:
+                raise RuntimeError("sample_ensemble: x_input must be [ldct (B,1,H,W)]")
+            codes = orientation_codes(orientations, K, x01.shape[2] == x01.shape[3])
+        x01 = x01.contiguous().float()
         B = x01.shape[0]
         seeds = self._slice_seeds(slice_seeds, B, "cpu")
         rows = torch.from_numpy(ensemble_seeds(seeds.numpy(), K).reshape(-1)).to(x01.device)
+        if codes is not None:
+            return self._ensemble_oriented(x01, K, rows, codes, return_samples)
         return _ensemble_result(self._range_checked(lambda: self._ensemble_rows(x01, K, rows), "a sampled image"), return_samples)
 
     def _rows_final(self, x_rows, seeds, passes, x_T, cond=None):
@@ -162,6 +186,45 @@ class TiledSampling:
         flat = self._rows_final(x_rows, seeds, ensemble_passes(B, K, self._group_rows()),
                                 lambda sd, size: self._keyed_noise(sd, self.X_T_STEP, size), cond)
         return flat.view((B, K) + tuple(x01.shape[1:]))
+
+    def _ensemble_oriented(self, x01, K, seeds, codes, return_samples):
+        """sample_ensemble(orientations=...): see its docstring.  seeds (B K,) int64 on the device, row b K + k; codes (K,) int32 on
+        the host, replica k's orientation."""
+        B, _, H, W = x01.shape
+        dev, s = x01.device, _stream(x01)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        elem = np.asarray([orientation_inverse(orientation_inverse(c)) for c in codes])         # codes 8..15 as their 0..7 twins
+        uniq, pos = np.unique(elem, return_inverse=True)                                         # D distinct orientations
+        D = len(uniq)
+
+        def oriented_rows():
+            x_n = self._normalize(x01)
+            x_rows = self._engines()[0]._b("ens_xin", (B * K, 1, H, W), torch.float32)
+            L.call("fd_rows_orient_f32", _p(x_n), _p(x_rows), _p(up(codes)), B, K, H, W, s)
+            # the tower on the B D distinct oriented inputs (row b D + d), at most max_sub_batch at a time; replica k of slice b
+            # takes row b D + pos[k]
+            x_tow = torch.empty((B * D, 1, H, W), device=dev, dtype=torch.float32)
+            L.call("fd_rows_orient_f32", _p(x_n), _p(x_tow), _p(up(uniq)), B, D, H, W, s)
+            tower, cond = self._cond_buffers("ori_tower", B * D), self._cond_buffers("ori", B * K)
+            take = up((np.arange(B)[:, None] * D + pos[None, :]).reshape(-1))
+            for e, (pe, la), (cpe, cla) in zip(self._engines(), tower, cond):
+                for lo in range(0, B * D, self.max_sub_batch):
+                    hi = min(lo + self.max_sub_batch, B * D)
+                    e.encode_condition(x_tow[lo:hi])
+                    pe[lo:hi].copy_(e.prompt_emb)
+                    la[lo:hi].copy_(e.local_all)
+                L.call("fd_rows_take_f32", _p(pe), _p(cpe), _p(take), B * K, e.time_dim, s)
+                L.call("fd_rows_take_f32", _p(la), _p(cla), _p(take), B * K, e.loc_total, s)
+            return self._rows_final(x_rows, seeds, ensemble_passes(B, K, self._group_rows()),
+                                    lambda sd, size: self._keyed_noise(sd, self.X_T_STEP, size), cond)
+        final = self._range_checked(oriented_rows, "a sampled image")
+        nblk = L.lib().fd_ensemble_nblk(H * W)
+        mean, std = torch.empty_like(x01), torch.empty_like(x01)
+        ws, spread = torch.empty(B * nblk, device=dev), torch.empty(B, device=dev)
+        samples = torch.empty((B, K, 1, H, W), device=dev, dtype=torch.float32) if return_samples else None
+        L.call("fd_ensemble_orient_stats_f32", _p(final), _p(up([orientation_inverse(c) for c in codes])), _p(mean), _p(std), _p(ws),
+               _p(spread), None if samples is None else _p(samples), B, K, H, W, s)
+        return EnsembleResult(mean, std, spread, samples)
 
     def _sample_ensemble_tiled(self, x_input, K, slice_seeds, return_samples, tile, overlap, condition, fuse):
         """sample_ensemble(tile=...): see its docstring"""

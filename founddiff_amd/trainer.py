@@ -549,7 +549,7 @@ class Trainer(object):
 
     @torch.no_grad()
     def test(self, sample=False, last=True, FID=False, batch_size=1, n_samples=1, ensemble_seed=0, tile=None, overlap=0,
-             tile_condition="tile", tile_fuse="final", tiled_ensemble=False, *, quantiles=None, estimate="mean"):
+             tile_condition="tile", tile_fuse="final", tiled_ensemble=False, *, quantiles=None, estimate="mean", orientations=None):
         """Evaluation loop of src/DADiff.py:1817-1966: init() the schedule, denoise every slice,
         PSNR/SSIM/RMSE vs NDCT (on device), np.save each output in [0,1], per-anatomy / per-dose means.
         `batch_size` > 1 batches independent slices (the reference uses 1).  `sample=True` keeps the
@@ -570,7 +570,13 @@ class Trainer(object):
         each slice's NDCT pixels inside [lowest level, highest level] (metrics.interval_coverage) goes to
         `self.test_running_coverage`, and its mean is logged next to the nominal highest - lowest.
         `estimate` (keyword-only): "mean", or "median" (n_samples > 1): the metrics and the saved image are those of the ensemble's
-        0.5 level, which joins the levels if it is not among them."""
+        0.5 level, which joins the levels if it is not among them.
+        `orientations` (keyword-only; None: all of the above): "d4", "flips" or a sequence of flip / rot90 codes; every slice is
+        denoised as an orientation ensemble (sample_ensemble(orientations=...)) of n_samples >= 1 replicas under the same slice
+        seeds, and scored and saved as an ensemble is; with n_samples=1 it is one sample of the oriented slice, turned back.  Not
+        built together with a tile: it raises."""
+        if orientations is not None and tile is not None:
+            raise RuntimeError("Trainer.test: orientation ensembles of tiled samples are not built")
         if int(n_samples) < 1:
             raise RuntimeError(f"Trainer.test: n_samples must be at least 1 (got {n_samples})")
         if estimate not in ("mean", "median"):
@@ -598,17 +604,18 @@ class Trainer(object):
         unets = [u for u in objectives.unets_of(getattr(self.ema.ema_model, "model", None)) if hasattr(u, "low_latency")]
         saved = [u.low_latency for u in unets]
         try:
-            if batch_size == 1 and int(n_samples) == 1 and tile is None:      # (an ensemble is a batch of replicas, a tiled slice
+            if batch_size == 1 and int(n_samples) == 1 and tile is None and orientations is None:   # (an ensemble is a batch of replicas, a tiled slice
                 for u in unets:                                           # a batch of tiles: the default kernel set)
                     u.low_latency = True
             tiled = None if tile is None else dict(tile=tile, overlap=overlap, tile_condition=tile_condition, tile_fuse=tile_fuse)
-            return self._test(sample, last, FID, batch_size, int(n_samples), int(ensemble_seed), tiled, qplan)
+            return self._test(sample, last, FID, batch_size, int(n_samples), int(ensemble_seed), tiled, qplan, orientations)
         finally:
             for u, v in zip(unets, saved):
                 u.low_latency = v
 
-    def _test(self, sample, last, FID, batch_size, n_samples=1, ensemble_seed=0, tiled=None, qplan=None):
-        """`tiled`: None, or the keyword arguments of sample_ensemble that make it tiled; `qplan`: None, or test()'s _QuantilePlan"""
+    def _test(self, sample, last, FID, batch_size, n_samples=1, ensemble_seed=0, tiled=None, qplan=None, orientations=None):
+        """`tiled`: None, or the keyword arguments of sample_ensemble that make it tiled; `qplan`: None, or test()'s _QuantilePlan;
+        `orientations`: None, or sample_ensemble's, which makes every slice an ensemble at any n_samples"""
         from .metrics import compute_metrics
         model = self.ema.ema_model                   # inference uses the EMA weights (src/DADiff.py:1818-1822)
         model.init()
@@ -636,6 +643,8 @@ class Trainer(object):
             if len(qplan.user) >= 2:                           # the interval [lowest level, highest level] of the caller's levels
                 q_cover = (qplan.user.index(min(qplan.user)), qplan.user.index(max(qplan.user)))
         ens_kw = dict(tiled or {}, **({} if qplan is None else {"quantiles": qplan.levels}))
+        if orientations is not None:
+            ens_kw["orientations"] = orientations
         ds = self.sample_dataset
         for s in range(0, len(ds), batch_size):
             idx = list(range(s, min(s + batch_size, len(ds))))
@@ -643,7 +652,7 @@ class Trainer(object):
             y = torch.stack([it[0] for it in items]).to(self.device)
             xs = [torch.stack([it[k] for it in items]).to(self.device) for k in range(1, len(items[0]))]
             y_std = y_q = cover = None
-            if n_samples > 1:
+            if n_samples > 1 or orientations is not None:
                 ens = model.sample_ensemble(xs, n_samples, slice_seeds=[ensemble_seed + i for i in idx], **ens_kw)
                 y_pred, y_std = ens.mean, ens.std
                 if qplan is not None:

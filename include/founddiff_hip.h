@@ -859,6 +859,31 @@ int fd_ensemble_coverage_nblk(int64_t n);
 int fd_ensemble_coverage_f32(const float *lo_map, int64_t lo_bstride, const float *hi_map, int64_t hi_bstride, const float *target,
                              int64_t target_bstride, int *ws, int64_t *count, int B, int64_t n, void *stream);
 
+/* ---- an ensemble over the orientations of the square (fd_ensemble_orient.hip; ResidualDiffusion.sample_ensemble(orientations=...),
+ * founddiff_amd/ensemble.py) --------
+ * fp32, the same in both builds of the library.  Deterministic, no float atomics.  A code is the training augmentation's (the slice
+ * store below): bit 0 flips H, bit 1 flips W, bits 2-3 = k, out = rot90(flip_W(flip_H(m)), k); codes are DEVICE int32 arrays of K
+ * entries, one per replica.  1 <= B, K <= 65535, H, W <= 32768.
+ * fd_rows_orient_f32: src [B][H W] -> dst [B K][H W], dst[b K + k] = src[b] under codes[k]: a copy, the repeat of
+ *   fd_rows_repeat_f32 and the orientation in one launch.  The entry reads the K codes back (it waits for the stream): a code
+ *   outside 0..15, or a transposing code (bit 2) with H != W, returns an error and nothing is launched.  16-byte accesses (reversed in
+ *   registers under a W flip, through a padded LDS tile where the code transposes) when W % 4 == 0 and both pointers are 16-byte
+ *   aligned; scalar otherwise: the same bits.
+ * fd_ensemble_orient_stats_f32: samples [B][K][H W], replica k in its own orientation -> mean, std [B][H W], spread [B] and, where
+ *   samples_out ([B K][H W]) is not NULL, the K un-oriented images; replica k's pixel is read through inv_codes[k], the code of the
+ *   INVERSE of its orientation (ensemble.orientation_inverse; the low 4 bits are used, and a transposing code on H != W is read as
+ *   its non-transposing part: no argument reads outside samples).  All outputs have the bits of un-orienting every replica followed
+ *   by fd_ensemble_stats_f32(B, K, H W); mean, std and spread are the same with and without samples_out.  A slice's rows depend on K,
+ *   H, W, the codes and its own samples alone.  Between its two launches std holds the variance.  16-byte accesses when W % 4 == 0
+ *   and samples, mean, std (and samples_out, if given) are 16-byte aligned; the scalar form has the same bits.
+ *   ws: B * fd_ensemble_nblk(H W) floats.
+ * fd_rows_take_f32: dst [R][n], dst[r] = src[idx[r]] (idx DEVICE int32 [R], every entry a row of src): conditioning rows shared by
+ *   the replicas of one orientation.  fd_rows_repeat_f32's alignment rule. */
+int fd_rows_orient_f32(const float *src, float *dst, const int *codes, int B, int K, int H, int W, void *stream);
+int fd_ensemble_orient_stats_f32(const float *samples, const int *inv_codes, float *mean, float *std, float *ws, float *spread,
+                                 float *samples_out, int B, int K, int H, int W, void *stream);
+int fd_rows_take_f32(const float *src, float *dst, const int *idx, int R, int64_t n, void *stream);
+
 /* ---- a slice as overlapping tiles (fd_tiles.hip; ResidualDiffusion.sample_tiled; founddiff_amd/tiling.py) --------
  * fp32, the same in both builds of the library.  Deterministic, no atomics, no workspace.  The plan: my x mx tiles of th x tw
  * pixels at the origins ys [my], xs [mx] (int32, DEVICE memory; 0 <= ys <= H - th, 0 <= xs <= W - tw, a tile whose origin is
