@@ -192,6 +192,12 @@ SIGNATURES = {
     "fd_ensemble_coverage_nblk": (i32, [i64]),
     # (lo_map, its batch stride, hi_map, its stride, target, its stride, ws, count, B, n, stream)
     "fd_ensemble_coverage_f32": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, i32, i64, vp]),
+    "fd_interval_hist_nblk": (i32, [i64]),
+    # (center, its batch stride, lo_map, stride, hi_map, stride, target, stride, grid: device floats [G], G, floor, ws, hist, B, n, stream)
+    "fd_interval_hist_f32": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i32, f32, vp, vp, i32, i64, vp]),
+    "fd_interval_scale_nblk": (i32, [i64]),
+    # (center, its batch stride, lo_map, stride, hi_map, stride, scale, floor, lo_out, hi_out, ws, width, B, n, stream)
+    "fd_interval_scale_f32": (i32, [vp, i64, vp, i64, vp, i64, f32, f32, vp, vp, vp, vp, i32, i64, vp]),
     # (src, dst, codes: device int32 [K], B, K, H, W, stream)
     "fd_rows_orient_f32": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
     # (samples, inv_codes: device int32 [K], mean, std, ws, spread, samples_out or None, B, K, H, W, stream)

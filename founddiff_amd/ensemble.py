@@ -4,6 +4,10 @@
 A replica is an ordinary slice of the samplers with a seed of its own: x_T and the ancestral sampler's step noise are functions of
 (seed, step, pixel) alone (fd_keyed_normal), so replica k of a slice is the same image in any batch, on any rank and stream.
 """
+import math
+from fractions import Fraction
+from typing import NamedTuple, Optional
+
 import numpy as np
 
 _M64 = (1 << 64) - 1
@@ -67,6 +71,97 @@ def quantile_suffix(levels):
     if len(set(names)) != len(names):
         raise RuntimeError(f"quantile_suffix: levels {list(levels)} collide when rounded to per-mille ({names})")
     return names
+
+
+# ---- calibrated intervals: one scale for both half-widths, chosen on held-out slices so that the share of missed pixels is controlled
+class IntervalCalibration(NamedTuple):
+    """risk_control's result.  scale = grid[g], g the smallest accepted index; risk = the empirical risk R(g) of the calibration
+    slices at that scale, raw_risk = R at the largest grid value <= 1 (the unscaled interval; None if the grid has none);
+    n_slices x n_pixels is what was counted; settings: what the scale is valid for (Trainer.calibrate_intervals fills it)."""
+    scale: float
+    g: int
+    alpha: float
+    bound: str
+    delta: Optional[float]
+    n_slices: int
+    n_pixels: int
+    risk: float
+    raw_risk: Optional[float]
+    grid_max: float
+    settings: Optional[dict] = None
+
+
+def interval_grid(max_scale=16.0, n=1025):
+    """np.linspace(0, max_scale, n) as float32: the default grid of scales (an API default, not a tuned number)"""
+    return np.linspace(0, max_scale, n).astype(np.float32)
+
+
+def _exact(x):
+    """the decimal the caller wrote (0.1 is 1/10, not the double next to it): acceptance is decided in rationals"""
+    return Fraction(repr(float(x)))
+
+
+def risk_control(hist, n_pixels, grid, alpha, bound="crc", delta=None):
+    """The smallest scale of `grid` whose risk bound is at most `alpha`, from the counts of N calibration slices.
+    hist (N, G + 1) integers: metrics.interval_hist's rows, hist[i][j] pixels of slice i in bin j, every row summing to n_pixels.
+    cum[i][g] = hist[i][0] + ... + hist[i][g] pixels of slice i have a score <= grid[g]; the loss of slice i at g is
+    1 - cum[i][g] / n_pixels and the empirical risk R(g) = (N n_pixels - sum_i cum[i][g]) / (N n_pixels), formed from Python
+    integers and non-increasing in g.
+    bound="crc" (conformal risk control, Angelopoulos et al. 2022): g is accepted iff (N R(g) + 1) / (N + 1) <= alpha, decided in
+    rationals; the expected loss of a new slice exchangeable with the N is then at most alpha.  It needs 1 / (N + 1) <= alpha.
+    bound="hoeffding" (needs 0 < delta < 1; Bates et al. 2021 with Hoeffding's inequality): g is accepted iff
+    R(g) + sqrt(ln(1 / delta) / (2 N)) <= alpha; with probability at least 1 - delta over the calibration set the expected loss is at
+    most alpha.  It needs N >= ln(1 / delta) / (2 alpha^2).
+    Returns an IntervalCalibration; raises RuntimeError where no index is accepted, saying whether N is too small for the bound
+    (and which N would do) or the grid ends too early (and R at its last value)."""
+    g32 = np.asarray(grid, dtype=np.float32).reshape(-1)
+    G = int(g32.size)
+    h = np.asarray(hist)
+    if h.ndim != 2 or h.shape[0] < 1 or h.shape[1] != G + 1 or not np.issubdtype(h.dtype, np.integer):
+        raise RuntimeError(f"risk_control: hist must be an (N, G + 1) = (N, {G + 1}) integer array with N >= 1 (got shape "
+                           f"{tuple(h.shape)}, dtype {h.dtype})")
+    N, n_pixels = int(h.shape[0]), int(n_pixels)
+    rows = [[int(v) for v in r] for r in h.tolist()]
+    if n_pixels < 1 or any(min(r) < 0 or sum(r) != n_pixels for r in rows):
+        raise RuntimeError(f"risk_control: every row of hist must be non-negative and sum to n_pixels = {n_pixels}")
+    if bound not in ("crc", "hoeffding"):
+        raise RuntimeError(f"risk_control: bound must be 'crc' or 'hoeffding' (got {bound!r})")
+    if not 0 < float(alpha) < 1:
+        raise RuntimeError(f"risk_control: alpha must be in (0, 1) (got {alpha})")
+    if bound == "hoeffding":
+        if delta is None or not 0 < float(delta) < 1:
+            raise RuntimeError(f"risk_control: bound='hoeffding' needs 0 < delta < 1 (got {delta})")
+        delta = float(delta)
+    elif delta is not None:
+        raise RuntimeError("risk_control: delta belongs to bound='hoeffding' (bound='crc' takes none)")
+    alpha = float(alpha)
+    total = N * n_pixels
+    miss, covered = [], 0                                                # miss[g] = N n_pixels - sum_i cum[i][g]
+    for g in range(G):
+        covered += sum(r[g] for r in rows)
+        miss.append(total - covered)
+    if bound == "crc":
+        a = _exact(alpha)
+        ok = lambda g: Fraction(miss[g] + n_pixels, n_pixels * (N + 1)) <= a
+        feasible = Fraction(1, N + 1) <= a
+        need = int(math.ceil(1 / a - 1))
+        limit = f"conformal risk control needs 1 / (N + 1) <= alpha: N >= {need} calibration slices at alpha = {alpha}"
+    else:
+        slack = math.sqrt(math.log(1 / delta) / (2 * N))
+        ok = lambda g: miss[g] / total + slack <= alpha
+        feasible = slack <= alpha
+        need = int(math.ceil(math.log(1 / delta) / (2 * alpha * alpha)))
+        limit = (f"the Hoeffding bound needs N >= ln(1 / delta) / (2 alpha^2): N >= {need} calibration slices at alpha = {alpha}, "
+                 f"delta = {delta}")
+    star = next((g for g in range(G) if ok(g)), None)
+    if star is None:
+        if not feasible:
+            raise RuntimeError(f"risk_control: N = {N} is too small for the bound: {limit}")
+        raise RuntimeError(f"risk_control: the grid ends too early: at its last value {float(g32[-1])} the empirical risk "
+                           f"R({G - 1}) = {miss[-1] / total} is still not accepted at alpha = {alpha}: extend the grid")
+    raw = [g for g in range(G) if g32[g] <= 1]
+    return IntervalCalibration(scale=float(g32[star]), g=star, alpha=alpha, bound=bound, delta=delta, n_slices=N, n_pixels=n_pixels,
+                               risk=miss[star] / total, raw_risk=miss[raw[-1]] / total if raw else None, grid_max=float(g32[-1]))
 
 
 # ---- orientation ensembles: replica k sees the slice under a flip / rot90 code and is turned back before the reduction

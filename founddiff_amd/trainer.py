@@ -13,14 +13,64 @@ import torch
 
 from . import diffusion_train as dt
 from . import objectives
-from .ensemble import quantile_suffix, quantile_table
-from .metrics import interval_coverage
+from .ensemble import (ORIENTATIONS_D4, ORIENTATIONS_FLIPS, IntervalCalibration, interval_grid, quantile_suffix, quantile_table,
+                       risk_control)
+from .metrics import INTERVAL_FLOOR, check_interval_grid, interval_coverage, interval_hist, interval_scale
 from .schedule import load_weights
 from .tiling import tiled_ensemble_opt_in
 
 # Trainer.test's quantiles: the levels handed to sample_ensemble, the caller's among them (the first ones), the index of the
 # estimate's level or None
 _QuantilePlan = namedtuple("_QuantilePlan", ["levels", "user", "estimate"])
+_IntervalPlan = namedtuple("_IntervalPlan", ["scale", "floor", "nominal"])        # nominal: 1 - alpha of a calibration, or None
+
+
+def _ensemble_plan(fn, n_samples, quantiles, estimate, tile, tiled_ensemble, orientations):
+    """The argument checks that `fn` (Trainer.test, Trainer.calibrate_intervals) makes before any sampling, and the _QuantilePlan
+    of the call (None without levels): the levels sample_ensemble is asked for, the caller's, and the place of the 0.5 level
+    under estimate="median"."""
+    if orientations is not None and tile is not None:
+        raise RuntimeError(f"{fn}: orientation ensembles of tiled samples are not built")
+    if int(n_samples) < 1:
+        raise RuntimeError(f"{fn}: n_samples must be at least 1 (got {n_samples})")
+    if estimate not in ("mean", "median"):
+        raise RuntimeError(f"{fn}: estimate must be 'mean' or 'median' (got {estimate!r})")
+    if (quantiles is not None or estimate == "median") and int(n_samples) <= 1:
+        raise RuntimeError(f"{fn}: quantiles and estimate='median' need an ensemble, n_samples > 1 (got {n_samples})")
+    qplan = None
+    if quantiles is not None or estimate == "median":
+        levels = tuple(float(q) for q in (() if quantiles is None else quantiles))
+        n_user = len(levels)
+        if estimate == "median" and 0.5 not in levels:
+            levels = levels + (0.5,)
+        quantile_table(levels, int(n_samples))
+        quantile_suffix(levels[:n_user])
+        qplan = _QuantilePlan(levels, levels[:n_user], levels.index(0.5) if estimate == "median" else None)
+    tiled_ensemble_opt_in(fn, tile, n_samples, tiled_ensemble)
+    return qplan
+
+
+def _interval_settings(model, n_samples, levels, estimate, floor, tile, overlap, tile_condition, tile_fuse, orientations):
+    """What a calibrated scale is valid for, as JSON holds it: the ensemble, the interval, the sampler and the model's objective.
+    `model`: the diffusion model that samples (None in a check that has none: its fields are then None)."""
+    from .tiling import tile_pair
+    if orientations is None:
+        codes = None
+    elif isinstance(orientations, str):                                  # the named sets as their codes: "flips" is (0, 1, 2, 3)
+        codes = list({"d4": ORIENTATIONS_D4, "flips": ORIENTATIONS_FLIPS}.get(orientations, ())) or orientations
+    else:
+        codes = [int(c) for c in orientations]
+    steps = getattr(model, "sampling_timesteps", None)
+    return {
+        "n_samples": int(n_samples), "levels": [float(q) for q in levels], "estimate": estimate,
+        "floor": None if floor is None else float(floor),
+        "sampler": None if model is None else ("ddim" if getattr(model, "is_ddim_sampling", False) else "ancestral"),
+        "sampling_timesteps": None if steps is None else int(steps),
+        "objective": getattr(model, "objective", None),
+        "tile": None if tile is None else [int(v) for v in tile_pair("Trainer", tile, "tile")], "overlap": int(overlap) if tile is not None else 0,
+        "tile_condition": tile_condition if tile is not None else None, "tile_fuse": tile_fuse if tile is not None else None,
+        "orientations": codes,
+    }
 
 
 class _Accel:
@@ -549,7 +599,8 @@ class Trainer(object):
 
     @torch.no_grad()
     def test(self, sample=False, last=True, FID=False, batch_size=1, n_samples=1, ensemble_seed=0, tile=None, overlap=0,
-             tile_condition="tile", tile_fuse="final", tiled_ensemble=False, *, quantiles=None, estimate="mean", orientations=None):
+             tile_condition="tile", tile_fuse="final", tiled_ensemble=False, *, quantiles=None, estimate="mean", orientations=None,
+             interval_scale=None):
         """Evaluation loop of src/DADiff.py:1817-1966: init() the schedule, denoise every slice,
         PSNR/SSIM/RMSE vs NDCT (on device), np.save each output in [0,1], per-anatomy / per-dose means.
         `batch_size` > 1 batches independent slices (the reference uses 1).  `sample=True` keeps the
@@ -574,27 +625,45 @@ class Trainer(object):
         `orientations` (keyword-only; None: all of the above): "d4", "flips" or a sequence of flip / rot90 codes; every slice is
         denoised as an orientation ensemble (sample_ensemble(orientations=...)) of n_samples >= 1 replicas under the same slice
         seeds, and scored and saved as an ensemble is; with n_samples=1 it is one sample of the oriented slice, turned back.  Not
-        built together with a tile: it raises."""
-        if orientations is not None and tile is not None:
-            raise RuntimeError("Trainer.test: orientation ensembles of tiled samples are not built")
-        if int(n_samples) < 1:
-            raise RuntimeError(f"Trainer.test: n_samples must be at least 1 (got {n_samples})")
-        if estimate not in ("mean", "median"):
-            raise RuntimeError(f"Trainer.test: estimate must be 'mean' or 'median' (got {estimate!r})")
-        if (quantiles is not None or estimate == "median") and int(n_samples) <= 1:
-            raise RuntimeError(f"Trainer.test: quantiles and estimate='median' need an ensemble, n_samples > 1 (got {n_samples})")
-        qplan = None
-        if quantiles is not None or estimate == "median":
-            levels = tuple(float(q) for q in (() if quantiles is None else quantiles))
-            n_user = len(levels)
-            if estimate == "median" and 0.5 not in levels:
-                levels = levels + (0.5,)
-            quantile_table(levels, int(n_samples))
-            quantile_suffix(levels[:n_user])
-            qplan = _QuantilePlan(levels, levels[:n_user], levels.index(0.5) if estimate == "median" else None)
-        tiled_ensemble_opt_in("Trainer.test", tile, n_samples, tiled_ensemble)
+        built together with a tile: it raises.
+        `interval_scale` (keyword-only; None: all of the above, every launch, file, list and log line as it is): a number >= 0, or
+        "calibrated" for the scale of `self.interval_calibration` (calibrate_intervals / load_interval_calibration), which raises
+        if there is none or if its `settings` differ from this call's, naming the field.  It needs `quantiles` with at least two
+        levels.  Per batch the interval [lowest level, highest level] is scaled around the estimate (metrics.interval_scale) and
+        the NDCT pixels it covers are counted by the calibration's own criterion, score <= scale (bin 0 of
+        metrics.interval_hist on the one-value grid [scale]): their share per slice goes to
+        `self.test_running_coverage_calibrated`, the mean width per slice to `self.test_running_interval_width`, and outside
+        training `<name>_lo.npy` and `<name>_hi.npy` are saved beside `<name>_std.npy`, cropped the same way.  One more log line
+        gives the mean calibrated coverage, 1 - alpha when known, the mean width and that of the unscaled interval.  The `_qNNNN`
+        maps and `test_running_coverage` stay those of the raw levels.  The guarantee of a calibration holds for slices exchangeable
+        with its calibration slices: test on other patients than those calibrated on, with the same model and sampling settings."""
+        qplan = _ensemble_plan("Trainer.test", n_samples, quantiles, estimate, tile, tiled_ensemble, orientations)
         if tile is not None and not last:
             raise RuntimeError("Trainer.test: tile with last=False is not built (sample_tiled returns the final image)")
+        iplan = None
+        if interval_scale is not None:
+            if qplan is None or len(qplan.user) < 2:
+                raise RuntimeError("Trainer.test: interval_scale needs quantiles with at least two levels (the interval that is scaled)")
+            settings = _interval_settings(getattr(getattr(self, "ema", None), "ema_model", None), n_samples, qplan.user, estimate,
+                                          None, tile, overlap, tile_condition, tile_fuse, orientations)
+            if isinstance(interval_scale, str):
+                if interval_scale != "calibrated":
+                    raise RuntimeError(f"Trainer.test: interval_scale must be None, a number or 'calibrated' (got {interval_scale!r})")
+                cal = getattr(self, "interval_calibration", None)
+                if cal is None:
+                    raise RuntimeError("Trainer.test: interval_scale='calibrated' needs a calibration: call calibrate_intervals or "
+                                       "load_interval_calibration first")
+                settings["floor"] = (cal.settings or {}).get("floor")
+                for key, value in settings.items():
+                    if (cal.settings or {}).get(key) != value:
+                        raise RuntimeError(f"Trainer.test: the calibration is not valid for this call: {key} was "
+                                           f"{(cal.settings or {}).get(key)!r} when it was made and is {value!r} now")
+                iplan = _IntervalPlan(cal.scale, float(settings["floor"]), 1 - cal.alpha)
+            else:
+                if isinstance(interval_scale, bool) or not isinstance(interval_scale, (int, float, np.integer, np.floating)) or \
+                        not 0 <= float(interval_scale) < float("inf"):
+                    raise RuntimeError(f"Trainer.test: interval_scale must be None, a number >= 0 or 'calibrated' (got {interval_scale!r})")
+                iplan = _IntervalPlan(float(interval_scale), INTERVAL_FLOOR, None)
         # batch_size 1 is the reference's loop: one slice per sample() call -> the kernel set for a lone slice (DAEngine
         # low_latency: same arithmetic, chunked scans at every level; outputs differ from a batched run by fp32
         # summation order).  The switch is only ever turned ON here (FOUNDDIFF_LOW_LATENCY=1 stays in force for any batch
@@ -608,14 +677,16 @@ class Trainer(object):
                 for u in unets:                                           # a batch of tiles: the default kernel set)
                     u.low_latency = True
             tiled = None if tile is None else dict(tile=tile, overlap=overlap, tile_condition=tile_condition, tile_fuse=tile_fuse)
-            return self._test(sample, last, FID, batch_size, int(n_samples), int(ensemble_seed), tiled, qplan, orientations)
+            return self._test(sample, last, FID, batch_size, int(n_samples), int(ensemble_seed), tiled, qplan, orientations, iplan)
         finally:
             for u, v in zip(unets, saved):
                 u.low_latency = v
 
-    def _test(self, sample, last, FID, batch_size, n_samples=1, ensemble_seed=0, tiled=None, qplan=None, orientations=None):
+    def _test(self, sample, last, FID, batch_size, n_samples=1, ensemble_seed=0, tiled=None, qplan=None, orientations=None,
+              iplan=None):
         """`tiled`: None, or the keyword arguments of sample_ensemble that make it tiled; `qplan`: None, or test()'s _QuantilePlan;
-        `orientations`: None, or sample_ensemble's, which makes every slice an ensemble at any n_samples"""
+        `orientations`: None, or sample_ensemble's, which makes every slice an ensemble at any n_samples; `iplan`: None, or
+        test()'s _IntervalPlan (then qplan has at least two of the caller's levels)"""
         from .metrics import compute_metrics
         model = self.ema.ema_model                   # inference uses the EMA weights (src/DADiff.py:1818-1822)
         model.init()
@@ -642,6 +713,9 @@ class Trainer(object):
             q_names = quantile_suffix(qplan.user)
             if len(qplan.user) >= 2:                           # the interval [lowest level, highest level] of the caller's levels
                 q_cover = (qplan.user.index(min(qplan.user)), qplan.user.index(max(qplan.user)))
+        if iplan is not None:
+            self.test_running_coverage_calibrated, self.test_running_interval_width = [], []
+            raw_width = []
         ens_kw = dict(tiled or {}, **({} if qplan is None else {"quantiles": qplan.levels}))
         if orientations is not None:
             ens_kw["orientations"] = orientations
@@ -651,7 +725,7 @@ class Trainer(object):
             items = [ds[i] for i in idx]
             y = torch.stack([it[0] for it in items]).to(self.device)
             xs = [torch.stack([it[k] for it in items]).to(self.device) for k in range(1, len(items[0]))]
-            y_std = y_q = cover = None
+            y_std = y_q = cover = scaled = None
             if n_samples > 1 or orientations is not None:
                 ens = model.sample_ensemble(xs, n_samples, slice_seeds=[ensemble_seed + i for i in idx], **ens_kw)
                 y_pred, y_std = ens.mean, ens.std
@@ -661,6 +735,14 @@ class Trainer(object):
                         y_pred = y_q[:, qplan.estimate]
                     if q_cover is not None and not sample:
                         cover = interval_coverage(y_q[:, q_cover[0]], y_q[:, q_cover[1]], y)[1]
+                    if iplan is not None and not sample:
+                        # the scaled interval around the estimate, and the pixels it holds by the calibration's own criterion:
+                        # bin 0 of the one-value grid [scale] is score <= scale
+                        maps = (y_pred, y_q[:, q_cover[0]], y_q[:, q_cover[1]])
+                        lo_s, hi_s, width = interval_scale(*maps, iplan.scale, iplan.floor)
+                        inside = interval_hist(*maps, y, [iplan.scale], iplan.floor)[:, 0].cpu().numpy()
+                        scaled = (lo_s, hi_s, inside.astype("float64") / y[0].numel(), width.cpu().numpy(),
+                                  interval_scale(*maps, 1.0, iplan.floor)[2].cpu().numpy())
             elif tiled is not None:
                 outs = model.sample_tiled(xs, tiled["tile"], tiled["overlap"], slice_seeds=[ensemble_seed + i for i in idx],
                                           condition=tiled["tile_condition"], fuse=tiled["tile_fuse"])
@@ -693,6 +775,10 @@ class Trainer(object):
                     print("(psnr: %.4f, ssim: %.4f,rmse:.%.4f) " % (m[j, 0], m[j, 1], m[j, 2]))
                     if cover is not None:
                         self.test_running_coverage.append(float(cover[j]))
+                    if scaled is not None:
+                        self.test_running_coverage_calibrated.append(float(scaled[2][j]))
+                        self.test_running_interval_width.append(float(scaled[3][j]))
+                        raw_width.append(float(scaled[4][j]))
                 if not getattr(self.opt, "is_train", False) and not sample:
                     h, w = y_save.shape[-2:]
                     np.save(self.results_folder + "/" + file_name[:-4], y_save[j].detach().cpu().numpy().reshape(h, w))
@@ -702,6 +788,10 @@ class Trainer(object):
                     for qi, suffix in enumerate(q_names):      # the caller's levels, cropped like the image
                         np.save(self.results_folder + "/" + file_name[:-4] + suffix,
                                 y_q[j, qi, :, :h, :w].detach().cpu().numpy().reshape(h, w))
+                    if scaled is not None:                     # the scaled interval, cropped like the image
+                        for suffix, t in (("_lo", scaled[0]), ("_hi", scaled[1])):
+                            np.save(self.results_folder + "/" + file_name[:-4] + suffix,
+                                    t[j, :, :h, :w].detach().cpu().numpy().reshape(h, w))
                     print("test-save " + file_name)
         if sample:
             print("test end")
@@ -713,6 +803,97 @@ class Trainer(object):
             self.train_logger.info("test_coverage: {:.4f} of the NDCT pixels inside [q{:g}, q{:g}] (nominal {:.4f})".format(
                 np.mean(self.test_running_coverage), qplan.user[q_cover[0]], qplan.user[q_cover[1]],
                 qplan.user[q_cover[1]] - qplan.user[q_cover[0]]))
+        if iplan is not None:
+            self.train_logger.info("test_coverage_calibrated: {:.4f} of the NDCT pixels inside the interval scaled by {:g} ({}), "
+                                   "mean width {:.6f} (unscaled: {:.6f})".format(
+                                       np.mean(self.test_running_coverage_calibrated), iplan.scale,
+                                       "no calibration" if iplan.nominal is None else "calibrated for {:.4f}".format(iplan.nominal),
+                                       np.mean(self.test_running_interval_width), np.mean(raw_width)))
         print("test end")
         return float(np.mean(self.test_running_psnr)), float(np.mean(self.test_running_ssim)), \
             float(np.mean(self.test_running_rmse))
+
+    INTERVAL_CALIBRATION_FILE = "interval_calibration.json"
+
+    @torch.no_grad()
+    def calibrate_intervals(self, dataset=None, *, n_samples, quantiles, estimate="mean", alpha=0.1, bound="crc", delta=None,
+                            grid=None, floor=INTERVAL_FLOOR, ensemble_seed=0, batch_size=1, items=None, tile=None, overlap=0,
+                            tile_condition="tile", tile_fuse="final", tiled_ensemble=False, orientations=None):
+        """One scale for the ensemble interval of this model, chosen on held-out slices so that the share of NDCT pixels the scaled
+        interval misses is controlled (ensemble.risk_control: `alpha`, `bound` "crc" or "hoeffding" with `delta`).
+        `dataset` (None: `val_dataset`) is read as test() reads its own: item -> [ndct, ldct].  The EMA model samples every one of
+        the first `items` slices (None: all) as test(n_samples=, quantiles=, estimate=, tile..., orientations=) would, under the
+        slice seeds `ensemble_seed` + index; l and u are the lowest and the highest of the caller's levels, the centre is the
+        ensemble mean, or the 0.5 level under estimate="median".  Per batch metrics.interval_hist bins every pixel's score over
+        `grid` (None: ensemble.interval_grid()) with the half-width floor `floor`; the counts stay on the device and are read back
+        once.  Returns the IntervalCalibration, keeps it as `self.interval_calibration` (and the counts per slice, (N, G + 1), as
+        `self.interval_counts`) and, on rank 0 outside training, writes `<results_folder>/interval_calibration.json`.  Its
+        `settings` record what the scale is valid for: test(interval_scale="calibrated") refuses any other.  The guarantee is
+        for slices exchangeable with those calibrated on: adjacent slices of one patient are not independent, so calibrate on
+        patients other than those tested, and again for another model, sampler, step count or ensemble."""
+        fn = "Trainer.calibrate_intervals"
+        if quantiles is None or len(tuple(quantiles)) < 2:
+            raise RuntimeError(f"{fn}: quantiles must hold at least two levels, the interval that is scaled (got {quantiles!r})")
+        qplan = _ensemble_plan(fn, n_samples, quantiles, estimate, tile, tiled_ensemble, orientations)
+        grid = check_interval_grid(interval_grid() if grid is None else grid)
+        if not 0 < float(floor) < float("inf"):
+            raise RuntimeError(f"{fn}: floor must be positive and finite (got {floor})")
+        if not 0 < float(alpha) < 1 or bound not in ("crc", "hoeffding") or (bound == "hoeffding") != (delta is not None) or \
+                (delta is not None and not 0 < float(delta) < 1):
+            raise RuntimeError(f"{fn}: need 0 < alpha < 1 and bound 'crc', or 'hoeffding' with 0 < delta < 1 (got alpha={alpha!r} "
+                               f"bound={bound!r} delta={delta!r})")
+        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+        if not is_int(batch_size) or batch_size < 1 or not (items is None or (is_int(items) and items >= 1)):
+            raise RuntimeError(f"{fn}: batch_size must be an integer >= 1 and items None or an integer >= 1 (got {batch_size!r}, "
+                               f"{items!r})")
+        ds = dataset if dataset is not None else getattr(self, "val_dataset", None)
+        if ds is None:
+            raise RuntimeError(f"{fn}: no dataset: pass one, or construct the Trainer with val_dataset=")
+        N = len(ds) if items is None else min(int(items), len(ds))
+        if N < 1:
+            raise RuntimeError(f"{fn}: the dataset is empty")
+        self._fresh_engines()
+        model = self.ema.ema_model
+        model.init()
+        settings = _interval_settings(model, n_samples, qplan.user, estimate, floor, tile, overlap, tile_condition, tile_fuse,
+                                      orientations)
+        lo_i, hi_i = qplan.user.index(min(qplan.user)), qplan.user.index(max(qplan.user))
+        ens_kw = dict(quantiles=qplan.levels)
+        if tile is not None:
+            ens_kw.update(tile=tile, overlap=overlap, tile_condition=tile_condition, tile_fuse=tile_fuse)
+        if orientations is not None:
+            ens_kw["orientations"] = orientations
+        counts, n_pixels = [], None
+        for s in range(0, N, batch_size):
+            idx = list(range(s, min(s + batch_size, N)))
+            its = [ds[i] for i in idx]
+            y = torch.stack([it[0] for it in its]).to(self.device)
+            xs = [torch.stack([it[k] for it in its]).to(self.device) for k in range(1, len(its[0]))]
+            ens = model.sample_ensemble(xs, int(n_samples), slice_seeds=[int(ensemble_seed) + i for i in idx], **ens_kw)
+            centre = ens.mean if qplan.estimate is None else ens.quantiles[:, qplan.estimate]
+            counts.append(interval_hist(centre, ens.quantiles[:, lo_i], ens.quantiles[:, hi_i], y, grid, floor))
+            n_pixels = y[0].numel()
+        self.interval_counts = torch.cat(counts).cpu().numpy()                     # the one read-back
+        cal = risk_control(self.interval_counts, n_pixels, grid, alpha, bound, delta)._replace(settings=settings)
+        self.interval_calibration = cal
+        if self.accelerator.is_main_process and not getattr(self.opt, "is_train", False):
+            import json
+            with open(os.path.join(self.results_folder, self.INTERVAL_CALIBRATION_FILE), "w") as f:
+                json.dump(cal._asdict(), f, indent=1)
+                f.write("\n")
+        self.train_logger.info("interval_calibration: scale {:g} ({} at alpha {:g}, {} slices of {} pixels): risk {:.4f}, "
+                               "unscaled {}".format(cal.scale, cal.bound, cal.alpha, cal.n_slices, cal.n_pixels, cal.risk,
+                                                    "n/a" if cal.raw_risk is None else "{:.4f}".format(cal.raw_risk)))
+        return cal
+
+    def load_interval_calibration(self, path=None):
+        """Read an IntervalCalibration back from `path` (None: `<results_folder>/interval_calibration.json`) into
+        `self.interval_calibration`, and return it."""
+        import json
+        with open(path or os.path.join(self.results_folder, self.INTERVAL_CALIBRATION_FILE)) as f:
+            d = json.load(f)
+        missing = [k for k in IntervalCalibration._fields if k not in d]
+        if missing:
+            raise RuntimeError(f"Trainer.load_interval_calibration: the file lacks {missing}")
+        self.interval_calibration = IntervalCalibration(**{k: d[k] for k in IntervalCalibration._fields})
+        return self.interval_calibration

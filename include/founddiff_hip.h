@@ -859,6 +859,36 @@ int fd_ensemble_coverage_nblk(int64_t n);
 int fd_ensemble_coverage_f32(const float *lo_map, int64_t lo_bstride, const float *hi_map, int64_t hi_bstride, const float *target,
                              int64_t target_bstride, int *ws, int64_t *count, int B, int64_t n, void *stream);
 
+/* ---- calibrated ensemble intervals: the scale that makes [centre - scale d_lo, centre + scale d_hi] cover a target (fd_interval.hip;
+ * metrics.interval_hist, metrics.interval_scale, Trainer.calibrate_intervals, Trainer.test(interval_scale=...)) --------
+ * fp32, the same in both builds of the library.  Deterministic, no float atomics, no atomics on global memory.  Per pixel, with the
+ * centre m, the lower map l, the upper map u and floor > 0:  d_lo = fmaxf(m - l, floor),  d_hi = fmaxf(u - m, floor), each
+ * difference one fp32 rounding.  Slice b of each input map starts b * its own stride (in floats, >= 0) past the pointer, as in
+ * fd_ensemble_coverage_f32, so l and u may be rows of one [B][Q][n] tensor of quantiles.  16-byte accesses when n % 4 == 0, every map
+ * pointer is 16-byte aligned and the strides are multiples of 4; scalar otherwise: the same results.  A slice's results do not depend
+ * on B or on the other slices.  1 <= B <= 65535, 0 < n < 2^34.
+ * fd_interval_hist_f32: hist [B][G + 1] (int64).  The score of a pixel against the target y is
+ *   s = fmaxf((m - y) / d_lo, (y - m) / d_hi), each difference and each quotient one correctly rounded fp32 operation: the smallest
+ *   scale whose interval holds y.  grid: G ascending floats in DEVICE memory, 1 <= G <= 4096 (the caller vouches for the order).
+ *   hist[b][j] = the number of pixels of slice b whose bin is j; the bin is the number of grid values strictly below s, so
+ *   s == grid[g] falls in bin g.  A pixel with a NaN among m, l, u, y, or whose either quotient is NaN (inf / inf), is covered at no
+ *   scale and goes to bin G, as s = +inf does.  Every row sums to n.  Form: per-workgroup partial histograms in LDS (grid and
+ *   counters, 2 x 16 KB; lanes of a wave that share a bin are counted by ballot and added once), written to ws and added per slice
+ *   in index order by a second launch.  ws: B * fd_interval_hist_nblk(n) * (G + 1) ints (nblk 0: unsupported n).
+ * fd_interval_scale_f32: lo_out, hi_out [B][n] (dense), width [B].  lo_out = min(max(m - scale d_lo, 0), 1) and
+ *   hi_out = min(max(m + scale d_hi, 0), 1), the product and the sum two separate fp32 roundings; scale >= 0.  width[b] = the mean
+ *   over the slice's pixels of hi_out - lo_out: fp32 workgroup sums, added per slice in index order in double.  A NaN in m, l or u
+ *   makes lo_out and hi_out NaN at that pixel and at no other, and makes width[b] NaN: the mean is not taken over the rest.
+ *   ws: B * fd_interval_scale_nblk(n) floats (0: unsupported n). */
+int fd_interval_hist_nblk(int64_t n);
+int fd_interval_hist_f32(const float *center, int64_t center_bstride, const float *lo_map, int64_t lo_bstride, const float *hi_map,
+                         int64_t hi_bstride, const float *target, int64_t target_bstride, const float *grid, int G, float floor,
+                         int *ws, int64_t *hist, int B, int64_t n, void *stream);
+int fd_interval_scale_nblk(int64_t n);
+int fd_interval_scale_f32(const float *center, int64_t center_bstride, const float *lo_map, int64_t lo_bstride, const float *hi_map,
+                          int64_t hi_bstride, float scale, float floor, float *lo_out, float *hi_out, float *ws, float *width, int B,
+                          int64_t n, void *stream);
+
 /* ---- an ensemble over the orientations of the square (fd_ensemble_orient.hip; ResidualDiffusion.sample_ensemble(orientations=...),
  * founddiff_amd/ensemble.py) --------
  * fp32, the same in both builds of the library.  Deterministic, no float atomics.  A code is the training augmentation's (the slice
