@@ -379,8 +379,11 @@ class ResidualDiffusion(nn.Module, TiledSampling):
     def __init__(self, model, *, image_size, timesteps=1000, sampling_timesteps=None, loss_type="l1",
                  objective="pred_res_noise", ddim_sampling_eta=0., condition=False, sum_scale=None,
                  input_condition=False, input_condition_mask=False, test_res_or_noise="None",
-                 use_graph=True, final_fp32_steps=None):
+                 use_graph=True, final_fp32_steps=None, ssim_weight=0.0):
         super().__init__()
+        # the weight of the structural term of the training loss (diffusion_train.structural_loss; 0.0: none, the reference's
+        # loss).  A training setting like loss_type: forward, p_losses and train_step read it, a checkpoint does not hold it
+        self.ssim_weight = dt.check_ssim_weight("ResidualDiffusion", ssim_weight)
         assert not (type(self) == ResidualDiffusion and model.channels != model.out_dim)
         assert not model.random_or_learned_sinusoidal_cond
         objectives.check_objective(objective)
@@ -1301,7 +1304,7 @@ class ResidualDiffusion(nn.Module, TiledSampling):
         (Trainer(optimizer='radam') does), NotImplementedError before that."""
         fn = "ResidualDiffusion.forward"
         self._train_ready(fn)
-        model_fn, schedule, objective, loss_type = dt._diffusion_args(fn, self)
+        model_fn, schedule, objective, loss_type, ssim_weight = dt._diffusion_args(fn, self)
         if isinstance(imgs, dt.StoreBatch):
             if t is None:
                 t = torch.randint(0, self.num_timesteps, (len(imgs),), device=imgs.device).long()
@@ -1309,10 +1312,11 @@ class ResidualDiffusion(nn.Module, TiledSampling):
             raise RuntimeError(f"{fn}: imgs must be [x_start, x_input] (condition=True without an input condition)")
         elif t is None:
             t = torch.randint(0, self.num_timesteps, (imgs[0].shape[0],), device=imgs[0].device).long()
-        return dt.p_losses_fn(model_fn, imgs, t, schedule, objective, loss_type, noise, slice_seeds, step, 1.0, normalize=True)
+        return dt.p_losses_fn(model_fn, imgs, t, schedule, objective, loss_type, noise, slice_seeds, step, 1.0, normalize=True,
+                              ssim_weight=ssim_weight)
 
     @torch.no_grad()
-    def eval_items(self, imgs, t, noise=None, slice_seeds=None, step=0, precision="fp32"):
+    def eval_items(self, imgs, t, noise=None, slice_seeds=None, step=0, precision="fp32", ssim=False):
         """What forward() measures, per slice and forward-only: imgs, t, noise, slice_seeds and step as forward takes them (t is
         required) -> one (B, 2) device tensor per U-Net the objective trains, diffusion_train.val_items of its output: column 0
         the slice's loss against p_losses' target (the mean over the batch is forward()'s loss), column 1 the one-step
@@ -1321,9 +1325,11 @@ class ResidualDiffusion(nn.Module, TiledSampling):
         encode_condition, forward, val_items; unet0 gets times[0] (times[1] for 'pred_noise'), unet1 times[1].  Nothing asks for
         the trainable view or touches requires_grad, so this runs on a model that never trained, on the EMA copy and on two
         U-Nets.  precision: the engine's; 'fp32' by default, the precision training runs in, None for the model's sampling
-        precision.  The engines hold packed weights: after an optimiser step, weights_changed() comes first."""
+        precision.  The engines hold packed weights: after an optimiser step, weights_changed() comes first.
+        ssim=True: every tensor is (B, 3); column 2 is the SSIM of that one-step estimate by the definition Trainer.test reports
+        (metrics.compute_metrics, clamped map) on the pair diffusion_train.onestep_pair writes, NaN where column 1 is."""
         fn = "ResidualDiffusion.eval_items"
-        _, schedule, objective, loss_type = dt._diffusion_args(fn, self)
+        _, schedule, objective, loss_type, _ = dt._diffusion_args(fn, self)
         x_in, times, targets = dt._diffused(fn, imgs, t, schedule, noise, slice_seeds, step, True, x0_out=True)
         x_t, x_input = x_in[:, 0:1].contiguous(), x_in[:, 1:2].contiguous()
         out = []
@@ -1332,5 +1338,13 @@ class ResidualDiffusion(nn.Module, TiledSampling):
                 eng = getattr(self.model, objectives.UNET_NAMES[r.unet]).engine(precision)
                 eng.encode_condition(x_input)
                 pred = eng.forward(x_t, x_input, times[r.time])
-                out.append(dt.val_items(pred, targets[r.target], loss_type, *((x_input, targets["x0"]) if r.residual else ())))
+                items = dt.val_items(pred, targets[r.target], loss_type, *((x_input, targets["x0"]) if r.residual else ()))
+                if ssim:
+                    if r.residual:
+                        from .metrics import compute_metrics
+                        col = compute_metrics(*dt.onestep_pair(pred, x_input, targets["x0"]))[:, 1:2]
+                    else:
+                        col = torch.full_like(items[:, :1], float("nan"))
+                    items = torch.cat([items, col], 1)
+                out.append(items)
         return out

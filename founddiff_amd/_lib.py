@@ -184,6 +184,11 @@ SIGNATURES = {
     "fd_grads_rank_sum_f32": (i32, [vp, vp, vp, i32, vp, i32, i64, vp, i64, i32, i32, vp]),
     "fd_val_items_ws_floats": (i64, [i32, i64]),
     "fd_val_items_f32": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, i64, vp]),
+    "fd_ssim_loss_ws_floats": (i64, [i32, i32, i32]),
+    # (out, x_input or None, its batch stride, x_start, residual, scale, loss, items, dout, accumulate, ws, B, H, W, stream)
+    "fd_ssim_loss_f32": (i32, [vp, vp, i64, vp, i32, f64, vp, vp, vp, i32, vp, i32, i32, i32, vp]),
+    # (pred, x_input, its batch stride, x_start, est, tgt, B, npix, stream)
+    "fd_onestep_u01_f32": (i32, [vp, vp, i64, vp, vp, vp, i32, i64, vp]),
     "fd_ensemble_nblk": (i32, [i64]),
     "fd_rows_repeat_f32": (i32, [vp, vp, i32, i32, i64, vp]),
     "fd_ensemble_stats_f32": (i32, [vp, vp, vp, vp, vp, i32, i32, i64, vp]),

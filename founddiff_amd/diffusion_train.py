@@ -23,6 +23,11 @@
                                                    model output (csrc/fd_validate.hip); val_draws keys the t and the noise of a
                                                    held-out evaluation per (item, noise band), val_summary reduces the rows per
                                                    band on the host (ResidualDiffusion.eval_items, Trainer.validate)
+    structural_loss(out, x_start, x_input, ...)    1 - SSIM of the one-step estimate against x_start (the unclamped map) with its
+                                                   gradient from the same call (csrc/fd_ssim_train.hip); ssim_items the per-slice
+                                                   means; p_losses_fn(ssim_weight=w) adds it onto the loss and the gradient of the
+                                                   row that predicts the residual or x0, inside that row's one autograd node;
+                                                   onestep_pair writes the image pair validation measures SSIM on
 
 Binding for a training run:
 
@@ -57,7 +62,8 @@ __all__ = ["q_sample", "residual_loss", "p_losses_fn", "p_losses", "ClipAdamEMA"
            "adam_state_unpack", "adam_state_pack", "train_batch_indices", "train_t_and_seeds", "train_augment", "augment_source_index",
            "train_crop", "crop_source_index", "StoreBatch", "checkpoint_pack", "checkpoint_unpack", "CHUNK", "check_bands", "val_draws",
            "val_items", "val_summary", "ClipRAdamEMA", "radam_scalars", "optimizer_kind", "CHECKPOINT_KEYS", "CHECKPOINT_KEYS_2",
-           "checkpoint_pack2", "checkpoint_unpack2", "GradReducer", "ordered_sum", "dp_micro"]
+           "checkpoint_pack2", "checkpoint_unpack2", "GradReducer", "ordered_sum", "dp_micro", "structural_loss", "ssim_items", "onestep_pair",
+           "check_ssim_weight"]
 
 CHUNK = 4096                      # elements of a parameter per workgroup (fd_opt_chunk_elems())
 _LOSS_TYPES = {"l1": 1, "l2": 2}
@@ -283,20 +289,22 @@ def val_summary(items, band, n_bands):
     """The rows of val_items gathered on the host, (n, 2) = (loss, one-step MSE in [0, 1] units) with their band indices (n,),
     per band in float64: {"loss": mean loss, "mse": mean MSE, "psnr": mean of -10 log10(mse), "rmse": mean of sqrt(mse), "n": the
     item count}, lists of n_bands.  PSNR and RMSE are averaged over items, as the reference averages its per-slice metrics
-    (src/DADiff.py:1883-1886, 1952).  A band without items has n = 0 and NaN means; NaN rows (no residual output) give NaN."""
+    (src/DADiff.py:1883-1886, 1952).  A band without items has n = 0 and NaN means; NaN rows (no residual output) give NaN.
+    Rows of eval_items(ssim=True), (n, 3) with the one-step SSIM as their third column, give "ssim" too: its mean over items."""
     it, bd = np.asarray(items, dtype=np.float64), np.asarray(band)
-    if it.ndim != 2 or it.shape[1] != 2 or bd.shape != (it.shape[0],) or bd.dtype.kind not in "iu" or int(n_bands) < 1:
+    if it.ndim != 2 or it.shape[1] not in (2, 3) or bd.shape != (it.shape[0],) or bd.dtype.kind not in "iu" or int(n_bands) < 1:
         raise RuntimeError(f"val_summary: inconsistent shapes items{it.shape} band{bd.shape} (items (n, 2), band (n,) integers, "
                            f"n_bands >= 1)")
     if bd.size and (bd.min() < 0 or bd.max() >= n_bands):
         raise RuntimeError(f"val_summary: band {int(bd[(bd < 0) | (bd >= n_bands)][0])} outside [0, {int(n_bands)})")
-    out = {"loss": [], "mse": [], "psnr": [], "rmse": [], "n": []}
+    names = ("loss", "mse", "psnr", "rmse") + (("ssim",) if it.shape[1] == 3 else ())
+    out = {name: [] for name in names + ("n",)}
     mean = lambda v: float(v.sum() / v.size) if v.size else float("nan")
     for k in range(int(n_bands)):
         rows = it[bd == k]
         with np.errstate(divide="ignore", invalid="ignore"):
-            cols = (rows[:, 0], rows[:, 1], -10.0 * np.log10(rows[:, 1]), np.sqrt(rows[:, 1]))
-        for name, v in zip(("loss", "mse", "psnr", "rmse"), cols):
+            cols = (rows[:, 0], rows[:, 1], -10.0 * np.log10(rows[:, 1]), np.sqrt(rows[:, 1])) + tuple(rows[:, 2:].T)
+        for name, v in zip(names, cols):
             out[name].append(mean(v))
         out["n"].append(int(rows.shape[0]))
     return out
@@ -674,6 +682,129 @@ def residual_loss(pred, target, loss_type, scale=1.0):
     return _Loss.apply(pred, target, loss_type, scale)
 
 
+# ---- the structural term (csrc/fd_ssim_train.hip) ------------------------------------------------------------------------------------
+def check_ssim_weight(fn, w):
+    """`w` as a float: a finite number >= 0"""
+    if isinstance(w, (bool, np.bool_)) or not isinstance(w, (int, float, np.integer, np.floating)) or not np.isfinite(w) or w < 0:
+        raise RuntimeError(f"{fn}: ssim_weight must be a finite number >= 0 (got {w!r})")
+    return float(w)
+
+
+def _check_ssim(fn, out, x_start, x_input, residual, scale):
+    """as _check_loss: types and dtypes, then shapes, then devices.  Returns (B, H, W)."""
+    _check_f32(fn, (("out", out), ("x_start", x_start), ("x_input", x_input)), optional=() if residual else ("x_input",))
+    if not isinstance(scale, (int, float)):
+        raise RuntimeError(f"{fn}: scale must be a number (got {type(scale).__name__})")
+    named = (("out", out), ("x_start", x_start), ("x_input", x_input if residual else None))
+    shapes = " ".join(f"{n}{tuple(v.shape)}" for n, v in named if v is not None)
+    if out.dim() not in (3, 4) or out.numel() < 1 or (out.dim() == 4 and out.shape[1] != 1) or \
+            any(v is not None and v.shape != out.shape for _, v in named):
+        raise RuntimeError(f"{fn}: inconsistent shapes {shapes} (equal, (B, 1, H, W) or (B, H, W))")
+    B, (H, W) = out.shape[0], out.shape[-2:]
+    if H < 6 or W < 6:
+        raise RuntimeError(f"{fn}: unsupported shape {shapes} (the 11-tap window's reflect padding of 5 needs H, W >= 6)")
+    if B > 65535 or H > 32768 or W > 32768:
+        raise RuntimeError(f"{fn}: unsupported shape {shapes} (at most 65535 slices, H, W <= 32768)")
+    _check_gpu(fn, named)
+    return B, H, W
+
+
+def _slices(x, npix):
+    """(the tensor to keep alive, its batch stride in elements): x itself where its slices are dense, npix elements each, at a
+    common distance -- a channel of q_sample's x_in goes to the kernels as it lies --, else a dense copy"""
+    if x.dim() == 4:
+        x = x[:, 0]
+    if x.stride()[1:] == (x.shape[2], 1) and (x.shape[0] == 1 or x.stride(0) >= npix):
+        return x, (x.stride(0) if x.shape[0] > 1 else npix)
+    return x.contiguous(), npix
+
+
+def _ssim_launch(out, x_input, x_start, residual, scale, loss, items, dout, accumulate, dims):
+    B, H, W = dims
+    dev = out.device
+    xi, ld = _slices(x_input.detach(), H * W) if residual else (None, 0)
+    ws = workspace("fd_ssim_loss_ws_floats", dev, B, H, W)
+    L.call("fd_ssim_loss_f32", ptr(out), ptr(xi), ld, ptr(x_start), int(bool(residual)), float(scale), ptr(loss), ptr(items), ptr(dout),
+           int(bool(accumulate)), ptr(ws), B, H, W, stream(dev))
+
+
+class _RowLoss(torch.autograd.Function):
+    """One loss of one model output: loss_type None: the structural term alone (scale); else residual_loss(out, target, loss_type,
+    scale) with the structural term under scale * ssim_weight added onto its loss and its gradient in the forward.  The backward
+    is _Loss's: the saved gradient times the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, out, target, x_input, x_start, loss_type, scale, residual, ssim_weight):
+        dims = _check_ssim("structural_loss", out, x_start, x_input, residual, scale)
+        dev, B = out.device, out.shape[0]
+        of, x0 = out.contiguous(), x_start.detach().contiguous()
+        with torch.cuda.device(dev):
+            new = empty(dev)
+            loss, dout = new(1), new(out.shape)
+            if loss_type is not None:
+                npix = out.numel() // B
+                ws = workspace("fd_res_loss_ws_floats", dev, B, npix)
+                L.call("fd_res_loss_f32", ptr(of), ptr(target.contiguous()), _LOSS_TYPES[loss_type], float(scale), ptr(loss), ptr(dout),
+                       ptr(ws), B, npix, stream(dev))
+            _ssim_launch(of, x_input, x0, residual, float(scale) * float(ssim_weight), loss, None, dout, loss_type is not None, dims)
+        ctx.save_for_backward(dout)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        return _Loss.backward(ctx, dloss) + (None,) * 4
+
+
+def structural_loss(out, x_start, x_input=None, *, residual, scale=1.0):
+    """scale * (1 - mean over slices of (mean over pixels of S)), a scalar on the device: S the SSIM map of fd_metrics (11-tap
+    Gaussian, sigma 1.5, reflect padding of 5, C1 = 0.01^2, C2 = 0.03^2 in [0, 1] units) WITHOUT its clamp to [0, 1], between
+    y = (x_start + 1) / 2 and the one-step estimate p = (x_input - out + 1) / 2 of a residual output (residual=True; x_input is
+    then required) or p = (out + 1) / 2 of an x0 output; nothing is clamped.  out, x_start, x_input (B, 1, H, W) or (B, H, W) fp32
+    in [-1, 1], as q_sample returns them; H, W >= 6.  Differentiable in out alone: the gradient comes from the forward pass
+    (csrc/fd_ssim_train.hip) and the backward multiplies it by the incoming scalar, as residual_loss."""
+    fn = "structural_loss"
+    if not isinstance(residual, (bool, np.bool_)):
+        raise RuntimeError(f"{fn}: residual must be a bool (got {residual!r})")
+    if residual and x_input is None:
+        raise RuntimeError(f"{fn}: a residual output needs x_input (the estimate is x_input - out)")
+    _check_ssim(fn, out, x_start, x_input, residual, scale)
+    return _RowLoss.apply(out, None, x_input, x_start, None, scale, bool(residual), 1.0)
+
+
+def ssim_items(out, x_start, x_input=None, *, residual):
+    """(B,) on the device, without a gradient: per slice the mean of the unclamped map S of structural_loss, whose value is
+    scale * (1 - ssim_items(...).mean()).  A slice's entry does not depend on the rest of its batch."""
+    fn = "ssim_items"
+    if residual and x_input is None:
+        raise RuntimeError(f"{fn}: a residual output needs x_input (the estimate is x_input - out)")
+    dims = _check_ssim(fn, out, x_start, x_input, bool(residual), 1.0)
+    dev = out.device
+    with torch.no_grad(), torch.cuda.device(dev):
+        items = empty(dev)(dims[0])
+        _ssim_launch(out.detach().contiguous(), x_input, x_start.detach().contiguous(), bool(residual), 1.0, None, items, None, False, dims)
+    return items
+
+
+def onestep_pair(pred, x_input, x_start):
+    """(u(clamp(x_input - clamp(pred))), u(x_start)), two tensors shaped as pred in [0, 1] units, from one launch of
+    fd_onestep_u01_f32: val_items' one-step estimate as the image pair metrics.compute_metrics reads.  Nothing is differentiable."""
+    fn = "onestep_pair"
+    named = (("pred", pred), ("x_input", x_input), ("x_start", x_start))
+    _check_f32(fn, named)
+    if pred.dim() < 2 or pred.numel() < 1 or any(v.shape != pred.shape for _, v in named):
+        raise RuntimeError(f"{fn}: inconsistent shapes " + " ".join(f"{n}{tuple(v.shape)}" for n, v in named) + " (equal, (B, ...))")
+    if pred.shape[0] > 65535:
+        raise RuntimeError(f"{fn}: unsupported shape pred{tuple(pred.shape)} (at most 65535 slices)")
+    _check_gpu(fn, named)
+    dev, B = pred.device, pred.shape[0]
+    npix = pred.numel() // B
+    with torch.no_grad(), torch.cuda.device(dev):
+        pf, xi, x0 = pred.detach().contiguous(), x_input.detach().contiguous(), x_start.detach().contiguous()
+        est, tgt = torch.empty_like(pf), torch.empty_like(pf)
+        L.call("fd_onestep_u01_f32", ptr(pf), ptr(xi), npix, ptr(x0), ptr(est), ptr(tgt), B, npix, stream(dev))
+    return est, tgt
+
+
 def val_items(pred, target, loss_type, x_input=None, x_start=None):
     """(B, 2) on the device, one row per slice, from one pass of fd_val_items_f32 (csrc/fd_validate.hip) that writes no gradient:
     column 0 = the slice's mean of |pred - target| ('l1') or (pred - target)^2 ('l2'), so that its mean over the batch is
@@ -723,24 +854,48 @@ def _diffused(fn, imgs, t, schedule, noise, slice_seeds, step, normalize, x0_out
 
 
 def p_losses_fn(model_fn, imgs, t, schedule, objective="pred_res", loss_type="l1", noise=None, slice_seeds=None, step=0, scale=1.0,
-                normalize=False):
+                normalize=False, ssim_weight=0.0):
     """p_losses (src/DADiff.py:1399-1482) for condition=True, input_condition=False on a free function:
     model_fn(x_in (B, 2, H, W), [time0 (B,), time1 (B,)]) -> list of (B, 1, H, W), one per U-Net.  imgs = [x_start, x_input];
-    normalize=True takes them in [0, 1] as ResidualDiffusion.forward does.  Returns the list of losses, each times scale."""
+    normalize=True takes them in [0, 1] as ResidualDiffusion.forward does.  Returns the list of losses, each times scale.
+    ssim_weight > 0 (the reference carries a structural term on the one-step estimate commented out, src/DADiff.py:1480): the
+    loss of the row that predicts "res" or "x0" becomes residual_loss + structural_loss(scale=scale * ssim_weight), bit for bit,
+    in the loss and in the gradient, from one autograd node; a "noise" row has no term, and an objective without such a row
+    ('pred_noise') raises before anything launches.  0.0 is the path without the term: the same launches as ever."""
     fn = "p_losses"
     if not callable(model_fn):
         raise RuntimeError(f"{fn}: model_fn must be callable (got {type(model_fn).__name__})")
     objectives.check_objective(objective, RuntimeError, f"{fn}: ")
     if loss_type not in _LOSS_TYPES:
         raise RuntimeError(f"{fn}: invalid loss type {loss_type!r} ('l1' or 'l2')")
+    ssim_weight = check_ssim_weight(fn, ssim_weight)
     rows = objectives.TRAINING[objective]
-    x_in, times, targets = _diffused(fn, imgs, t, schedule, noise, slice_seeds, step, normalize, x0_out=any(r.target == "x0" for r in rows))
+    if ssim_weight > 0:
+        if not any(r.target in ("res", "x0") for r in rows):
+            raise RuntimeError(f"{fn}: ssim_weight={ssim_weight} needs an output with a one-step estimate ('res' or 'x0'); objective "
+                               f"{objective!r} predicts the noise alone")
+        first = imgs if isinstance(imgs, StoreBatch) else (imgs[0] if isinstance(imgs, (list, tuple)) and imgs else None)
+        hw = tuple(getattr(first, "shape", ()))[-2:]                     # (anything else is _diffused's to refuse)
+        if len(hw) == 2 and min(hw) < 6:
+            raise RuntimeError(f"{fn}: ssim_weight={ssim_weight} on images of {hw[0]} x {hw[1]}: the 11-tap window's reflect padding "
+                               f"of 5 needs H, W >= 6")
+    x_in, times, targets = _diffused(fn, imgs, t, schedule, noise, slice_seeds, step, normalize,
+                                     x0_out=ssim_weight > 0 or any(r.target == "x0" for r in rows))
     model_out = model_fn(x_in, [times[0], times[1]])
     target = [targets[r.target] for r in rows]
     if not isinstance(model_out, (list, tuple)) or len(model_out) != len(target):
         raise RuntimeError(f"{fn}: objective {objective!r} needs {len(target)} model output(s) (got "
                            f"{len(model_out) if isinstance(model_out, (list, tuple)) else type(model_out).__name__})")
-    return [residual_loss(o, tg, loss_type, scale) for o, tg in zip(model_out, target)]
+    if ssim_weight == 0:
+        return [residual_loss(o, tg, loss_type, scale) for o, tg in zip(model_out, target)]
+    losses = []
+    for r, o, tg in zip(rows, model_out, target):
+        if r.target == "noise":
+            losses.append(residual_loss(o, tg, loss_type, scale))
+            continue
+        _check_loss("residual_loss", o, tg, loss_type, scale)
+        losses.append(_RowLoss.apply(o, tg, x_in[:, 1:2] if r.residual else None, targets["x0"], loss_type, scale, r.residual, ssim_weight))
+    return losses
 
 
 def _diffusion_args(fn, self):
@@ -754,15 +909,17 @@ def _diffusion_args(fn, self):
     schedule = dict(alphas_cumsum=self.alphas_cumsum, betas_cumsum=self.betas_cumsum)
     if schedule["alphas_cumsum"].numel() != self.num_timesteps:
         raise RuntimeError(f"{fn}: alphas_cumsum has {schedule['alphas_cumsum'].numel()} rows, num_timesteps is {self.num_timesteps}")
-    return (lambda x, times: self.model(x, times)), schedule, self.objective, self.loss_type
+    ssim_weight = check_ssim_weight(fn, getattr(self, "ssim_weight", 0.0))       # reference-shaped objects have none: no term
+    return (lambda x, times: self.model(x, times)), schedule, self.objective, self.loss_type, ssim_weight
 
 
 def p_losses(self, imgs, t, noise=None, slice_seeds=None, step=0, scale=1.0):
     """ResidualDiffusion.p_losses on the reference's attribute names (objective, loss_type, condition, num_timesteps, model, the
     alphas_cumsum / betas_cumsum buffers): imgs = [x_start, x_input] already normalised, as ResidualDiffusion.forward hands them
     over.  self_condition and input_condition raise before anything launches."""
-    model_fn, schedule, objective, loss_type = _diffusion_args("p_losses", self)
-    return p_losses_fn(model_fn, imgs, t, schedule, objective, loss_type, noise, slice_seeds, step, scale, normalize=False)
+    model_fn, schedule, objective, loss_type, ssim_weight = _diffusion_args("p_losses", self)
+    return p_losses_fn(model_fn, imgs, t, schedule, objective, loss_type, noise, slice_seeds, step, scale, normalize=False,
+                       ssim_weight=ssim_weight)
 
 
 # ---- the optimiser -----------------------------------------------------------------------------------------------------------------
@@ -1064,7 +1221,7 @@ class GradReducer:
 
 # ---- the loop body -----------------------------------------------------------------------------------------------------------------
 def train_step(diffusion_or_fn, opt, batch, t=None, noise=None, slice_seeds=None, step=0, schedule=None, objective="pred_res",
-               loss_type="l1", normalize=True, reducer=None):
+               loss_type="l1", normalize=True, reducer=None, ssim_weight=0.0):
     """The loop body of Trainer.train (src/DADiff.py:1689-1725) for one accumulation group: p_losses -> backward per loss ->
     opt.step() (clip, Adam, zero_grad, EMA).  diffusion_or_fn: an object with the reference's ResidualDiffusion attributes, or a
     free model_fn(x_in, [time0, time1]) -> list of (B, 1, H, W) together with schedule, objective and loss_type.  batch:
@@ -1077,7 +1234,8 @@ def train_step(diffusion_or_fn, opt, batch, t=None, noise=None, slice_seeds=None
     rank's micro-batches of the step, the a-th of them being global micro-batch a W + rank of len(batch) W (dp_micro: the caller
     draws its indices, t and seeds under that number); each loss is scaled by one over len(batch) W, and reducer.reduce() follows
     every micro-batch's backward passes.  The gradients opt.step() sees and the losses returned are then, on every rank, bit for
-    bit those of a single process over all len(batch) W micro-batches."""
+    bit those of a single process over all len(batch) W micro-batches.
+    ssim_weight: p_losses_fn's, for a free model_fn; a diffusion object brings its own attribute (0.0 where it has none)."""
     fn = "train_step"
     if not isinstance(opt, ClipAdamEMA):
         raise RuntimeError(f"{fn}: opt must be a ClipAdamEMA (got {type(opt).__name__})")
@@ -1091,7 +1249,7 @@ def train_step(diffusion_or_fn, opt, batch, t=None, noise=None, slice_seeds=None
     many = not single and isinstance(batch[0], (list, tuple, StoreBatch))
     groups = list(batch) if many or single else [batch]
     if hasattr(diffusion_or_fn, "alphas_cumsum") and hasattr(diffusion_or_fn, "objective"):
-        model_fn, schedule, objective, loss_type = _diffusion_args(fn, diffusion_or_fn)
+        model_fn, schedule, objective, loss_type, ssim_weight = _diffusion_args(fn, diffusion_or_fn)
     elif callable(diffusion_or_fn):
         model_fn = diffusion_or_fn
     else:
@@ -1116,7 +1274,7 @@ def train_step(diffusion_or_fn, opt, batch, t=None, noise=None, slice_seeds=None
                 raise RuntimeError(f"{fn}: a micro-batch must be [x_start, x_input] on the GPU (there is no CPU path)")
             ti = torch.randint(0, ac.numel(), (imgs[0].shape[0],), device=imgs[0].device).long()
         losses = p_losses_fn(model_fn, imgs, ti, schedule, objective, loss_type, pick(noise, i), pick(slice_seeds, i), step,
-                             1.0 / n_micro, normalize)
+                             1.0 / n_micro, normalize, ssim_weight=ssim_weight)
         for loss in losses:
             loss.backward()
         det = [loss.detach() for loss in losses]

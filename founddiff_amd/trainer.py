@@ -150,7 +150,13 @@ class Trainer(object):
     train_batch_size over the ranks; here a rank keeps train_batch_size and A W counts the micro-batches of a step.  Rank 0's
     model and buffers are broadcast once when training is set up; a DeviceSliceStore is held whole by every rank; previews,
     validate() and the checkpoint file are rank 0's, save() is called by every rank and ends in a barrier and check_replicas(),
-    load(for_training=True) runs on every rank.  `split_batches` itself is ignored, as before."""
+    load(for_training=True) runs on every rank.  `split_batches` itself is ignored, as before.
+    `ssim_weight` (None: the model's own attribute, 0.0 unless it was constructed otherwise; a finite number >= 0 sets it on the
+    model and on the EMA copy) adds diffusion_train.structural_loss, 1 - SSIM of the one-step estimate under that weight, to the
+    loss of the U-Net that predicts the residual or x0, inside that loss's autograd node: augment, crop_size (a crop below 6
+    raises), optimizer='radam' and data_parallel see a loss and a gradient as before.  Like loss_type it is a setting of the
+    constructor and no part of a checkpoint: a resumed run must be given it again.  `val_ssim=True` makes validate() report the
+    one-step SSIM ("ssim", per U-Net and band) beside the PSNR and RMSE; best-checkpoint selection does not read it."""
 
     def __init__(self, opt, diffusion_model, folder=None, *, train_batch_size=16, gradient_accumulate_every=1,
                  augment_flip=True, train_lr=1e-4, train_num_steps=100000, ema_update_every=10, ema_decay=0.995,
@@ -159,7 +165,7 @@ class Trainer(object):
                  equalizeHist=False, crop_patch=False, generation=False, num_unet=2, checkpoint_folder=None,
                  is_train=True, train_logger=None, dataset=None, device=None, train_dataset=None, seed=0, log_every=100,
                  augment=False, crop_size=None, optimizer=None, radam_betas=(0.9, 0.999), val_crop_size=None, data_parallel=False,
-                 process_group=None, val_dataset=None,
+                 process_group=None, ssim_weight=None, val_ssim=False, val_dataset=None,
                  validate_every=0, val_bands=(0, 250, 500, 750, 1000), val_items=None, val_seed=0, val_batch_size=8, keep_best=False):
         import logging
         import os as _os
@@ -219,6 +225,13 @@ class Trainer(object):
         self.accelerator = _Accel(self.device, process_group, self.data_parallel)
         self.model = diffusion_model.to(self.device)
         self.ema = _EMAView(self.model)      # inference uses the EMA weights (src/DADiff.py:1818-1822)
+        self.ssim_weight, self.val_ssim = None, bool(val_ssim)
+        if ssim_weight is not None:          # a constructor setting like loss_type: on the model (and on the EMA copy, made of it)
+            self.ssim_weight = dt.check_ssim_weight("Trainer", ssim_weight)
+            if self.ssim_weight > 0 and self.crop_size is not None and min(self.crop_size) < 6:
+                raise RuntimeError(f"Trainer: ssim_weight={self.ssim_weight} with crop_size {self.crop_size[0]} x {self.crop_size[1]}: the "
+                                   "structural term's 11-tap window (reflect padding of 5) needs crops of at least 6 x 6")
+            self.model.ssim_weight = self.ssim_weight
         self.sample_dataset = dataset if dataset is not None else folder
         self.train_logger = train_logger or logging.getLogger("founddiff_amd")
         self.step = 0
@@ -306,6 +319,8 @@ class Trainer(object):
                 dif.weights_changed()
             if self.ema.ema_model is dif:
                 self.ema = _EMAView(dif.clone())
+            if self.ssim_weight is not None:
+                self.ema.ema_model.ssim_weight = self.ssim_weight
             eparams = list(self.ema.ema_model.parameters())
             cls, betas = (dt.ClipRAdamEMA, self.radam_betas) if self.optimizer == "radam" else (dt.ClipAdamEMA, self.adam_betas)
             self.opt0 = cls([params[i] for i in index], [eparams[i] for i in index], lr=self.train_lr, betas=betas, max_norm=1.0,
@@ -462,7 +477,8 @@ class Trainer(object):
         Every item is evaluated once per noise band of val_bands, at the t and with the
         noise diffusion_train.val_draws keys by (val_seed, item, band), in batches of val_batch_size (item, band) pairs through
         diffusion_train.StoreBatch and ResidualDiffusion.eval_items on the `precision` engine; a host dataset goes to the device
-        once, at the first call.  Returns {"step", "bands", "loss", "psnr", "rmse", "n"}: loss, psnr and rmse are lists per
+        once, at the first call.  With val_ssim the dict has "ssim" too, shaped as psnr: the SSIM of the same one-step estimate by
+        the definition test() reports.  Returns {"step", "bands", "loss", "psnr", "rmse", "n"}: loss, psnr and rmse are lists per
         U-Net, then per band, of diffusion_train.val_summary's means (psnr and rmse of the one-step denoising error, NaN for an
         output that is no residual), n the items per band; the dict is appended to val_log and logged, one line per band and
         one over all bands.  Deterministic: the numbers depend on the weights alone, not on the step, the training seed or
@@ -491,22 +507,27 @@ class Trainer(object):
             else:                                             # the centred window: CropToFixed(Center=True), origin (n - c) // 2
                 win = np.tile(np.array([[(store.H - crop[0]) // 2, (store.W - crop[1]) // 2]], dtype=np.int64), (len(item[sl]), 1))
                 batch = dt.StoreBatch(store, item[sl], None, win, crop)
-            rows.append(ema.eval_items(batch, t[sl], slice_seeds=seeds[sl], precision=precision))
+            kw = {"ssim": True} if self.val_ssim else {}              # off: the call a model without the keyword has always got
+            rows.append(ema.eval_items(batch, t[sl], slice_seeds=seeds[sl], precision=precision, **kw))
         nb = len(self.val_bands) - 1
         per_unet = [torch.cat([r[u] for r in rows]).cpu().numpy() for u in range(len(rows[0]))]      # the one synchronisation
         sums = [dt.val_summary(v, band, nb) for v in per_unet]
         res = {"step": self.step, "bands": list(self.val_bands), "loss": [s["loss"] for s in sums], "psnr": [s["psnr"] for s in sums],
                "rmse": [s["rmse"] for s in sums], "n": sums[0]["n"]}
+        if self.val_ssim:
+            res["ssim"] = [s["ssim"] for s in sums]
         self.val_log.append(res)
         info = self.train_logger.info
         for u, s in enumerate(sums):
             for k in range(nb):
-                info("Iters: [%d/%d], unet%d t in [%d, %d): val_loss: %.6f, val_psnr: %.4f, val_rmse: %.6f (%d items)" % (
+                extra = ", val_ssim: %.6f" % s["ssim"][k] if self.val_ssim else ""
+                info("Iters: [%d/%d], unet%d t in [%d, %d): val_loss: %.6f, val_psnr: %.4f, val_rmse: %.6f%s (%d items)" % (
                     self.step, self.train_num_steps, u, self.val_bands[k], self.val_bands[k + 1], s["loss"][k], s["psnr"][k],
-                    s["rmse"][k], s["n"][k]))
+                    s["rmse"][k], extra, s["n"][k]))
             tot = dt.val_summary(per_unet[u], np.zeros(len(band), dtype=np.int64), 1)
-            info("Iters: [%d/%d], unet%d val_loss: %.6f, val_psnr: %.4f, val_rmse: %.6f" % (
-                self.step, self.train_num_steps, u, tot["loss"][0], tot["psnr"][0], tot["rmse"][0]))
+            info("Iters: [%d/%d], unet%d val_loss: %.6f, val_psnr: %.4f, val_rmse: %.6f%s" % (
+                self.step, self.train_num_steps, u, tot["loss"][0], tot["psnr"][0], tot["rmse"][0],
+                ", val_ssim: %.6f" % tot["ssim"][0] if self.val_ssim else ""))
         return res
 
     @staticmethod

@@ -822,6 +822,29 @@ int64_t fd_val_items_ws_floats(int B, int64_t npix);
 int fd_val_items_f32(const float *pred, const float *target, const float *x_input, const float *x_start, int loss_type,
                      float *items, float *ws, int B, int64_t npix, void *stream);
 
+/* ---- the structural term of the training loss (fd_ssim_train.hip; diffusion_train.structural_loss) ------------
+ * fp32, the same in both builds of the library.  Deterministic, no atomics; a slice's numbers do not depend on its batch.
+ * With y = (x_start + 1) / 2 and p = (x_input - out + 1) / 2 (`residual`) or (out + 1) / 2 (an x0 output), nothing clamped, and
+ * w* the window of fd_metrics (11-tap Gaussian, sigma 1.5, normalised, separable, reflect padding of 5), C1 = 0.01^2, C2 = 0.03^2:
+ *   mp = w*p, my = w*y, vp = w*p^2 - mp^2, vy = w*y^2 - my^2, c = w*(p y) - mp my
+ *   a1 = 2 mp my + C1, a2 = 2 c + C2, b1 = mp^2 + my^2 + C1, b2 = vp + vy + C2, S = a1 a2 / (b1 b2)      (NOT clamped to [0, 1])
+ *   items[b] = mean_i S;  term = (float)(scale (1 - mean_b items[b])), the mean in double over the fp32 items
+ *   dS/dmu = 2 my a2 / (b1 b2) - S 2 mp / b1, dS/dv = -S / b2, dS/dc = 2 a1 / (b1 b2), A = dS/dmu - 2 mp dS/dv - my dS/dc
+ *   d term / d p = -scale (W^T A + 2 p W^T dS/dv + y W^T dS/dc) / N, N = B H W, W^T the adjoint of the reflect-padded filter;
+ *   d term / d out = -1/2 of it (`residual`) or +1/2 of it, rounded to fp32
+ * fd_ssim_loss_f32: out, x_start [B][H][W]; x_input: slice b at x_input + b x_input_bstride (null and 0 without `residual`).
+ *   loss (may be null): loss[0] = term, or loss[0] + term with `accumulate` (one fp32 add).  items (may be null): [B].
+ *   dout (may be null: no backward pass runs) [B][H][W] = the gradient, or dout + it with `accumulate` (one fp32 add, no fma).
+ *   ws: fd_ssim_loss_ws_floats(B, H, W) floats (0: unsupported shape).  Errors before anything launches: H or W < 6, B > 65535.
+ * fd_onestep_u01_f32: est = u(clamp(x_input - clamp(pred, -1, 1), -1, 1)), tgt = u(x_start), u(v) = clamp((v + 1) / 2, 0, 1),
+ *   all [B][npix] (x_input strided as above): the one-step estimate of fd_val_items_f32 as the image pair fd_metrics reads. */
+int64_t fd_ssim_loss_ws_floats(int B, int H, int W);
+int fd_ssim_loss_f32(const float *out, const float *x_input, int64_t x_input_bstride, const float *x_start, int residual,
+                     double scale, float *loss, float *items, float *dout, int accumulate, float *ws, int B, int H, int W,
+                     void *stream);
+int fd_onestep_u01_f32(const float *pred, const float *x_input, int64_t x_input_bstride, const float *x_start, float *est,
+                       float *tgt, int B, int64_t npix, void *stream);
+
 /* ---- an ensemble of K keyed realisations per slice (fd_ensemble.hip; ResidualDiffusion.sample_ensemble) --------
  * fp32, the same in both builds of the library.  Deterministic, no float atomics.
  * fd_rows_repeat_f32: dst [B K][n], dst[b K + k] = src[b] (src [B][n]): a slice's input plane or conditioning row, once per
