@@ -88,6 +88,8 @@ SIGNATURES = {
     "fd_pw_dw3x3_gram_f32": (i32, [vp, i32, i32, i32, vp, vp, f32, vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, vp]),
     "fd_pw_dw3x3_proj_f32_ok": (i32, [i32, i32, i32, i32]),
     "fd_pw_dw3x3_proj_f32": (i32, [vp, i32, i32, i32, vp, vp, f32, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+    # (entry, dtype_opts, Cin, Cdw, Cz, C, B, H, W, out[9])
+    "fd_pw_dw3x3_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
     "fd_dwconv_gram_ok": (i32, [i32, i32, i32, i32]),
     "fd_dwconv_gram_nblk": (i32, [i32, i32]),
     "fd_dwconv_gram": (i32, [i32, vp, i32, i32, vp, vp, i32, i32, i32, vp]),
@@ -241,6 +243,25 @@ def rows_form(lib, p):
     if not lib.fd_gemm_rows_form(C.byref(p), form):
         return None
     return dict(zip(ROWS_FORM_FIELDS, (int(v) for v in form)))
+
+
+# fd_pw_dw3x3_plan: the entry points (FD_PWDW_*), the kernels (FD_PWDW_K_*) and the answer's field order (include/founddiff_hip.h)
+PWDW_ENTRIES = ("fd_pw_dw3x3", "fd_pw_dw3x3_proj", "fd_pw_dw3x3_gram", "fd_dwconv_gram", "fd_pw_dw3x3_f32", "fd_pw_dw3x3_gram_f32",
+                "fd_pw_dw3x3_proj_f32")
+PWDW_KERNELS = ("pwdw_kernel<64>", "pwdw_kernel<128>", "pwdw_kernel<64, PROJ>", "pwdw_gram_kernel", "dwconv_gram_kernel",
+                "pwdw32_kernel<DW, 16>", "pwdw32_kernel<GRAM, 8>", "pwdw32_kernel<PROJ, 8>")
+PWDW_PLAN_FIELDS = ("kernel", "TW", "ntiles", "tpw", "gx", "gy", "gz", "wgroups", "chunks")
+
+
+def pwdw_plan(lib, entry, dtype_opts, Cin=0, Cdw=0, Cz=0, C_=0, B=1, H=0, W=0):
+    """the launch plan of one entry point of the fused LN -> 1x1 -> depthwise 3x3 family as a dict (`kernel` as its name), or None
+    where the matching _ok query refuses (host only).  entry: a name of PWDW_ENTRIES"""
+    out = (i32 * len(PWDW_PLAN_FIELDS))()
+    if not lib.fd_pw_dw3x3_plan(PWDW_ENTRIES.index(entry), dtype_opts, Cin, Cdw, Cz, C_, B, H, W, out):
+        return None
+    d = dict(zip(PWDW_PLAN_FIELDS, (int(v) for v in out)))
+    d["kernel"] = PWDW_KERNELS[d["kernel"]]
+    return d
 
 
 class FoundDiffHipError(RuntimeError):

@@ -346,3 +346,18 @@ struct fd_rows_plan {
     int zre;        // 0: none; 1: gemm_rows_zre_kernel<4, 256, true>; 2: gemm_rows_zre_kernel<8, 512, false>; 3: gemm_rows32_zre_kernel<256>
 };
 #define FD_ROWS_FORM_FIELDS 10
+
+// What the fused LN -> 1x1 -> depthwise 3x3 family launches (fd_pwdw.hip, fd_pwdw32.hip): decided in ONE place per file (pwdw_plan /
+// fd_pwdw32_plan), launched from it, and reported by fd_pw_dw3x3_plan in this field order (include/founddiff_hip.h).
+struct fd_pwdw_plan {
+    int kernel;     // FD_PWDW_K_*: which of the eight compiled kernels
+    int TW;         // tile width in pixels (tiles are 8 rows high)
+    int ntiles;     // tiles per image
+    int tpw;        // consecutive tiles per workgroup
+    int gx, gy, gz; // the grid: gx = cdiv(ntiles, tpw) workgroups per image (and per head pair of fd_dwconv_gram)
+    int wgroups;    // 32-row groups of 1x1 weights a tile consumes (0: no 1x1)
+    int chunks;     // depthwise chunks per tile (64 channels; 32 in the fp32-storage kernels)
+};
+#define FD_PWDW_PLAN_FIELDS 9
+// fd_pwdw32.hip: the plan of the fp32-storage entries (FD_PWDW_F32 / _GRAM_F32 / _PROJ_F32); NULL when served, else what refuses
+const char *fd_pwdw32_plan(int entry, int dtype_opts, int Cin, int Cdw, int B, int H, int W, fd_pwdw_plan *pl);

@@ -818,15 +818,115 @@ __global__ __launch_bounds__(256, 3) void dwconv_gram_kernel(const DwGramParams 
 
 }  // namespace
 
-extern "C" int fd_pw_dw3x3_ok(int dtype_opts, int Cin, int Cdw, int Cz, int H, int W) {
+// ---------------------------------------------------------------------------------------------------------------
+// The launch plan: which kernel, how many tiles per workgroup, which grid -- decided here for the four 16-bit entry points (the
+// fp32-storage ones: fd_pwdw32_plan), launched from it, reported by fd_pw_dw3x3_plan.  NULL when the shape is served, else what
+// refuses it.
+
+// the shapes pwdw_kernel<64 | 128> takes
+static const char *pwdw_refuses(int dtype_opts, int Cin, int Cdw, int Cz, int H, int W) {
     // `dtype | FD_OPT_LOW_LATENCY`: the kernel set for ONE slice keeps the C = 128 block on row-GEMM + depthwise (the fused
     // 128-channel form has two workgroups per CU and too few tiles for a lone slice: 155 -> 153 ms per 50-step slice)
-    const int dtype = dtype_opts & 0xff;
     const bool no128 = fd_dev(FD_DEV_NO_PWDW128);        // development switch
     const int minpix = fd_dev(FD_DEV_PWDW_MINPIX);    // development
-    const bool c64 = Cin == 64 && Cdw <= 192, c128 = Cin == 128 && Cdw <= 256 && Cz <= 256 && !no128 && !(dtype_opts & FD_OPT_LOW_LATENCY);
-    return dtype == FD_BF16 && (c64 || c128) && Cdw > 0 && Cdw % 64 == 0 && Cz >= 0 && Cz % 32 == 0 && H % PT_H == 0 &&
-           W % PT_W == 0 && (int64_t)H * W >= minpix && (int64_t)H * W * 256 < (1ll << 31);   // 32-bit element offsets
+    if ((dtype_opts & 0xff) != FD_BF16) return "dtype is not the 16-bit type";
+    if (Cin == 64) {
+        if (Cdw > 192) return "Cdw > 192 at Cin = 64";
+    } else if (Cin == 128) {
+        if (Cdw > 256 || Cz > 256) return "Cdw or Cz > 256 at Cin = 128";
+        if (no128) return "Cin = 128 switched off";
+        if (dtype_opts & FD_OPT_LOW_LATENCY) return "Cin = 128 is not in the low-latency kernel set";
+    } else {
+        return "Cin is not 64 or 128";
+    }
+    if (Cdw <= 0 || Cdw % 64) return "Cdw is no positive multiple of 64";
+    if (Cz < 0 || Cz % 32) return "Cz is no multiple of 32";
+    if (H % PT_H) return "H % 8";
+    if (W % PT_W) return "W % 16";
+    if ((int64_t)H * W < minpix) return "fewer than 32768 px";
+    if ((int64_t)H * W * 256 >= (1ll << 31)) return "H * W * 256 >= 2^31 (32-bit element offsets)";
+    return nullptr;
+}
+
+// tiles per workgroup of the Gram-fused qkv kernel: a constant of the kernel set (the order of the partial sums, hence
+// the result, must not depend on the batch): 8 in the throughput set (round 4: -0.3 % per batch-8 forward against 4;
+// 16: +0.6 %), 4 under FD_OPT_LOW_LATENCY (one slice: 8 leaves 256 workgroups for 256 CUs, +2.5 ms per 50-step slice);
+// FD_GRAM_TPW overrides both for experiments
+static int gram_tpw(int dtype_opts) {
+    const int gv = fd_dev(FD_DEV_GRAM_TPW), forced = gv >= 1 && gv <= 64 ? gv : 0;
+    return forced ? forced : ((dtype_opts & FD_OPT_LOW_LATENCY) ? 4 : 8);
+}
+
+static int dwgram_tpw(int ntiles) { return ntiles >= 256 ? 4 : (ntiles >= 64 ? 2 : 1); }
+
+static const char *pwdw_plan(int entry, int dtype_opts, int Cin, int Cdw, int Cz, int C, int B, int H, int W, fd_pwdw_plan *pl) {
+    fd_pwdw_plan q = {};
+    q.TW = PT_W;
+    q.gy = B;
+    q.gz = 1;
+    const int ntiles = (H / PT_H) * (W / PT_W);
+    // (4 consecutive tiles per workgroup once the batch fills the chip; ONE for a lone slice: 154.6 -> 152.8 ms per 50-step
+    //  slice at batch 1.  Tiles are independent: the split does not touch the results)
+    const int tpw_env = fd_dev(FD_DEV_PWDW_TPW);
+    const int tpw_b = tpw_env > 0 ? tpw_env : (B >= 4 ? 4 : 1);
+    if (entry == FD_PWDW_DW) {
+        if (const char *why = pwdw_refuses(dtype_opts, Cin, Cdw, Cz, H, W)) return why;
+        q.kernel = Cin == 64 ? FD_PWDW_K_64 : FD_PWDW_K_128;
+        q.tpw = tpw_b;
+        q.wgroups = Cz / 32 + Cdw / 32;
+        q.chunks = Cdw / 64;
+    } else if (entry == FD_PWDW_PROJ) {
+        // (`dtype | FD_OPT_LOW_LATENCY`: for ONE slice the row-GEMM on the stored v is the shorter chain -- 151.7 against
+        //  152.7 ms per 50-step slice at batch 1; the throughput set gains 0.8 % per batch-8 forward with this kernel)
+        if (fd_dev(FD_DEV_NO_PWDW_PROJ)) return "switched off";      // development switch
+        if (dtype_opts & FD_OPT_LOW_LATENCY) return "not in the low-latency kernel set";
+        if (Cin != 64) return "Cin is not 64";
+        if (const char *why = pwdw_refuses(dtype_opts, Cin, 64, 0, H, W)) return why;
+        q.kernel = FD_PWDW_K_64_PROJ;
+        q.tpw = tpw_b;
+        q.wgroups = 2;
+        q.chunks = 1;
+    } else if (entry == FD_PWDW_GRAM) {
+        if (fd_dev(FD_DEV_NO_GRAM_FUSE)) return "switched off";      // development switch
+        if (Cin != 64) return "Cin is not 64";                       // pwdw_gram_kernel is the 64-channel form
+        if (const char *why = pwdw_refuses(dtype_opts, Cin, 192, 0, H, W)) return why;
+        q.kernel = FD_PWDW_K_GRAM;
+        q.tpw = gram_tpw(dtype_opts);
+        q.wgroups = 6;                                               // v, q, k (out_v = NULL: the four of q and k)
+        q.chunks = 3;
+    } else if (entry == FD_PWDW_DWGRAM) {
+        if (fd_dev(FD_DEV_NO_DWGRAM)) return "switched off";         // development switch
+        if (dtype_opts != FD_BF16) return "dtype is not the 16-bit type";      // (this entry takes no FD_OPT_* bits)
+        if (C < 64 || C % 64) return "C is no positive multiple of 64";
+        if (H % PT_H) return "H % 8";
+        if (W % PT_W) return "W % 16";
+        if ((int64_t)H * W * 3 * C >= (1ll << 31)) return "H * W * 3 C >= 2^31 (32-bit element offsets)";
+        q.kernel = FD_PWDW_K_DWGRAM;
+        q.tpw = dwgram_tpw(ntiles);
+        q.gy = C / 64;
+        q.gz = B;
+        q.wgroups = 0;
+        q.chunks = 2;                                                // q, k
+    } else {
+        return "no such entry";
+    }
+    q.ntiles = ntiles;
+    q.gx = (ntiles + q.tpw - 1) / q.tpw;
+    *pl = q;
+    return nullptr;
+}
+
+extern "C" int fd_pw_dw3x3_plan(int entry, int dtype_opts, int Cin, int Cdw, int Cz, int C, int B, int H, int W, int *out) {
+    fd_pwdw_plan pl = {};
+    const bool f32 = entry == FD_PWDW_F32 || entry == FD_PWDW_GRAM_F32 || entry == FD_PWDW_PROJ_F32;
+    if (f32 ? fd_pwdw32_plan(entry, dtype_opts, Cin, Cdw, B, H, W, &pl) : pwdw_plan(entry, dtype_opts, Cin, Cdw, Cz, C, B, H, W, &pl)) return 0;
+    const int f[FD_PWDW_PLAN_FIELDS] = {pl.kernel, pl.TW, pl.ntiles, pl.tpw, pl.gx, pl.gy, pl.gz, pl.wgroups, pl.chunks};
+    for (int i = 0; i < FD_PWDW_PLAN_FIELDS; ++i) out[i] = f[i];
+    return 1;
+}
+
+extern "C" int fd_pw_dw3x3_ok(int dtype_opts, int Cin, int Cdw, int Cz, int H, int W) {
+    return !pwdw_refuses(dtype_opts, Cin, Cdw, Cz, H, W);
 }
 
 extern "C" int fd_pw_dw3x3(int dtype, const void *x, int ld_x, int off_x, int Cin, const float *ln_gamma,
@@ -835,7 +935,8 @@ extern "C" int fd_pw_dw3x3(int dtype, const void *x, int ld_x, int off_x, int Ci
                            int dw_silu, void *out_dw, int ld_dw, int off_dw, int Cz, void *out_z, int ld_z,
                            int off_z, int B, int H, int W, void *stream) {
     dtype &= 0xff;
-    FD_REQUIRE(fd_pw_dw3x3_ok(dtype, Cin, Cdw, Cz, H, W),
+    fd_pwdw_plan pl;
+    FD_REQUIRE(!pwdw_plan(FD_PWDW_DW, dtype, Cin, Cdw, Cz, 0, B, H, W, &pl),
                "fd_pw_dw3x3: unsupported shape (bf16, Cin=64|128, Cdw%%64, Cz%%32, H%%8, W%%16, >= 32768 px): "
                "Cin=%d Cdw=%d Cz=%d H=%d W=%d", Cin, Cdw, Cz, H, W);
     FD_REQUIRE(x && ln_shift && ln_scale && w_pw && w_dw && out_dw && (Cz == 0 || out_z), "fd_pw_dw3x3: null pointer");
@@ -850,14 +951,11 @@ extern "C" int fd_pw_dw3x3(int dtype, const void *x, int ld_x, int off_x, int Ci
     p.out_dw = (bf16 *)out_dw; p.ld_dw = ld_dw; p.off_dw = off_dw;
     p.Cz = Cz; p.out_z = (bf16 *)out_z; p.ld_z = ld_z; p.off_z = off_z;
     p.H = H; p.W = W;
-    p.ntiles = (H / PT_H) * (W / PT_W);
-    const int tpw_env = fd_dev(FD_DEV_PWDW_TPW);
-    // (4 consecutive tiles per workgroup once the batch fills the chip; ONE for a lone slice: 154.6 -> 152.8 ms per 50-step
-    //  slice at batch 1.  Tiles are independent: the split does not touch the results)
-    p.tpw = tpw_env > 0 ? tpw_env : (B >= 4 ? 4 : 1);
-    dim3 grid((p.ntiles + p.tpw - 1) / p.tpw, B), block(256);
+    p.ntiles = pl.ntiles;
+    p.tpw = pl.tpw;
+    dim3 grid(pl.gx, pl.gy), block(256);
     const size_t pad = fd_occ_pad(FD_DEV_PAD_PWDW);
-    if (Cin == 64) hipLaunchKernelGGL(pwdw_kernel<64>, grid, block, pad, (hipStream_t)stream, p);
+    if (pl.kernel == FD_PWDW_K_64) hipLaunchKernelGGL(pwdw_kernel<64>, grid, block, pad, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(pwdw_kernel<128>, grid, block, pad, (hipStream_t)stream, p);
     FD_LAUNCH_OK("fd_pw_dw3x3");
     return FD_OK;
@@ -868,17 +966,16 @@ extern "C" int fd_pw_dw3x3(int dtype, const void *x, int ld_x, int off_x, int Ci
 // w_pw [64][64] (the v rows of qkv.weight), w_dw [9][32] fp16 channel pairs (the v taps of qkv_dwconv), w2 [B][64][64]
 // (fd_chan_attn_weff's output).  With fd_pw_dw3x3_gram(out_v = NULL) in front, v never reaches HBM.
 extern "C" int fd_pw_dw3x3_proj_ok(int dtype_opts, int Cin, int H, int W) {
-    const bool off = fd_dev(FD_DEV_NO_PWDW_PROJ);      // development switch
-    // (`dtype | FD_OPT_LOW_LATENCY`: for ONE slice the row-GEMM on the stored v is the shorter chain -- 151.7 against
-    //  152.7 ms per 50-step slice at batch 1; the throughput set gains 0.8 % per batch-8 forward with this kernel)
-    return !off && !(dtype_opts & FD_OPT_LOW_LATENCY) && Cin == 64 && fd_pw_dw3x3_ok(dtype_opts, Cin, 64, 0, H, W);
+    fd_pwdw_plan pl;
+    return !pwdw_plan(FD_PWDW_PROJ, dtype_opts, Cin, 64, 0, 0, 1, H, W, &pl);
 }
 
 extern "C" int fd_pw_dw3x3_proj(int dtype, const void *x, int ld_x, int off_x, int Cin, const float *ln_gamma,
                                 const float *ln_beta, float ln_eps, const float *ln_shift, const float *ln_scale,
                                 int ln_ld, const void *w_pw, const uint32_t *w_dw, const void *w2, const float *gate,
                                 int gate_ld, void *out, int ld_o, int off_o, int B, int H, int W, void *stream) {
-    FD_REQUIRE(fd_pw_dw3x3_proj_ok(dtype & 0xff, Cin, H, W),
+    fd_pwdw_plan pl;
+    FD_REQUIRE(!pwdw_plan(FD_PWDW_PROJ, dtype & 0xff, Cin, 64, 0, 0, B, H, W, &pl),
                "fd_pw_dw3x3_proj: unsupported shape (bf16, Cin=64, H%%8, W%%16, >= 32768 px): Cin=%d H=%d W=%d", Cin, H, W);
     FD_REQUIRE(x && ln_shift && ln_scale && w_pw && w_dw && w2 && gate && out, "fd_pw_dw3x3_proj: null pointer");
     FD_REQUIRE(ld_x % 8 == 0 && off_x % 8 == 0 && ld_o % 8 == 0 && off_o % 8 == 0,
@@ -894,28 +991,18 @@ extern "C" int fd_pw_dw3x3_proj(int dtype, const void *x, int ld_x, int off_x, i
     p.w2 = (const bf16 *)w2; p.w2_bstride = 64 * 64; p.gate = gate; p.gate_ld = gate_ld;
     p.out2 = (bf16 *)out; p.ld_o2 = ld_o; p.off_o2 = off_o;
     p.H = H; p.W = W;
-    p.ntiles = (H / PT_H) * (W / PT_W);
-    const int tpw_env = fd_dev(FD_DEV_PWDW_TPW);
-    p.tpw = tpw_env > 0 ? tpw_env : (B >= 4 ? 4 : 1);
-    dim3 grid((p.ntiles + p.tpw - 1) / p.tpw, B), block(256);
+    p.ntiles = pl.ntiles;
+    p.tpw = pl.tpw;
+    dim3 grid(pl.gx, pl.gy), block(256);
     const size_t pad = fd_occ_pad(FD_DEV_PAD_PWDW);
     hipLaunchKernelGGL((pwdw_kernel<64, true>), grid, block, pad, (hipStream_t)stream, p);
     FD_LAUNCH_OK("fd_pw_dw3x3_proj");
     return FD_OK;
 }
 
-// tiles per workgroup of the Gram-fused qkv kernel: a constant of the kernel set (the order of the partial sums, hence
-// the result, must not depend on the batch): 8 in the throughput set (round 4: -0.3 % per batch-8 forward against 4;
-// 16: +0.6 %), 4 under FD_OPT_LOW_LATENCY (one slice: 8 leaves 256 workgroups for 256 CUs, +2.5 ms per 50-step slice);
-// FD_GRAM_TPW overrides both for experiments
-static int gram_tpw(int dtype_opts) {
-    const int gv = fd_dev(FD_DEV_GRAM_TPW), forced = gv >= 1 && gv <= 64 ? gv : 0;
-    return forced ? forced : ((dtype_opts & FD_OPT_LOW_LATENCY) ? 4 : 8);
-}
-
 extern "C" int fd_pw_dw3x3_gram_ok(int dtype, int Cin, int H, int W) {
-    const bool off = fd_dev(FD_DEV_NO_GRAM_FUSE);      // development switch
-    return !off && Cin == 64 && fd_pw_dw3x3_ok(dtype, Cin, 192, 0, H, W);      // pwdw_gram_kernel is the 64-channel form
+    fd_pwdw_plan pl;
+    return !pwdw_plan(FD_PWDW_GRAM, dtype, Cin, 192, 0, 0, 1, H, W, &pl);
 }
 
 extern "C" int fd_pw_dw3x3_gram_nblk_opts(int dtype_opts, int H, int W) {
@@ -929,9 +1016,8 @@ extern "C" int fd_pw_dw3x3_gram(int dtype, const void *x, int ld_x, int off_x, i
                                 const float *ln_beta, float ln_eps, const float *ln_shift, const float *ln_scale,
                                 int ln_ld, const void *w_pw, const uint32_t *w_dw, void *out_v, int ld_v, int off_v,
                                 float *partial, int B, int H, int W, void *stream) {
-    const int dtype_opts = dtype;
-    dtype &= 0xff;
-    FD_REQUIRE(fd_pw_dw3x3_ok(dtype, Cin, 192, 0, H, W),
+    fd_pwdw_plan pl;
+    FD_REQUIRE(!pwdw_plan(FD_PWDW_GRAM, dtype, Cin, 192, 0, 0, B, H, W, &pl),
                "fd_pw_dw3x3_gram: unsupported shape (bf16, Cin=64, H%%8, W%%16, >= 32768 px): Cin=%d H=%d W=%d", Cin, H, W);
     FD_REQUIRE(x && ln_shift && ln_scale && w_pw && w_dw && partial, "fd_pw_dw3x3_gram: null pointer");      // out_v may be NULL: q, k only
     FD_REQUIRE(ld_x % 8 == 0 && off_x % 8 == 0 && ld_v % 8 == 0 && off_v % 8 == 0,
@@ -942,9 +1028,9 @@ extern "C" int fd_pw_dw3x3_gram(int dtype, const void *x, int ld_x, int off_x, i
     p.ln_gamma = ln_gamma; p.ln_beta = ln_beta; p.ln_shift = ln_shift; p.ln_scale = ln_scale; p.ln_ld = ln_ld; p.ln_eps = ln_eps;
     p.w_pw = (const bf16 *)w_pw; p.w_dw = w_dw;
     p.out_v = (bf16 *)out_v; p.ld_v = ld_v; p.off_v = off_v;
-    p.part = partial; p.nblk = fd_pw_dw3x3_gram_nblk_opts(dtype_opts, H, W);
-    p.H = H; p.W = W; p.tpw = gram_tpw(dtype_opts); p.ntiles = (H / PT_H) * (W / PT_W);
-    dim3 grid(p.nblk, B), block(256);
+    p.part = partial; p.nblk = pl.gx;
+    p.H = H; p.W = W; p.tpw = pl.tpw; p.ntiles = pl.ntiles;
+    dim3 grid(pl.gx, pl.gy), block(256);
     const size_t pad = fd_occ_pad(FD_DEV_PAD_PWDW);
     hipLaunchKernelGGL(pwdw_gram_kernel, grid, block, pad, (hipStream_t)stream, p);
     FD_LAUNCH_OK("fd_pw_dw3x3_gram");
@@ -952,12 +1038,9 @@ extern "C" int fd_pw_dw3x3_gram(int dtype, const void *x, int ld_x, int off_x, i
 }
 
 // ---- qkv_dwconv + Gram for C >= 128 (dwconv_gram_kernel): q, k of a [B,H,W,ld] qkv tensor -> Gram partials only
-static int dwgram_tpw(int ntiles) { return ntiles >= 256 ? 4 : (ntiles >= 64 ? 2 : 1); }
-
 extern "C" int fd_dwconv_gram_ok(int dtype, int C, int H, int W) {
-    const bool off = fd_dev(FD_DEV_NO_DWGRAM);         // development switch
-    return !off && dtype == FD_BF16 && C % 64 == 0 && C >= 64 && H % PT_H == 0 && W % PT_W == 0 &&
-           (int64_t)H * W * 3 * C < (1ll << 31);
+    fd_pwdw_plan pl;
+    return !pwdw_plan(FD_PWDW_DWGRAM, dtype, 0, 0, 0, C, 1, H, W, &pl);
 }
 
 extern "C" int fd_dwconv_gram_nblk(int H, int W) {
@@ -967,12 +1050,14 @@ extern "C" int fd_dwconv_gram_nblk(int H, int W) {
 
 extern "C" int fd_dwconv_gram(int dtype, const void *qkv, int ld, int C, const uint32_t *w_dw, float *partial, int B, int H,
                               int W, void *stream) {
-    FD_REQUIRE(fd_dwconv_gram_ok(dtype, C, H, W), "fd_dwconv_gram: unsupported shape (bf16, C %% 64, H %% 8, W %% 16): C=%d H=%d W=%d", C, H, W);
+    fd_pwdw_plan pl;
+    FD_REQUIRE(!pwdw_plan(FD_PWDW_DWGRAM, dtype, 0, 0, 0, C, B, H, W, &pl),
+               "fd_dwconv_gram: unsupported shape (bf16, C %% 64, H %% 8, W %% 16): C=%d H=%d W=%d", C, H, W);
     FD_REQUIRE(qkv && w_dw && partial && ld % 8 == 0 && ld >= 2 * C && ((uintptr_t)w_dw & 15) == 0, "fd_dwconv_gram: bad args");
     DwGramParams p;
     p.qkv = (const bf16 *)qkv; p.ld = ld; p.C = C; p.w_dw = w_dw; p.part = partial;
-    p.H = H; p.W = W; p.ntiles = (H / PT_H) * (W / PT_W); p.tpw = dwgram_tpw(p.ntiles); p.nblk = fd_dwconv_gram_nblk(H, W);
-    dim3 grid(p.nblk, C / 64, B), block(256);
+    p.H = H; p.W = W; p.ntiles = pl.ntiles; p.tpw = pl.tpw; p.nblk = pl.gx;
+    dim3 grid(pl.gx, pl.gy, pl.gz), block(256);
     hipLaunchKernelGGL(dwconv_gram_kernel, grid, block, 0, (hipStream_t)stream, p);
     FD_LAUNCH_OK("fd_dwconv_gram");
     return FD_OK;

@@ -340,8 +340,15 @@ __global__ __launch_bounds__(256, 2) void pwdw32_kernel(const Pw32Params p) {
 
 constexpr int PW32_GRAM_TPW = 16;       // 8 x 8 tiles per workgroup of the Gram form: fixes the order of the partial sums
 
-bool pw32_shape_ok(int dtype, int Cin, int H, int W, int TW) {
-    return dtype == FD_F32 && Cin == 64 && H % 8 == 0 && W % TW == 0 && (int64_t)H * W >= 16384 && (int64_t)H * W * 256 < (1ll << 31);
+// what refuses a shape (NULL: served); TW = 16 for the DW form, 8 for GRAM / PROJ
+const char *pw32_refuses(int dtype, int Cin, int H, int W, int TW) {
+    if (dtype != FD_F32) return "dtype is not fp32";
+    if (Cin != 64) return "Cin is not 64";
+    if (H % 8) return "H % 8";
+    if (W % TW) return TW == 16 ? "W % 16" : "W % 8";
+    if ((int64_t)H * W < 16384) return "fewer than 16384 px";
+    if ((int64_t)H * W * 256 >= (1ll << 31)) return "H * W * 256 >= 2^31";
+    return nullptr;
 }
 
 void pw32_common(Pw32Params &p, const void *x, int ld_x, int off_x, const float *ln_gamma, const float *ln_beta, float ln_eps,
@@ -352,68 +359,108 @@ void pw32_common(Pw32Params &p, const void *x, int ld_x, int off_x, const float 
 }
 
 template <int MODE, int TW>
-void pw32_launch(const Pw32Params &p, int B, hipStream_t s) {
+void pw32_launch(Pw32Params &p, const fd_pwdw_plan &pl, hipStream_t s) {
     constexpr size_t lds = pw32_lds<MODE, TW>();
     static_assert(lds <= 80 * 1024, "pwdw32_kernel: two workgroups per CU");
     (void)hipFuncSetAttribute((const void *)pwdw32_kernel<MODE, TW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    dim3 grid((p.ntiles + p.tpw - 1) / p.tpw, B), block(256);
+    p.tpw = pl.tpw;
+    p.nchunk = pl.chunks;
+    dim3 grid(pl.gx, pl.gy), block(256);
     hipLaunchKernelGGL((pwdw32_kernel<MODE, TW>), grid, block, lds, s, p);
 }
 
 }  // namespace
 
+// The launch plan of the three fp32-storage entry points (fd_pw_dw3x3_plan reports it, every launch runs it)
+const char *fd_pwdw32_plan(int entry, int dtype_opts, int Cin, int Cdw, int B, int H, int W, fd_pwdw_plan *pl) {
+    if (entry != FD_PWDW_F32 && entry != FD_PWDW_GRAM_F32 && entry != FD_PWDW_PROJ_F32) return "no such entry";
+    fd_pwdw_plan q = {};
+    q.TW = entry == FD_PWDW_F32 ? 16 : 8;
+    if (const char *why = pw32_refuses(dtype_opts & 0xff, Cin, H, W, q.TW)) return why;
+    if (entry == FD_PWDW_F32) {
+        if (Cdw <= 0 || Cdw % 32 || Cdw > 128) return "Cdw is no multiple of 32 in 32 .. 128";      // (taps of <= 128 channels staged in LDS)
+        q.kernel = FD_PWDW_K_32_DW;
+        q.tpw = B >= 4 ? 4 : 1;             // tiles are independent: the split does not touch the results
+        q.chunks = Cdw / 32;
+    } else if (entry == FD_PWDW_GRAM_F32) {
+        q.kernel = FD_PWDW_K_32_GRAM;
+        q.tpw = PW32_GRAM_TPW;
+        q.chunks = 4;                       // q, k of head 0, q, k of head 1
+    } else {
+        q.kernel = FD_PWDW_K_32_PROJ;
+        q.tpw = B >= 4 ? 8 : 2;
+        q.chunks = 2;
+    }
+    q.wgroups = q.chunks;                   // one 32-row weight group per 32-channel chunk
+    q.ntiles = (H / 8) * (W / q.TW);
+    q.gx = (q.ntiles + q.tpw - 1) / q.tpw;
+    q.gy = B;
+    q.gz = 1;
+    *pl = q;
+    return nullptr;
+}
+
 extern "C" int fd_pw_dw3x3_f32_ok(int dtype, int Cin, int Cdw, int H, int W) {
-    return pw32_shape_ok(dtype & 0xff, Cin, H, W, 16) && Cdw > 0 && Cdw % 32 == 0 && Cdw <= 128;      // (taps of <= 128 channels staged in LDS)
+    fd_pwdw_plan pl;
+    return !fd_pwdw32_plan(FD_PWDW_F32, dtype, Cin, Cdw, 1, H, W, &pl);
 }
 
 extern "C" int fd_pw_dw3x3_f32(const void *x, int ld_x, int off_x, int Cin, const float *ln_gamma, const float *ln_beta,
                                float ln_eps, const float *ln_shift, const float *ln_scale, int ln_ld, const void *w_pw_hi, const void *w_pw_lo, int Cdw,
                                const float *w_dw, const float *b_dw, int dw_silu, void *out_dw, int ld_dw, int off_dw, int B, int H,
                                int W, void *stream) {
-    FD_REQUIRE(fd_pw_dw3x3_f32_ok(FD_F32, Cin, Cdw, H, W), "fd_pw_dw3x3_f32: unsupported shape (Cin=64, Cdw%%32, H%%8, W%%16, >= 16384 px): "
-               "Cin=%d Cdw=%d H=%d W=%d", Cin, Cdw, H, W);
+    fd_pwdw_plan pl;
+    const char *why = fd_pwdw32_plan(FD_PWDW_F32, FD_F32, Cin, Cdw, B, H, W, &pl);
+    FD_REQUIRE(!why, "fd_pw_dw3x3_f32: unsupported shape (%s): Cin=%d Cdw=%d H=%d W=%d", why, Cin, Cdw, H, W);
     FD_REQUIRE(x && ln_shift && ln_scale && w_pw_hi && w_pw_lo && w_dw && out_dw, "fd_pw_dw3x3_f32: null pointer");
     FD_REQUIRE(ld_x % 4 == 0 && off_x % 4 == 0 && ld_dw % 4 == 0 && off_dw % 4 == 0, "fd_pw_dw3x3_f32: strides / offsets must be multiples of 4 channels");
     FD_REQUIRE((((uintptr_t)x | (uintptr_t)w_pw_hi | (uintptr_t)w_pw_lo | (uintptr_t)w_dw | (uintptr_t)out_dw | (uintptr_t)b_dw) & 15) == 0, "fd_pw_dw3x3_f32: 16-byte alignment");
     Pw32Params p = {};
     pw32_common(p, x, ld_x, off_x, ln_gamma, ln_beta, ln_eps, ln_shift, ln_scale, ln_ld, H, W, 16);
-    p.w_hi = (const bf16 *)w_pw_hi; p.w_lo = (const bf16 *)w_pw_lo; p.w_dw = w_dw; p.ld_wdw = Cdw; p.b_dw = b_dw; p.dw_silu = dw_silu; p.nchunk = Cdw / 32; p.ntap_ch = Cdw;
+    p.w_hi = (const bf16 *)w_pw_hi; p.w_lo = (const bf16 *)w_pw_lo; p.w_dw = w_dw; p.ld_wdw = Cdw; p.b_dw = b_dw; p.dw_silu = dw_silu; p.ntap_ch = Cdw;
     p.out = (float *)out_dw; p.ld_o = ld_dw; p.off_o = off_dw;
-    p.tpw = B >= 4 ? 4 : 1;             // tiles are independent: the split does not touch the results
-    pw32_launch<PW32_DW, 16>(p, B, (hipStream_t)stream);
+    pw32_launch<PW32_DW, 16>(p, pl, (hipStream_t)stream);
     FD_LAUNCH_OK("fd_pw_dw3x3_f32");
     return FD_OK;
 }
 
-extern "C" int fd_pw_dw3x3_gram_f32_ok(int dtype, int Cin, int H, int W) { return pw32_shape_ok(dtype & 0xff, Cin, H, W, 8); }
+extern "C" int fd_pw_dw3x3_gram_f32_ok(int dtype, int Cin, int H, int W) {
+    fd_pwdw_plan pl;
+    return !fd_pwdw32_plan(FD_PWDW_GRAM_F32, dtype, Cin, 0, 1, H, W, &pl);
+}
 
 extern "C" int fd_pw_dw3x3_gram_f32_nblk(int H, int W) { return ((H / 8) * (W / 8) + PW32_GRAM_TPW - 1) / PW32_GRAM_TPW; }
 
 extern "C" int fd_pw_dw3x3_gram_f32(const void *x, int ld_x, int off_x, int Cin, const float *ln_gamma, const float *ln_beta,
                                     float ln_eps, const float *ln_shift, const float *ln_scale, int ln_ld, const void *w_pw_hi, const void *w_pw_lo,
                                     const float *w_dw, int ld_wdw, float *partial, int B, int H, int W, void *stream) {
-    FD_REQUIRE(fd_pw_dw3x3_gram_f32_ok(FD_F32, Cin, H, W), "fd_pw_dw3x3_gram_f32: unsupported shape (Cin=64, H%%8, W%%8, >= 16384 px): "
-               "Cin=%d H=%d W=%d", Cin, H, W);
+    fd_pwdw_plan pl;
+    const char *why = fd_pwdw32_plan(FD_PWDW_GRAM_F32, FD_F32, Cin, 0, B, H, W, &pl);
+    FD_REQUIRE(!why, "fd_pw_dw3x3_gram_f32: unsupported shape (%s): Cin=%d H=%d W=%d", why, Cin, H, W);
     FD_REQUIRE(x && ln_shift && ln_scale && w_pw_hi && w_pw_lo && w_dw && partial, "fd_pw_dw3x3_gram_f32: null pointer");
     FD_REQUIRE(ld_x % 4 == 0 && off_x % 4 == 0 && ld_wdw % 4 == 0 && ld_wdw >= 128, "fd_pw_dw3x3_gram_f32: strides / offsets must be multiples of 4 channels");
     FD_REQUIRE((((uintptr_t)x | (uintptr_t)w_pw_hi | (uintptr_t)w_pw_lo | (uintptr_t)w_dw) & 15) == 0, "fd_pw_dw3x3_gram_f32: 16-byte alignment");
     Pw32Params p = {};
     pw32_common(p, x, ld_x, off_x, ln_gamma, ln_beta, ln_eps, ln_shift, ln_scale, ln_ld, H, W, 8);
-    p.w_hi = (const bf16 *)w_pw_hi; p.w_lo = (const bf16 *)w_pw_lo; p.w_dw = w_dw; p.ld_wdw = ld_wdw; p.nchunk = 4; p.ntap_ch = 128;
-    p.part = partial; p.nblk = fd_pw_dw3x3_gram_f32_nblk(H, W); p.tpw = PW32_GRAM_TPW;
-    pw32_launch<PW32_GRAM, 8>(p, B, (hipStream_t)stream);
+    p.w_hi = (const bf16 *)w_pw_hi; p.w_lo = (const bf16 *)w_pw_lo; p.w_dw = w_dw; p.ld_wdw = ld_wdw; p.ntap_ch = 128;
+    p.part = partial; p.nblk = pl.gx;
+    pw32_launch<PW32_GRAM, 8>(p, pl, (hipStream_t)stream);
     FD_LAUNCH_OK("fd_pw_dw3x3_gram_f32");
     return FD_OK;
 }
 
-extern "C" int fd_pw_dw3x3_proj_f32_ok(int dtype, int Cin, int H, int W) { return pw32_shape_ok(dtype & 0xff, Cin, H, W, 8); }
+extern "C" int fd_pw_dw3x3_proj_f32_ok(int dtype, int Cin, int H, int W) {
+    fd_pwdw_plan pl;
+    return !fd_pwdw32_plan(FD_PWDW_PROJ_F32, dtype, Cin, 0, 1, H, W, &pl);
+}
 
 extern "C" int fd_pw_dw3x3_proj_f32(const void *x, int ld_x, int off_x, int Cin, const float *ln_gamma, const float *ln_beta,
                                     float ln_eps, const float *ln_shift, const float *ln_scale, int ln_ld, const void *w_pw_hi, const void *w_pw_lo,
                                     const float *w_dw, int ld_wdw, const float *w2, const float *gate, int gate_ld, void *out,
                                     int ld_o, int off_o, int B, int H, int W, void *stream) {
-    FD_REQUIRE(fd_pw_dw3x3_proj_f32_ok(FD_F32, Cin, H, W), "fd_pw_dw3x3_proj_f32: unsupported shape (Cin=64, H%%8, W%%8, >= 16384 px): "
-               "Cin=%d H=%d W=%d", Cin, H, W);
+    fd_pwdw_plan pl;
+    const char *why = fd_pwdw32_plan(FD_PWDW_PROJ_F32, FD_F32, Cin, 0, B, H, W, &pl);
+    FD_REQUIRE(!why, "fd_pw_dw3x3_proj_f32: unsupported shape (%s): Cin=%d H=%d W=%d", why, Cin, H, W);
     FD_REQUIRE(x && ln_shift && ln_scale && w_pw_hi && w_pw_lo && w_dw && w2 && gate && out, "fd_pw_dw3x3_proj_f32: null pointer");
     FD_REQUIRE(ld_x % 4 == 0 && off_x % 4 == 0 && ld_o % 4 == 0 && off_o % 4 == 0 && ld_wdw % 4 == 0 && gate_ld % 4 == 0,
                "fd_pw_dw3x3_proj_f32: strides / offsets must be multiples of 4 channels");
@@ -421,11 +468,10 @@ extern "C" int fd_pw_dw3x3_proj_f32(const void *x, int ld_x, int off_x, int Cin,
                "fd_pw_dw3x3_proj_f32: 16-byte alignment");
     Pw32Params p = {};
     pw32_common(p, x, ld_x, off_x, ln_gamma, ln_beta, ln_eps, ln_shift, ln_scale, ln_ld, H, W, 8);
-    p.w_hi = (const bf16 *)w_pw_hi; p.w_lo = (const bf16 *)w_pw_lo; p.w_dw = w_dw; p.ld_wdw = ld_wdw; p.nchunk = 2; p.ntap_ch = 64;
+    p.w_hi = (const bf16 *)w_pw_hi; p.w_lo = (const bf16 *)w_pw_lo; p.w_dw = w_dw; p.ld_wdw = ld_wdw; p.ntap_ch = 64;
     p.w2 = w2; p.gate = gate; p.gate_ld = gate_ld;
     p.out = (float *)out; p.ld_o = ld_o; p.off_o = off_o;
-    p.tpw = B >= 4 ? 8 : 2;
-    pw32_launch<PW32_PROJ, 8>(p, B, (hipStream_t)stream);
+    pw32_launch<PW32_PROJ, 8>(p, pl, (hipStream_t)stream);
     FD_LAUNCH_OK("fd_pw_dw3x3_proj_f32");
     return FD_OK;
 }

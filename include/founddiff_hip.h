@@ -318,6 +318,31 @@ int fd_dwconv_gram_nblk(int H, int W);
 int fd_dwconv_gram(int dtype, const void *qkv, int ld, int C, const uint32_t *w_dw, float *partial, int B, int H, int W,
                    void *stream);
 
+/* The launch plan of the seven entry points above.  Host only: touches no device.  Returns 1 and fills out[0 .. 8] when the matching
+ * _ok query serves the shape, 0 (out untouched) otherwise; every launch runs exactly this plan.  entry = FD_PWDW_*; Cdw, Cz are read by
+ * FD_PWDW_DW (Cdw also by FD_PWDW_F32), C by FD_PWDW_DWGRAM only.  Field order:
+ *   [0] kernel, FD_PWDW_K_*   [1] tile width (tiles are 8 rows high)   [2] tiles per image   [3] tpw: consecutive tiles per workgroup
+ *   [4] grid x = ceil(tiles / tpw): workgroup x walks tiles x * tpw .. ; equals the _nblk query of the Gram entries
+ *   [5] grid y (images; fd_dwconv_gram: pairs of heads)   [6] grid z (fd_dwconv_gram: images)
+ *   [7] 32-row groups of 1x1 weights per tile (pass-through groups first; 0 for fd_dwconv_gram)
+ *   [8] depthwise chunks per tile (64 channels; 32 in the fp32-storage kernels)                                              */
+#define FD_PWDW_DW 0          /* fd_pw_dw3x3 */
+#define FD_PWDW_PROJ 1        /* fd_pw_dw3x3_proj */
+#define FD_PWDW_GRAM 2        /* fd_pw_dw3x3_gram */
+#define FD_PWDW_DWGRAM 3      /* fd_dwconv_gram */
+#define FD_PWDW_F32 4         /* fd_pw_dw3x3_f32 */
+#define FD_PWDW_GRAM_F32 5    /* fd_pw_dw3x3_gram_f32 */
+#define FD_PWDW_PROJ_F32 6    /* fd_pw_dw3x3_proj_f32 */
+#define FD_PWDW_K_64 0        /* pwdw_kernel<64> */
+#define FD_PWDW_K_128 1       /* pwdw_kernel<128> */
+#define FD_PWDW_K_64_PROJ 2   /* pwdw_kernel<64, PROJ> */
+#define FD_PWDW_K_GRAM 3      /* pwdw_gram_kernel */
+#define FD_PWDW_K_DWGRAM 4    /* dwconv_gram_kernel */
+#define FD_PWDW_K_32_DW 5     /* pwdw32_kernel<DW, 16> */
+#define FD_PWDW_K_32_GRAM 6   /* pwdw32_kernel<GRAM, 8> */
+#define FD_PWDW_K_32_PROJ 7   /* pwdw32_kernel<PROJ, 8> */
+int fd_pw_dw3x3_plan(int entry, int dtype_opts, int Cin, int Cdw, int Cz, int C, int B, int H, int W, int *out);
+
 /* ---- SS2D selective scan (replaces selective_scan_cuda_core.fwd, src/emamba2.py:154, together
  * with EfficientScan/EfficientMerge index maps 182-262, dt_proj einsum 340, softplus/bias).
  *   xc    [B,H,W,D]    (dtype)  dwconv+SiLU output, D = d_inner = 2C

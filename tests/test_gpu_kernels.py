@@ -786,7 +786,8 @@ def test_conv3x3_weights_in_registers(eng_factory, hw):
 @pytest.mark.parametrize("cfg", [dict(cdw=128, cz=128, silu=1, bias=True, affine=True, hw=(128, 256)),     # SS2D in_proj + conv2d
                                  dict(cdw=192, cz=0, silu=0, bias=False, affine=False, hw=(256, 128)),    # qkv + qkv_dwconv
                                  dict(cdw=256, cz=256, silu=1, bias=True, affine=True, hw=(128, 256), cin=128),   # C = 128 in_proj
-                                 dict(cdw=256, cz=256, silu=1, bias=True, affine=True, hw=(264, 144), cin=128)])  # ragged tile count
+                                 dict(cdw=256, cz=256, silu=1, bias=True, affine=True, hw=(264, 144), cin=128)])  # 297 tiles (B = 2: one per workgroup; the
+                                 # several-tiles walk and its ragged last workgroup: tests/test_gpu_pwdw_forms.py)
 def test_pw_dw3x3_fused(eng_factory, cfg):
     """Fused LN+modulate -> 1x1 -> depthwise 3x3 (bf16) against the unfused fp32 composition; borders
     included (the depthwise conv zero-pads the 1x1 OUTPUT)."""
